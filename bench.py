@@ -1,7 +1,7 @@
 """Headline benchmark: audio-frames/s of the ConformerCTC(S) hot path (waveform -> CTC greedy token ids) on
 N MI355X GPUs, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,9 @@ A "step" = one pass of mi355asr_recognize over one batch of 64 synthetic 10-seco
 already resident in HBM (BASELINE.json configs[1]; weak scaling: 64 utterances per GPU at every N), followed --
 when N > 1 -- by the all_gather of the token ids.  1 audio frame = one 10 ms feature hop (am_data.yml:8), so a
 10 s utterance is 1000 frames.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
+(float64; the inputs are seeded, so two builds run with the same arguments can be compared output for output).
 """
 import argparse
 import ctypes
@@ -611,10 +614,13 @@ def config5_main(args, world, rank, device, use_dist):
     B, L = 16, 480000
     wav = torch.from_numpy(synth_batch(rank * B, B, L)).to(device)
 
+    last = [None]
+
     def step():
         logits, counts = m.predict(wav)
         hyp = ctc_prefix_beam_decode(logits, counts, beam_width=10, cutoff_prob=0.99, cutoff_top_n=40, is_logits=True)
-        return all_gather_hypotheses(*hyp, device=device) if use_dist else hyp
+        last[0] = all_gather_hypotheses(*hyp, device=device) if use_dist else hyp
+        return last[0]
 
     for _ in range(args.warmup):
         step()
@@ -633,6 +639,8 @@ def config5_main(args, world, rank, device, use_dist):
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("ids", "lens", "scores", "n_hyp"), last[0])))
     if rank == 0:
         del m
         torch.cuda.empty_cache()
@@ -757,6 +765,14 @@ def repeated_regions(region, steps, min_s, dist, use_dist, device):
             return sum(times), times
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: tensor or array} -> out_dir/<name>.npy in float64 (ids, lengths and float32 scores are all exact in float64)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def region_stats(times, steps):
     per = sorted(t / steps * 1e3 for t in times)
     return {"regions": len(per), "min": round(per[0], 4), "median": round(per[len(per) // 2], 4), "max": round(per[-1], 4)}
@@ -843,9 +859,15 @@ def main():
     ap.add_argument("--exact-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="do not record per-kernel HIP events in the timed region (roofline fields become null)")
-    ap.add_argument("--min-timed-s", type=float, default=1.0,
-                    help="the headline region is repeated (whole K-step regions, each bracketed by barrier + synchronize) until this "
-                         "much time has been measured; ms_per_step = total time / total steps")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="0 (default): the headline region is exactly --steps steps.  > 0: whole K-step regions (each bracketed by "
+                         "barrier + synchronize) are repeated until this much time has been measured; ms_per_step = total time / total steps")
+    ap.add_argument("--min-warmup-s", type=float, default=1.0,
+                    help="after the --warmup steps, untimed K-step regions run until this much time has passed (steady clocks "
+                         "before the headline region; 0: none)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (config 2: ids, lens; config 5: ids, lens, scores, n_hyp) "
+                         "as DIR/<name>.npy in float64")
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="no GPU, no kernels: the launcher, the process group (gloo), the per-step id exchange, the max-over-ranks "
                          "timing and the JSON line with a stand-in recogniser (tests/test_distributed_cpu.py)")
@@ -900,10 +922,12 @@ def main():
         from tensorflowasr_amd.parallel import ids_lens_buffer
         rot = [ids_lens_buffer(B, T, device) for _ in range(3)]
     nstep = [0]
+    last = [None]                                                # (ids, lens) the latest step returned
 
     def step():
         if use_dist:
             ids, lens = model.recognize(wav, out=rot[nstep[0] % 3])
+            last[0] = ids, lens
             nstep[0] += 1
             if os.environ.get("MI355ASR_BENCH_DEBUG_NO_GATHER") == "1":     # diagnosis only: what the exchange itself costs
                 return ids, lens
@@ -914,7 +938,8 @@ def main():
             while len(pending) > 2:
                 pending.pop(0).wait()
             return work
-        return model.recognize(wav, reuse_buffers=True)          # the C-ABI call writes into pre-allocated outputs
+        last[0] = model.recognize(wav, reuse_buffers=True)       # the C-ABI call writes into pre-allocated outputs
+        return last[0]
 
     lib = _lib.lib()
     nk = len(_lib.KERNEL_NAMES)
@@ -930,11 +955,17 @@ def main():
         pending.pop().wait()
     # region 1: the headline number -- exactly K steps, no instrumentation
     _lib.check(lib.mi355asr_profile_enable(h.ptr, 0))
-    # the driver asks for K = 20 steps = 40 ms, less than the box-to-box spread: whole K-step regions are repeated until
-    # --min-timed-s seconds have been measured, and the spread over the regions is reported next to the mean
+    # untimed K-step regions until --min-warmup-s has passed: a region right after a few warm-up steps runs ~5 % slower than
+    # the ones after it (measured: 1.93 against 1.84 ms/step), which is the clock and not the code
+    warm_s = sum(repeated_regions(lambda: timed_region(args.steps), args.steps, args.min_warmup_s, dist, use_dist, device)[1]) \
+        if args.min_warmup_s > 0 else 0.0
+    # --min-timed-s > 0 repeats whole K-step regions until that much time has been measured (K = 20 steps is ~40 ms, less
+    # than the box-to-box spread) and reports the spread over the regions next to the mean; by default one region of K steps
     total_s, region_s = repeated_regions(lambda: timed_region(args.steps), args.steps, args.min_timed_s, dist, use_dist, device)
     n_regions = len(region_s)
     elapsed = total_s / n_regions                    # seconds per K-step region (mean over the regions)
+    if rank == 0 and args.dump_outputs:              # before anything else reuses the output buffers
+        dump_outputs(args.dump_outputs, {"ids": last[0][0], "lens": last[0][1]})
     # region 2: the same K steps again with HIP events recorded on the launch stream around every kernel
     # (costs ~0.9 ms/step of event traffic, which is why it is not the region `value` is computed from)
     elapsed_ev = None
@@ -1071,7 +1102,7 @@ def main():
                           "power-of-two scaled operands (three MFMAs) where a bound is known, else three exact bf16 terms (six) or the fp32 "
                           "instruction; same measured distance from the fp64 oracle (DESIGN.md section 2, profiles/r03d_parity_excused_frames.jsonl)",
             "frames_per_s_per_gpu": round(value / world, 1),
-            "timed_region_s": round(total_s, 4), "timed_steps_total": n_regions * args.steps,
+            "timed_region_s": round(total_s, 4), "timed_steps_total": n_regions * args.steps, "untimed_warmup_s": round(warm_s, 3),
             "region_ms_per_step": region_stats(region_s, args.steps),
             "ms_per_step_with_kernel_events": round(elapsed_ev / args.steps * 1e3, 3) if elapsed_ev else None,
             "rtf": round(elapsed / args.steps / (world * B * args.seconds), 8),

@@ -13,6 +13,12 @@ Outputs (all under tests/golden/):
                            ctc_greedy_decoder.h (compiled by oracle/Makefile into oracle/_ref)
   beam_kat.npz             known-answer tests produced by the reference's scorer-less prefix beam search
                            (externals/ctc_decoders.zip compiled by oracle/Makefile target ref_beam)
+  ctc_model_graph.onnx     ctc_model.onnx without the weight payloads that ctc_decoder_weights.npz holds:
+                           rebuild_ctc_model() puts them back, byte for byte
+  standin_greedy_kat.json  the reference's C++ greedy decoder on the blank-heavy batches of
+                           tests/test_tfshim.py::test_standin_ctc_decode_equals_the_reference_cpp_greedy_decoder
+
+  python tests/golden/make_golden.py standin_greedy_kat      (one fixture only: the make_<name> generator)
 """
 import ctypes
 import json
@@ -105,6 +111,172 @@ def make_onnx_fixtures():
           "| blank share b: %.2f" % (yb.argmax(-1) == 1331).mean())
 
 
+# ---- ctc_model_graph.onnx: the export minus the payload ctc_decoder_weights.npz already holds -----------------------------
+# Fields are copied as the file encodes them; only the length prefixes of the edited messages are written anew (minimal varints,
+# as protobuf writes them), so stripping and refilling the raw_data of an initializer gives back the original bytes.
+def _enc_varint(n):
+    out = bytearray()
+    while True:
+        b = n & 0x7F
+        n >>= 7
+        if n:
+            out.append(b | 0x80)
+        else:
+            out.append(b)
+            return bytes(out)
+
+
+def _spans(buf):
+    """[(field number, value start, end, start)] of one message, in file order"""
+    out, pos = [], 0
+    while pos < len(buf):
+        start = pos
+        key, pos = onnx_mini._varint(buf, pos)
+        fno, wt = key >> 3, key & 7
+        if wt == 0:
+            vs = pos
+            _, pos = onnx_mini._varint(buf, pos)
+        elif wt == 2:
+            ln, vs = onnx_mini._varint(buf, pos)
+            pos = vs + ln
+        elif wt in (1, 5):
+            vs, pos = pos, pos + (8 if wt == 1 else 4)
+        else:
+            raise ValueError("unsupported wire type %d" % wt)
+        out.append((fno, vs, pos, start))
+    return out
+
+
+def _field(fno, payload):
+    return _enc_varint(fno << 3 | 2) + _enc_varint(len(payload)) + bytes(payload)
+
+
+def _tensor_header(buf):
+    """TensorProto -> (name, dims, data type, has data)"""
+    name, dims, dtype, has = "", [], 1, False
+    for fno, vs, e, st in _spans(buf):
+        if fno == 1:
+            if buf[st] & 7 == 2:
+                dims += onnx_mini._packed_varints(buf[vs:e])
+            else:
+                dims.append(onnx_mini._signed(onnx_mini._varint(buf, vs)[0]))
+        elif fno == 2:
+            dtype = onnx_mini._varint(buf, vs)[0]
+        elif fno == 8:
+            name = bytes(buf[vs:e]).decode()
+        elif fno in (4, 5, 7, 9, 10, 11):
+            has = True
+    return name, dims, dtype, has
+
+
+def _edit_initializers(model, edit):
+    """model bytes with every initializer TensorProto replaced by edit(tensor bytes)"""
+    model, out = memoryview(model), bytearray()
+    for fno, vs, e, st in _spans(model):
+        if fno != 7:
+            out += model[st:e]
+            continue
+        graph, g = model[vs:e], bytearray()
+        for f2, vs2, e2, st2 in _spans(graph):
+            g += _field(5, edit(graph[vs2:e2])) if f2 == 5 else graph[st2:e2]
+        out += _field(7, g)
+    return bytes(out)
+
+
+def _weight_sources(shapes):
+    """shapes {initializer name: dims} of the initializers to trace -> {weight key: int64 array of 1-based positions in the
+    concatenation of those initializers (file order), 0 where the weight element comes from none of them}.  extract_weights
+    runs on marker values (each element its position, exact in float32 below 2^24); every other initializer reads as NaN."""
+    markers, pos = {}, 1
+    for name, dims in shapes.items():
+        n = int(np.prod(dims))
+        markers[name] = np.arange(pos, pos + n, dtype=np.float64).reshape(dims)
+        pos += n
+    assert pos < 1 << 24
+    return markers, pos - 1
+
+
+def _trace(markers, others):
+    inits = dict(others)
+    inits.update(markers)
+    out = {}
+    for k, v in extract_weights(inits).items():
+        v = np.asarray(v, np.float64).ravel()
+        ok = np.isfinite(v) & (v >= 1) & (v == np.round(v))
+        out[k] = np.where(ok, v, 0).astype(np.int64)
+    return out
+
+
+def rebuild_ctc_model(graph_path, weights):
+    """ctc_model_graph.onnx + the CTCDecoder weights (ctc_decoder_weights.npz) -> the bytes of the reference's ctc_model.onnx"""
+    with open(graph_path, "rb") as f:
+        model = f.read()
+    headers = []
+    _edit_initializers(model, lambda t: headers.append(_tensor_header(t)) or t)
+    empty = {n: d for n, d, dt, has in headers if not has and int(np.prod(d)) > 0}
+    assert all(dt == 1 for n, d, dt, has in headers if n in empty), "only float32 payloads are stripped"
+    others = {n: np.full(d, np.nan) for n, d, dt, has in headers if n not in empty}
+    markers, total = _weight_sources(empty)
+    flat = np.full(total + 1, np.nan, np.float32)
+    for k, src in _trace(markers, others).items():
+        sel = src > 0
+        flat[src[sel]] = np.asarray(weights[k], np.float32).ravel()[sel]
+    assert not np.isnan(flat[1:]).any(), "a stripped initializer element has no source in the weights"
+    payload, pos = {}, 1
+    for name, d in empty.items():
+        n = int(np.prod(d))
+        payload[name] = flat[pos:pos + n].astype("<f4").tobytes()
+        pos += n
+
+    def refill(t):
+        name = _tensor_header(t)[0]
+        if name not in payload:
+            return t
+        t, out, done = memoryview(t), bytearray(), False
+        for fno, vs, e, st in _spans(t):
+            if fno > 9 and not done:
+                out += _field(9, payload[name])
+                done = True
+            out += t[st:e]
+        return bytes(out) if done else bytes(out) + _field(9, payload[name])
+    return _edit_initializers(model, refill)
+
+
+def make_ctc_model_graph():
+    """ctc_model_graph.onnx: the export with the raw_data of every float32 initializer whose elements all reach
+    ctc_decoder_weights.npz through extract_weights removed; checked to rebuild byte for byte"""
+    import hashlib
+    with open(ONNX, "rb") as f:
+        model = f.read()
+    headers = []
+    _edit_initializers(model, lambda t: headers.append(_tensor_header(t)) or t)
+    _, inits, _, _ = onnx_mini.load(ONNX)
+    floats = {n: d for n, d, dt, has in headers if dt == 1 and has and int(np.prod(d)) > 1}
+    markers, total = _weight_sources(floats)
+    seen = np.zeros(total + 1, bool)
+    for src in _trace(markers, {n: np.full(np.shape(a), np.nan) for n, a in inits.items() if n not in floats}).values():
+        seen[src] = True
+    strip, pos = set(), 1
+    for name, d in floats.items():
+        n = int(np.prod(d))
+        if seen[pos:pos + n].all():
+            strip.add(name)
+        pos += n
+
+    def drop(t):
+        if _tensor_header(t)[0] not in strip:
+            return t
+        t = memoryview(t)
+        return b"".join(bytes(t[st:e]) for fno, vs, e, st in _spans(t) if fno != 9)
+    out = os.path.join(OUT, "ctc_model_graph.onnx")
+    with open(out, "wb") as f:
+        f.write(_edit_initializers(model, drop))
+    w = dict(np.load(os.path.join(OUT, "ctc_decoder_weights.npz")))
+    assert rebuild_ctc_model(out, w) == model, "the stripped export does not rebuild byte for byte"
+    print("ctc_model_graph.onnx: %d of %d initializers stripped, %d -> %d bytes, sha256 %s" % (
+        len(strip), len(headers), len(model), os.path.getsize(out), hashlib.sha256(model).hexdigest()))
+
+
 def make_greedy_kats():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_ctc_greedy.so"))
@@ -144,6 +316,42 @@ def make_greedy_kats():
     with open(os.path.join(OUT, "greedy_kat.json"), "w") as f:
         json.dump(kats, f)
     print("greedy KATs:", len(kats), "hand KAT ->", kats[-1]["expect"])
+
+
+def standin_greedy_batches():
+    """(T, V, lens, probabilities (3, T, V) float32) of the stand-in greedy test, in its order; the test rebuilds them from the
+    same seed"""
+    rng = np.random.default_rng(3)
+    for T, V in ((1, 3), (7, 4), (60, 12), (250, 1332)):
+        B = 3
+        logits = rng.standard_normal((B, T, V)).astype(np.float32) * 3
+        logits[:, :, -1] += 2.0                                   # blank-heavy, like a trained CTC model
+        logits[0, T // 2] = logits[0, T // 2].max()               # a frame of exact ties: first index wins on both sides
+        p = np.exp(logits - logits.max(-1, keepdims=True))
+        p /= p.sum(-1, keepdims=True)
+        yield T, V, np.array([T, max(1, T - 2), max(1, T // 2)], np.int32), p
+
+
+def make_standin_greedy_kat():
+    """the reference's C++ greedy decoder on log(p + 1e-7) (test_asr.py:167-185 / asr.py:41-61 feed it that) for every row of
+    standin_greedy_batches(): {"T,V": [ids of row 0, row 1, row 2]}"""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_ctc_greedy.so"))
+    fn = lib.ref_ctc_greedy
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    kat = {}
+    for T, V, lens, p in standin_greedy_batches():
+        rows = []
+        for b in range(p.shape[0]):
+            lp = np.ascontiguousarray(np.log(p[b, :lens[b]] + 1e-7), np.float32)
+            out = np.zeros(T + 1, np.int32)
+            n = fn(lp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(lens[b]), V, V - 1, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+            rows.append(out[:n].tolist())
+        kat["%d,%d" % (T, V)] = rows
+    with open(os.path.join(OUT, "standin_greedy_kat.json"), "w") as f:
+        json.dump(kat, f)
+    print("standin_greedy_kat.json:", {k: [len(r) for r in v] for k, v in kat.items()})
 
 
 def make_beam_kats():
@@ -288,9 +496,14 @@ def make_wer_kats():
 
 if __name__ == "__main__":
     sys.path.insert(0, REF)
+    if len(sys.argv) > 1:
+        for name in sys.argv[1:]:
+            globals()["make_" + name]()
+        sys.exit(0)
     make_wer_kats()
     make_stateful_beam_kats()
     make_onnx_fixtures()
+    make_ctc_model_graph()
     make_greedy_kats()
     make_beam_kats()
     make_long_beam_kats()

@@ -12,7 +12,7 @@ inputs `synth_batch(0, 64, 160000)` with the two weight sets of tests/golden/mak
 Same keys as config2_oracle_b64.npz (`<head>_enc_every10`, `_top4_idx`, `_top4_val`, `_logits_every50`, `_ids`, `_lens`) from
 the float32 run, plus `<head>_top4_val_f64` / `<head>_top4_idx_f64` from the run that carries float32 tensors in float64.
 tests/test_tf_goldens.py checks the oracle fixture against it (CPU: ids of all 64 utterances, the top-4 logits of every frame)
-and re-runs two utterances of this recipe; tests/test_gpu_baseline_shapes.py holds libmi355asr.so to it at the benched shape.
+and tests/golden/check_recipes.py re-runs two utterances of this recipe; tests/test_gpu_baseline_shapes.py holds libmi355asr.so to it at the benched shape.
 """
 import os
 import pickle

@@ -26,7 +26,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.environ.get("MI355ASR_TF_GOLDEN_OUT", HERE)          # tests/test_tf_recipe_runs.py regenerates into a scratch directory
+OUT = os.environ.get("MI355ASR_TF_GOLDEN_OUT", HERE)          # tests/golden/check_recipes.py regenerates into a scratch directory
 REF = os.environ.get("REFERENCE_ROOT", "/root/reference")
 for p in (ROOT, os.path.join(ROOT, "tests"), REF):
     if p not in sys.path:

@@ -21,6 +21,25 @@ def golden_ctc_io():
     return np.load(os.path.join(GOLDEN, "ctc_decoder_io.npz"))
 
 
+CTC_MODEL_SHA256 = "72ec320b03bde8efc92cef1476d72e04e6349a717b24d268135444cfd6d9f79a"   # the reference's asr/models/offline/ctc_model.onnx
+
+
+def ctc_model_onnx(directory):
+    """the reference's exported ctc_model.onnx, rebuilt byte for byte from tests/golden/ctc_model_graph.onnx (the export without
+    the weight payloads) and ctc_decoder_weights.npz (tests/golden/make_golden.py) -> its path under `directory`"""
+    import hashlib
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    make_golden = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_golden)
+    model = make_golden.rebuild_ctc_model(os.path.join(GOLDEN, "ctc_model_graph.onnx"), golden_ctc_weights())
+    assert hashlib.sha256(model).hexdigest() == CTC_MODEL_SHA256, "the rebuilt export differs from the reference's ctc_model.onnx"
+    path = os.path.join(str(directory), "ctc_model.onnx")
+    with open(path, "wb") as f:
+        f.write(model)
+    return path
+
+
 def small_cfg(num_blocks=2, base=None):
     cfg = dict(base or co.CONFORMER_S)
     cfg["num_blocks"] = num_blocks

@@ -1,16 +1,16 @@
 """tensorflowasr_amd/tfbundle.py against the one TensorFlow tensor bundle the reference ships (the VAD SavedModel's
-variables): the index parses, every block and every tensor passes its CRC32C, the object graph yields the Keras
-variable names.  The file is read where it lies (not copied into the repository)."""
+variables, stored as tests/golden/online_vad_model/variables): the index parses, every block and every tensor passes its
+CRC32C, the object graph yields the Keras variable names."""
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+from helpers import GOLDEN
 from tensorflowasr_amd import tfbundle
 
-REF = "/root/reference/vad/online_vad_model"
-needs_ref = pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is only present in the build container")
+REF = os.path.join(GOLDEN, "online_vad_model")
 
 
 def test_crc32c_known_answers():
@@ -20,7 +20,6 @@ def test_crc32c_known_answers():
     assert tfbundle.masked_crc32c(b"123456789") == (((0xE3069283 >> 15) | (0xE3069283 << 17)) + 0xA282EAD8) & 0xFFFFFFFF
 
 
-@needs_ref
 def test_reference_bundle_reads_with_all_checksums():
     b = tfbundle.Bundle(tfbundle.checkpoint_prefix(REF), verify=True)
     assert b.num_shards == 1 and len(b.entries) == 19
@@ -36,7 +35,6 @@ def test_reference_bundle_reads_with_all_checksums():
     assert tfbundle.checkpoint_prefix(REF + "/variables/variables.index") == REF + "/variables/variables"
 
 
-@needs_ref
 def test_corruption_is_detected(tmp_path):
     for name in os.listdir(REF + "/variables"):
         shutil.copy(os.path.join(REF, "variables", name), tmp_path / name)

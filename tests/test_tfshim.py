@@ -2,34 +2,25 @@
 Python on.  The stand-in is test infrastructure; these tests are what entitles the tf_*.npz fixtures to be called "the
 reference's output":
 
-1. reference-held data: the reference's `CTCDecoder` CLASS (asr/models/conformer_blocks.py:385-438, imported unmodified from
-   /root/reference), executed on the stand-in with the weights of the reference's exported `ctc_model.onnx`, must reproduce
-   what the ONNX graph itself computes (tests/golden/ctc_decoder_io.npz, produced by oracle/onnx_mini.py from the .onnx
-   file) within 1e-4 with identical argmax -- Dense, LayerNormalization, the reference's MultiHeadAttention einsums,
-   Conv1D, SeparableConv1D 'same' 15/16, BatchNormalization, swish, GLU, Add, the 0.5 residual, the name scopes;
-2. reference-held data: Keras auto-naming.  Building the encoder (13 blocks) and then the CTC decoder the way
-   test_asr.py:26-75 does must give the decoder's layers the numbers the exported graph carries (dense_53 .. dense_57,
-   layer_normalization_65 .. 69, multi_head_attention_13, batch_normalization_13);
-3. reference-held data: keras.backend.ctc_decode (greedy) against the reference's own C++ `ctc_greedy_decoder.h`, compiled in
-   place (oracle/_ref/libref_ctc_greedy.so);
-4. every primitive against its torch.nn.functional twin on random data (float64, 1e-10): strided / dilated convolutions
+1. reference-held data: keras.backend.ctc_decode (greedy) against the ids the reference's own C++ `ctc_greedy_decoder.h`
+   returned for the same batches (tests/golden/standin_greedy_kat.json);
+2. every primitive against its torch.nn.functional twin on random data (float64, 1e-10): strided / dilated convolutions
    with TF 'SAME' padding (compared with explicitly padded torch convolutions), depthwise, separable-causal, dense,
    layer / batch / instance normalisation, Keras MultiHeadAttention with a mask (torch scaled_dot_product_attention),
    pooling, embedding, pad modes, FFTs, repeat / roll / band_part / where / dynamic_stitch, scan, while_loop.
 
-Needs /root/reference (present in the build container, absent on the GPU box: the whole module skips there)."""
-import ctypes
+The checks that execute the reference's own Python on the stand-in (its CTCDecoder class against the exported ONNX graph,
+Keras auto-naming, the fixture recipes) need the reference checkout and live in tests/golden/check_recipes.py."""
+import json
 import os
 import sys
 
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, ROOT, golden_ctc_io, golden_ctc_weights
+from helpers import GOLDEN, ROOT
 
-REF = os.environ.get("REFERENCE_ROOT", "/root/reference")
 SHIM = os.path.join(ROOT, "oracle", "_tfshim")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "asr", "models")), reason="needs the reference checkout")
 
 _PURGE = ("tensorflow", "tensorflow_addons", "librosa", "asr", "leaf_audio", "utils")
 
@@ -38,7 +29,7 @@ _PURGE = ("tensorflow", "tensorflow_addons", "librosa", "asr", "leaf_audio", "ut
 def tf():
     """the stand-in on sys.path for this module only; everything it brought in is forgotten afterwards"""
     before = list(sys.path)
-    sys.path[:0] = [SHIM, REF]
+    sys.path[:0] = [SHIM]
     for k in [k for k in sys.modules if k.split(".")[0] in _PURGE]:
         del sys.modules[k]
     import tensorflow as tf
@@ -56,70 +47,25 @@ def _fresh_names(tf):
     _impl.reset_uids()
 
 
-# ---- 1 + 2: the reference's classes against the reference's exported graph -----------------------------------------------
-def test_reference_ctc_decoder_class_on_the_standin_reproduces_the_exported_onnx_graph(tf):
-    from asr.models import conformer_blocks as cb
-    from tensorflowasr_amd import checkpoint
-    _fresh_names(tf)
-    # test_asr.py:26-75: encoder first, then the CTC decoder -- the layer numbering of the export depends on it
-    enc = cb.ConformerEncoder(dmodel=144, reduction_factor=4, num_blocks=13, head_size=36, num_heads=4, kernel_size=32, fc_factor=0.5,
-                              dropout=0.0, add_wav_info=False, sample_rate=16000, n_mels=80, mel_layer_type="Melspectrogram",
-                              mel_layer_trainable=False, stride_ms=10)
-    ctc = cb.CTCDecoder(num_classes=1332, dmodel=144, num_blocks=1, head_size=36, num_heads=4, kernel_size=32, dropout=0.0, fc_factor=0.5)
-    ctc._build()
-    names = [v.name for v in ctc.weights]
-    # (2) the numbers in the exported graph's scope names (`grep ReadVariableOp` over the initializers)
-    _, inits = checkpoint.read_onnx(os.path.join(REF, "Inference", "PythonInference", "asr", "models", "offline", "ctc_model.onnx"))
-    import re
-    auto = re.compile(r"^(dense|layer_normalization|multi_head_attention|batch_normalization|conv1d|separable_conv1d)_\d+$")
-    exported = {p for k in inits for p in k.split("/") if auto.match(p)}
-    mine = {p for n in names for p in n.split(":")[0].split("/")[1:-1] if auto.match(p)}
-    assert len(exported) == 12 and exported == mine, (sorted(exported - mine), sorted(mine - exported))
-    assert {"dense_53", "dense_54", "dense_57", "layer_normalization_65", "layer_normalization_69", "multi_head_attention_13",
-            "batch_normalization_13"} <= mine
-    assert len(enc.conformer_blocks) == 13
-    # (1) the trained weights of the export, through the product's own Keras-name map, into the reference's class
-    w = golden_ctc_weights()
-    m = checkpoint.keras_names_to_abi(names)
-    assert sorted(m.values()) == sorted(w), (sorted(set(w) - set(m.values())), sorted(set(names) - set(m)))
-    for v in ctc.weights:
-        v.assign(np.asarray(w[m[v.name]], np.float32).reshape(v.shape))
-    io = golden_ctc_io()                      # what oracle/onnx_mini.py computed from ctc_model.onnx itself (tests/golden/make_golden.py)
-    got = ctc(tf.constant(io["x_a"]), training=False).numpy()
-    assert got.shape == io["logits_a"].shape and np.abs(got - io["logits_a"]).max() < 1e-4
-    assert np.array_equal(got.argmax(-1), io["logits_a"].argmax(-1))
-    got = ctc(tf.constant(io["x_b"]), training=False).numpy()
-    assert np.array_equal(got.argmax(-1), io["argmax_b"]) and np.abs(got.max(-1) - io["max_b"]).max() < 1e-4
-    assert np.abs(got[:, ::8] - io["logits_b_every8"]).max() < 1e-4
-
-
+# ---- 1: the stand-in's ctc_decode against the reference's C++ greedy decoder -----------------------------------------
 def test_standin_ctc_decode_equals_the_reference_cpp_greedy_decoder(tf):
-    lib_path = os.path.join(ROOT, "oracle", "_ref", "libref_ctc_greedy.so")
-    if not os.path.exists(lib_path):
-        pytest.skip("oracle/_ref/libref_ctc_greedy.so not built (make -C oracle)")
-    lib = ctypes.CDLL(lib_path)
-    fn = lib.ref_ctc_greedy
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    rng = np.random.default_rng(3)
-    for T, V in ((1, 3), (7, 4), (60, 12), (250, 1332)):
-        B = 3
-        logits = rng.standard_normal((B, T, V)).astype(np.float32) * 3
-        logits[:, :, -1] += 2.0                                   # blank-heavy, like a trained CTC model
-        logits[0, T // 2] = logits[0, T // 2].max()               # a frame of exact ties: first index wins on both sides
-        p = np.exp(logits - logits.max(-1, keepdims=True))
-        p /= p.sum(-1, keepdims=True)
-        lens = np.array([T, max(1, T - 2), max(1, T // 2)], np.int32)
+    """the ids the reference's C++ decoder returned for these batches, on log(p + 1e-7) as test_asr.py:167-185 / asr.py:41-61
+    feed it (tests/golden/standin_greedy_kat.json, tests/golden/make_golden.py standin_greedy_kat)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    make_golden = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_golden)
+    with open(os.path.join(GOLDEN, "standin_greedy_kat.json")) as f:
+        kat = json.load(f)
+    cases = list(make_golden.standin_greedy_batches())
+    assert sorted(kat) == sorted("%d,%d" % (T, V) for T, V, _, _ in cases)
+    for T, V, lens, p in cases:
         dense = tf.keras.backend.ctc_decode(tf.constant(p), lens)[0][0].numpy()
-        for b in range(B):
-            # the C++ decoder works on log(p + 1e-7) too (test_asr.py:167-185 / asr.py:41-61 feed it that)
-            lp = np.ascontiguousarray(np.log(p[b, :lens[b]] + 1e-7), np.float32)
-            out = np.zeros(T + 1, np.int32)
-            n = fn(lp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(lens[b]), V, V - 1, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
-            assert [int(t) for t in dense[b] if t >= 0] == out[:n].tolist(), (T, V, b)
+        for b in range(p.shape[0]):
+            assert [int(t) for t in dense[b] if t >= 0] == kat["%d,%d" % (T, V)][b], (T, V, b)
 
 
-# ---- 4: primitives against torch ------------------------------------------------------------------------------------------
+# ---- 2: primitives against torch ------------------------------------------------------------------------------------------
 def _t(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a))
