@@ -328,6 +328,35 @@ int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids_dev, const
                                 int32_t U, int32_t T, float* logits_dev, int32_t* argmax_dev, void* ws_dev,
                                 size_t ws_bytes, void* stream);
 
+/* ---- Voice-activity detector: waveform -> one score per 10 ms frame ------------------------------------------
+ * replaces: VAD.inference on Inference/PythonInference/vad/models/vad.onnx (offline_asr_session.py OfflineVAD.vad,
+ * CppInference asr_session.cpp Session::VadInference).  A frame is 80 samples of 8 kHz audio; decimate = 2 takes
+ * every second sample of 16 kHz input in the kernel (wav[::2]), decimate = 1 reads 8 kHz input as it is.
+ * Network per frame: dense -> dense_1 + ReLU -> conv1d (k 5, causal zero pad on the activations) + ReLU ->
+ * dense_2 + ReLU -> LayerNorm (eps 1e-3) -> conv1d_1 (k 5, causal) + ReLU -> dense_3 + ReLU -> dense_4; a frame
+ * depends on itself and the 8 frames before it.  Speech: score >= 0 (offline session) or > -0.1 (C++ gate).
+ * Weight names and layouts (fp32, tf2onnx graph names):
+ *   dense/kernel, dense_1/kernel, dense_2/kernel, dense_3/kernel  [80 in, 80 out]   + <name>/bias [80]
+ *   conv1d/kernel, conv1d_1/kernel  [5 taps, 80 in, 80 out] (tap 4 is the current frame) + <name>/bias [80]
+ *   layer_normalization/gamma, layer_normalization/beta  [80]
+ *   dense_4/kernel [80, 1], dense_4/bias [1]
+ * load with mi355asr_load_weight, then mi355asr_finalize_weights; mi355asr_destroy frees the handle. */
+typedef struct {
+  int32_t dmodel;     /* 80 */
+  int32_t frame;      /* 80 samples (after decimation) per frame */
+  int32_t decimate;   /* 1 or 2 */
+} mi355asr_vad_config;
+int mi355asr_vad_create(const mi355asr_vad_config* cfg, mi355asr_model** out);
+/* T = floor(L / (80 * decimate)) frames for L input samples */
+int mi355asr_vad_frames(const mi355asr_model* m, int32_t L, int32_t* T);
+/* always 0 today (every activation stays on chip); kept so a caller can size a workspace if that changes */
+int mi355asr_vad_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t L, size_t* bytes);
+/* wav_dev f32 [B, L]; in_len_dev i32 [B] samples per row or NULL (every row has L); scores_dev f32 [B, T] with
+ * T = mi355asr_vad_frames(L).  Row b gets floor(min(in_len[b], L) / (80 * decimate)) scores; samples past a row's
+ * length are never read and score entries past its frame count are not written. */
+int mi355asr_vad_forward(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
+                         float* scores_dev, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

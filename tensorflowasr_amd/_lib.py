@@ -39,6 +39,11 @@ class TranslatorConfig(ctypes.Structure):
         [("fc_factor", ctypes.c_float), ("inp_classes", ctypes.c_int32), ("tar_classes", ctypes.c_int32)]
 
 
+class VadConfig(ctypes.Structure):
+    """mirror of `mi355asr_vad_config`."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("dmodel", "frame", "decimate")]
+
+
 class ChunkOutputs(ctypes.Structure):
     """mirror of `mi355asr_chunk_outputs`."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("front_out", "enc_out", "picker_logits", "picker_hidden", "picked",
@@ -100,6 +105,10 @@ SIGNATURES = {
     "mi355asr_translator_create": (ctypes.c_int, [ctypes.POINTER(TranslatorConfig), ctypes.POINTER(_P)]),
     "mi355asr_translator_workspace_bytes": (ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_translator_forward": (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi355asr_vad_create": (ctypes.c_int, [ctypes.POINTER(VadConfig), ctypes.POINTER(_P)]),
+    "mi355asr_vad_frames": (ctypes.c_int, [_P, _I, ctypes.POINTER(_I)]),
+    "mi355asr_vad_workspace_bytes": (ctypes.c_int, [_P, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_vad_forward": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "mi355asr_profile_enable": (ctypes.c_int, [_P, _I]),
     "mi355asr_profile_schemes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _I]),
     "mi355asr_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), _I, _I]),

@@ -116,8 +116,11 @@ class ASR:
 
     # test_asr.py:186-219
     def offline_stt(self, wav_path):
-        data = self.speech_featurizer.load_wav(wav_path)
-        input_wav = data.reshape([1, -1, 1])
+        return self.offline_stt_wave(self.speech_featurizer.load_wav(wav_path))
+
+    def offline_stt_wave(self, data):
+        """offline_stt on an in-memory 1-D waveform at the model's sample rate (one utterance)."""
+        input_wav = np.asarray(data, np.float32).reshape([1, -1, 1])
         t0 = time.time()
         enc_outputs = self.encoder(input_wav, training=False)
         ctc_decode, _ = self._phone_ids(enc_outputs)

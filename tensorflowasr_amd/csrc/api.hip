@@ -1286,6 +1286,7 @@ int check_ready(const mi355asr_model* m, bool need_encoder = false) {
   if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
   if (m->is_chunk) return fail(MI355ASR_ESTATE, "ChunkConformer handle: use mi355asr_chunk_predict");
   if (m->is_translator) return fail(MI355ASR_ESTATE, "Translator handle: use mi355asr_translator_forward");
+  if (m->is_vad) return fail(MI355ASR_ESTATE, "VAD handle: use mi355asr_vad_forward");
   if (need_encoder && !m->cfg.has_encoder) return fail(MI355ASR_ESTATE, "model was created without an encoder (has_encoder=0)");
   return 0;
 }
@@ -1797,6 +1798,7 @@ int mi355asr_finalize_weights(mi355asr_model* m, void* stream) {
     if (!m->host.count(e.name) || !m->host[e.name].set) return fail(MI355ASR_EWEIGHT, "missing weight '%s'", e.name.c_str());
   if (m->is_chunk) return finalize_chunk(m, (hipStream_t)stream);
   if (m->is_translator) return finalize_translator(m, (hipStream_t)stream);
+  if (m->is_vad) return finalize_vad(m, (hipStream_t)stream);
   const auto& c = m->cfg;
   const Dims& dm = m->dm;
   const int d = c.dmodel;

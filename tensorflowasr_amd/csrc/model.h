@@ -177,6 +177,9 @@ struct mi355asr_model {
   mi355asr_translator_config tcfg;
   StackDev t_stack;
   const float *t_emb = nullptr, *t_pe = nullptr;   // [inp_classes, d], [kMaxTokens, d]
+  // voice-activity detector (mi355asr_vad_create): packed weights in `arena` (vad.hip)
+  bool is_vad = false;
+  mi355asr_vad_config vcfg;
   StackDev c_enc, c_picker, c_helper, c_decoder;
   // optional per-kernel timing with HIP events on the launch stream (mi355asr_profile_*)
   mutable bool prof = false;
@@ -336,5 +339,6 @@ bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);   //
 void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V);   // api_chunk.hip
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip
+int finalize_vad(mi355asr_model* m, hipStream_t s);          // vad.hip
 
 }  // namespace mi355

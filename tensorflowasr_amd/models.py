@@ -66,7 +66,8 @@ class _Handle:
         self.device = torch.device(device)
         self.ptr = ctypes.c_void_p()
         create = {_lib.ChunkConfig: self.lib.mi355asr_chunk_create,
-                  _lib.TranslatorConfig: self.lib.mi355asr_translator_create}.get(type(cfg), self.lib.mi355asr_create)
+                  _lib.TranslatorConfig: self.lib.mi355asr_translator_create,
+                  _lib.VadConfig: self.lib.mi355asr_vad_create}.get(type(cfg), self.lib.mi355asr_create)
         _lib.check(create(ctypes.byref(cfg), ctypes.byref(self.ptr)))
         self._ws = None
         self.built = False

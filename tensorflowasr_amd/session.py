@@ -1,0 +1,40 @@
+"""`ASRSession`: offline_asr_session.py ASRSession on the MI355X -- VAD segmentation of a long recording, then one
+recognition per segment.
+
+    session = ASRSession(asr, vad)
+    for r in session.send('long.wav'):
+        print(r['sentence_begin_time'], r['sentence_end_time'], r['best_text'])
+
+Each segment is decoded as its own utterance (`ASR.offline_stt_wave` on the slice): the encoder has no mask, so
+padding segments into one batch would change their results.  Punctuation (the reference's Punc model) is not
+applied; `best_text` is the Translator's text.  The segmentation is the reference's OfflineVAD (vad.py), including
+its behaviour of returning at most one segment, from the first speech onset to the end of the recording."""
+import numpy as np
+
+from .featurizers import read_raw_audio
+from .vad import OfflineVAD
+
+
+class ASRSession:
+    def __init__(self, asr, vad, session="asr_1", sample_rate=16000):
+        self.session = session
+        self.sample_rate = sample_rate
+        self.asr = asr
+        self.offline_vad = OfflineVAD(sr=sample_rate)
+        self.offline_vad.compile(vad)
+
+    def send(self, wav_path):
+        """wav path or 1-D array -> [{session, sentence_index, sentence_begin_time, best_text, sentence_end_time}],
+        times in integer ms.  Like the reference, every dict carries session 'asr_1'.  Also sets `self.phones`, the
+        phone string behind each best_text."""
+        wav = read_raw_audio(wav_path, self.sample_rate) if not isinstance(wav_path, np.ndarray) else wav_path
+        wav = np.asarray(wav, np.float32).reshape(-1)
+        wav = wav[:len(wav) // 80 * 80]
+        responses, self.phones = [], []
+        for idx, (s, e) in enumerate(self.offline_vad.vad(wav)):
+            data = wav[int(s * self.sample_rate):int(e * self.sample_rate)]
+            phones, text = self.asr.offline_stt_wave(data)
+            self.phones.append(phones)
+            responses.append({"session": "asr_1", "sentence_index": idx, "sentence_begin_time": int(s * 1000),
+                              "best_text": text, "sentence_end_time": int(e * 1000)})
+        return responses
