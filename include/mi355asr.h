@@ -357,6 +357,23 @@ int mi355asr_vad_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t L, 
 int mi355asr_vad_forward(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
                          float* scores_dev, void* stream);
 
+/* ---- Speech enhancement from the online VAD's voice-mask head ------------------------------------------------
+ * replaces: the second output of vad/online_vad_model (the SavedModel's online_cnn_vad call): after dense_3 + ReLU,
+ * mask = dense_3 @ audio_voice_mask/kernel + audio_voice_mask/bias (linear, no activation), enhanced = frame * mask.
+ * An enhancer handle takes the 16 weights above plus
+ *   audio_voice_mask/kernel [80 in, 80 out], audio_voice_mask/bias [80]
+ * (tensorflowasr_amd/vad.py VAD.load_saved_model maps the SavedModel's variables to these names).
+ * mi355asr_vad_forward works on an enhancer handle and returns the same scores as on a scores-only one. */
+int mi355asr_vad_enhancer_create(const mi355asr_vad_config* cfg, mi355asr_model** out);
+/* One launch: scores and enhanced frames.  wav_dev / in_len_dev as mi355asr_vad_forward; scores_dev f32 [B, T] or
+ * NULL (not written); enhanced_dev f32 [B, T * 80] with T = mi355asr_vad_frames(L).  The mask multiplies the samples
+ * the network reads, so the enhanced output is 8 kHz audio, 80 samples per frame, whatever the decimation: with
+ * decimate = 2 it is the enhanced wav[::2] of 16 kHz input (resampling back to 16 kHz is the caller's).  Row b gets
+ * floor(min(in_len[b], L) / (80 * decimate)) * 80 samples; nothing past that is written.  MI355ASR_EINVAL on a
+ * handle from mi355asr_vad_create. */
+int mi355asr_vad_enhance(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
+                         float* scores_dev, float* enhanced_dev, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

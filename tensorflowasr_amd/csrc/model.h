@@ -179,6 +179,7 @@ struct mi355asr_model {
   const float *t_emb = nullptr, *t_pe = nullptr;   // [inp_classes, d], [kMaxTokens, d]
   // voice-activity detector (mi355asr_vad_create): packed weights in `arena` (vad.hip)
   bool is_vad = false;
+  bool vad_enhance = false;   // mi355asr_vad_enhancer_create: the arena also holds audio_voice_mask
   mi355asr_vad_config vcfg;
   StackDev c_enc, c_picker, c_helper, c_decoder;
   // optional per-kernel timing with HIP events on the launch stream (mi355asr_profile_*)

@@ -8,6 +8,14 @@
 // v_mfma_f32_16x16x4_f32; wave w of the five owns output columns 16w .. 16w+15 of every row of the tile, so each weight
 // fragment it reads from L2 (pre-packed in fragment order, 1 KiB per wave load) feeds kRows / 16 MFMAs.  Activations
 // ping-pong between two LDS buffers; four leading rows of each stay zero so the conv taps of the first rows read zeros.
+//
+// Speech enhancement (mi355asr_vad_enhance, the online SavedModel's second output): vad_kernel<VadEnhanceArgs> runs one more
+// 80x80 layer on dense_3's output, audio_voice_mask (linear: no activation), and writes enhanced = frame * mask for the
+// tile's output frames.  The frame samples are re-read from global memory (L2) since the LDS copy has been overwritten
+// by then.  The mask multiplies the samples the network saw: with decimate = 2 that is wav[::2] of 16 kHz input, so
+// the enhanced output is 8 kHz audio, 80 samples per frame, for either decimation.  vad_kernel<VadArgs> is the
+// scores-only kernel, with the arithmetic it had before the variant existed; the enhance variant's score head is the
+// same code, so both return the same scores bit for bit.
 #include "common.h"
 #include "model.h"
 
@@ -35,13 +43,22 @@ constexpr size_t kGammaOff = kBiasOff + 6 * kC;
 constexpr size_t kBetaOff = kGammaOff + kC;
 constexpr size_t kHeadOff = kBetaOff + kC;          // dense_4 kernel [80] then its bias
 constexpr size_t kArenaFloats = kHeadOff + kC + 4;
+// enhancer handles only: audio_voice_mask packed like the other 80x80 layers, then its bias
+constexpr size_t kMaskOff = kArenaFloats;
+constexpr size_t kMaskBiasOff = kMaskOff + pack_floats(1);
+constexpr size_t kEnhArenaFloats = kMaskBiasOff + kC;
+static_assert(kMaskOff % 4 == 0, "fragment loads of the mask layer need 16-byte alignment");
 
 struct VadArgs {
   const float* wav;        // [B, L]
   const int32_t* in_len;   // [B] samples, or null
-  float* scores;           // [B, T]
+  float* scores;           // [B, T], or null (enhance only)
   const float* w;          // arena
   int B, L, T, dec, tiles;
+};
+
+struct VadEnhanceArgs : VadArgs {
+  float* enhanced;         // [B, T * 80]
 };
 
 // out[i][16w + c] = act(sum_{tap,k} in[i - (TAPS-1) + tap][k] * W[tap][k][16w + c] + bias), rows i in [0, kRows).
@@ -87,7 +104,10 @@ __device__ __forceinline__ void mfma_layer(const float* in, float* out, const f3
     }
 }
 
-__global__ __launch_bounds__(kThreads) void vad_kernel(VadArgs a) {
+// Args = VadArgs: scores only; VadEnhanceArgs: scores (optional) and enhanced frames
+template <class Args>
+__global__ __launch_bounds__(kThreads) void vad_kernel(Args a) {
+  constexpr bool kEnhance = std::is_same<Args, VadEnhanceArgs>::value;
   __shared__ __attribute__((aligned(16))) float lds[2][(kPadRows + kRows) * kLd];
   const int tile = blockIdx.x % a.tiles, b = blockIdx.x / a.tiles;
   int Tb = a.T;
@@ -135,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void vad_kernel(VadArgs a) {
   __syncthreads();
   mfma_layer<1>(Y, X, W + w_off(5) / 4, bias + 5 * kC, true, 0);
   __syncthreads();
-  if (tid < kTile) {
+  if (tid < kTile && (!kEnhance || a.scores)) {
     const int f = t0 + tid;
     if (f < Tb) {
       const float* x = X + (kHalo + tid) * kLd;
@@ -144,33 +164,85 @@ __global__ __launch_bounds__(kThreads) void vad_kernel(VadArgs a) {
       a.scores[(size_t)b * a.T + f] = s + a.w[kHeadOff + kC];
     }
   }
+  if constexpr (kEnhance) {
+    // mask = dense_3 @ K + b (no activation) into Y; the head above only reads X, so no barrier between them
+    mfma_layer<1>(X, Y, W + kMaskOff / 4, a.w + kMaskBiasOff, false, 0);
+    __syncthreads();
+    // enhanced[b, f*80 + c] = frame sample * mask for the tile's output frames [t0, t0 + nf): one contiguous span of
+    // the output row, stored in thread order; the samples are the ones the input rows read above
+    const int nf = min(kTile, Tb - t0);
+    float* erow = a.enhanced + (size_t)b * a.T * kC + (size_t)t0 * kC;
+    const float* xin = wrow + (size_t)t0 * kC * a.dec;
+    for (int i = tid; i < nf * kC; i += kThreads) {
+      const int row = i / kC, c = i - row * kC;
+      erow[i] = xin[(size_t)i * a.dec] * Y[(kHalo + row) * kLd + c];
+    }
+  }
 }
 
 const char* kDenseNames[4] = {"dense", "dense_1", "dense_2", "dense_3"};
+
+// weights [taps][80 in][80 out] -> fragments [n-tile w][tap][group g][lane][j] = W[tap][16g + 4(lane>>4) + j][16w + (lane&15)]
+void pack_layer(const std::vector<float>& w, int taps, float* p) {
+  const int G = kC / 16;
+  for (int wv = 0; wv < kWaves; ++wv)
+    for (int tap = 0; tap < taps; ++tap)
+      for (int g = 0; g < G; ++g)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int k = 16 * g + 4 * (lane >> 4) + j, n = 16 * wv + (lane & 15);
+            p[((((size_t)wv * taps + tap) * G + g) * 64 + lane) * 4 + j] = w[((size_t)tap * kC + k) * kC + n];
+          }
+}
+
+int create_vad(const mi355asr_vad_config* cfg, mi355asr_model** out, bool enhance) {
+  if (!cfg || !out) return fail(MI355ASR_EINVAL, "null argument");
+  if (cfg->dmodel != kC || cfg->frame != kC) return fail(MI355ASR_EINVAL, "VAD: dmodel=%d frame=%d, supported is 80 / 80", cfg->dmodel, cfg->frame);
+  if (cfg->decimate != 1 && cfg->decimate != 2) return fail(MI355ASR_EINVAL, "VAD: decimate=%d, must be 1 or 2", cfg->decimate);
+  auto* m = new mi355asr_model();
+  m->is_vad = true;
+  m->vad_enhance = enhance;
+  m->vcfg = *cfg;
+  std::memset(&m->cfg, 0, sizeof(m->cfg));
+  std::memset(&m->dm, 0, sizeof(m->dm));
+  auto& ex = m->expected;
+  for (const char* n : kDenseNames) {
+    ex.push_back({std::string(n) + "/kernel", {kC, kC}});
+    ex.push_back({std::string(n) + "/bias", {kC}});
+  }
+  ex.push_back({"conv1d/kernel", {5, kC, kC}});
+  ex.push_back({"conv1d/bias", {kC}});
+  ex.push_back({"layer_normalization/gamma", {kC}});
+  ex.push_back({"layer_normalization/beta", {kC}});
+  ex.push_back({"conv1d_1/kernel", {5, kC, kC}});
+  ex.push_back({"conv1d_1/bias", {kC}});
+  ex.push_back({"dense_4/kernel", {kC, 1}});
+  ex.push_back({"dense_4/bias", {1}});
+  if (enhance) {
+    ex.push_back({"audio_voice_mask/kernel", {kC, kC}});
+    ex.push_back({"audio_voice_mask/bias", {kC}});
+  }
+  for (const auto& e : ex) m->host[e.name] = HostTensor{};
+  *out = m;
+  return 0;
+}
 
 }  // namespace
 
 namespace mi355 {
 
 int finalize_vad(mi355asr_model* m, hipStream_t s) {
-  std::vector<float> arena(kArenaFloats, 0.f);
-  // layer i of kTaps: weights [taps][80 in][80 out] -> fragments [n-tile w][tap][group g][lane][j] =
-  // W[tap][16g + 4(lane>>4) + j][16w + (lane&15)]
+  // the scores-only layout is a prefix of the enhancer's, so mi355asr_vad_forward reads either arena alike
+  std::vector<float> arena(m->vad_enhance ? kEnhArenaFloats : kArenaFloats, 0.f);
   const char* mats[6] = {"dense/kernel", "dense_1/kernel", "conv1d/kernel", "dense_2/kernel", "conv1d_1/kernel", "dense_3/kernel"};
   const char* biases[6] = {"dense/bias", "dense_1/bias", "conv1d/bias", "dense_2/bias", "conv1d_1/bias", "dense_3/bias"};
   for (int L = 0; L < 6; ++L) {
-    const auto& w = m->host[mats[L]].data;
-    const int taps = kTaps[L], G = kC / 16;
-    float* p = arena.data() + w_off(L);
-    for (int wv = 0; wv < kWaves; ++wv)
-      for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < G; ++g)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 4; ++j) {
-              const int k = 16 * g + 4 * (lane >> 4) + j, n = 16 * wv + (lane & 15);
-              p[((((size_t)wv * taps + tap) * G + g) * 64 + lane) * 4 + j] = w[((size_t)tap * kC + k) * kC + n];
-            }
+    pack_layer(m->host[mats[L]].data, kTaps[L], arena.data() + w_off(L));
     std::memcpy(arena.data() + kBiasOff + L * kC, m->host[biases[L]].data.data(), kC * sizeof(float));
+  }
+  if (m->vad_enhance) {
+    pack_layer(m->host["audio_voice_mask/kernel"].data, 1, arena.data() + kMaskOff);
+    std::memcpy(arena.data() + kMaskBiasOff, m->host["audio_voice_mask/bias"].data.data(), kC * sizeof(float));
   }
   std::memcpy(arena.data() + kGammaOff, m->host["layer_normalization/gamma"].data.data(), kC * sizeof(float));
   std::memcpy(arena.data() + kBetaOff, m->host["layer_normalization/beta"].data.data(), kC * sizeof(float));
@@ -189,31 +261,10 @@ int finalize_vad(mi355asr_model* m, hipStream_t s) {
 }  // namespace mi355
 
 extern "C" {
-int mi355asr_vad_create(const mi355asr_vad_config* cfg, mi355asr_model** out) {
-  if (!cfg || !out) return fail(MI355ASR_EINVAL, "null argument");
-  if (cfg->dmodel != kC || cfg->frame != kC) return fail(MI355ASR_EINVAL, "VAD: dmodel=%d frame=%d, supported is 80 / 80", cfg->dmodel, cfg->frame);
-  if (cfg->decimate != 1 && cfg->decimate != 2) return fail(MI355ASR_EINVAL, "VAD: decimate=%d, must be 1 or 2", cfg->decimate);
-  auto* m = new mi355asr_model();
-  m->is_vad = true;
-  m->vcfg = *cfg;
-  std::memset(&m->cfg, 0, sizeof(m->cfg));
-  std::memset(&m->dm, 0, sizeof(m->dm));
-  auto& ex = m->expected;
-  for (const char* n : kDenseNames) {
-    ex.push_back({std::string(n) + "/kernel", {kC, kC}});
-    ex.push_back({std::string(n) + "/bias", {kC}});
-  }
-  ex.push_back({"conv1d/kernel", {5, kC, kC}});
-  ex.push_back({"conv1d/bias", {kC}});
-  ex.push_back({"layer_normalization/gamma", {kC}});
-  ex.push_back({"layer_normalization/beta", {kC}});
-  ex.push_back({"conv1d_1/kernel", {5, kC, kC}});
-  ex.push_back({"conv1d_1/bias", {kC}});
-  ex.push_back({"dense_4/kernel", {kC, 1}});
-  ex.push_back({"dense_4/bias", {1}});
-  for (const auto& e : ex) m->host[e.name] = HostTensor{};
-  *out = m;
-  return 0;
+int mi355asr_vad_create(const mi355asr_vad_config* cfg, mi355asr_model** out) { return create_vad(cfg, out, false); }
+
+int mi355asr_vad_enhancer_create(const mi355asr_vad_config* cfg, mi355asr_model** out) {
+  return create_vad(cfg, out, true);
 }
 
 int mi355asr_vad_frames(const mi355asr_model* m, int32_t L, int32_t* T) {
@@ -241,9 +292,29 @@ int mi355asr_vad_forward(mi355asr_model* m, const float* wav, int32_t B, int32_t
   VadArgs a{wav, in_len, scores, m->arena, B, L, T, dec, ceil_div(T, kTile)};
   const int64_t blocks = (int64_t)B * a.tiles;
   if (blocks > INT32_MAX) return fail(MI355ASR_EINVAL, "B * tiles = %lld exceeds the grid", (long long)blocks);
-  hipLaunchKernelGGL(vad_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(vad_kernel<VadArgs>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MI355ASR_EHIP, "launch vad_kernel: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int mi355asr_vad_enhance(mi355asr_model* m, const float* wav, int32_t B, int32_t L, const int32_t* in_len,
+                         float* scores, float* enhanced, void* stream) {
+  if (!m || !m->is_vad) return fail(MI355ASR_EINVAL, "not a VAD handle");
+  if (!m->vad_enhance) return fail(MI355ASR_EINVAL, "VAD handle has no voice-mask head: create it with mi355asr_vad_enhancer_create");
+  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
+  if (B < 1 || L < 0) return fail(MI355ASR_EINVAL, "B must be positive and L >= 0 (got %d, %d)", B, L);
+  const int dec = m->vcfg.decimate, T = L / (kC * dec);
+  if (T == 0) return 0;
+  if (!wav || !enhanced) return fail(MI355ASR_EINVAL, "null argument");
+  VadEnhanceArgs a;
+  static_cast<VadArgs&>(a) = VadArgs{wav, in_len, scores, m->arena, B, L, T, dec, ceil_div(T, kTile)};
+  a.enhanced = enhanced;
+  const int64_t blocks = (int64_t)B * a.tiles;
+  if (blocks > INT32_MAX) return fail(MI355ASR_EINVAL, "B * tiles = %lld exceeds the grid", (long long)blocks);
+  hipLaunchKernelGGL(vad_kernel<VadEnhanceArgs>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MI355ASR_EHIP, "launch vad_kernel (enhance): %s", hipGetErrorString(e));
   return 0;
 }
 }  // extern "C"

@@ -60,14 +60,14 @@ def default_weights(names_and_shapes, rng, sample_rate=16000, n_dft=1024, n_mels
 class _Handle:
     """Owns one `mi355asr_model*` plus its device workspace."""
 
-    def __init__(self, cfg, device):
+    def __init__(self, cfg, device, create=None):
         self.lib = _lib.lib()
         self.cfg = cfg
         self.device = torch.device(device)
         self.ptr = ctypes.c_void_p()
-        create = {_lib.ChunkConfig: self.lib.mi355asr_chunk_create,
-                  _lib.TranslatorConfig: self.lib.mi355asr_translator_create,
-                  _lib.VadConfig: self.lib.mi355asr_vad_create}.get(type(cfg), self.lib.mi355asr_create)
+        create = create or {_lib.ChunkConfig: self.lib.mi355asr_chunk_create,
+                            _lib.TranslatorConfig: self.lib.mi355asr_translator_create,
+                            _lib.VadConfig: self.lib.mi355asr_vad_create}.get(type(cfg), self.lib.mi355asr_create)
         _lib.check(create(ctypes.byref(cfg), ctypes.byref(self.ptr)))
         self._ws = None
         self.built = False
