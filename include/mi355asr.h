@@ -201,6 +201,29 @@ int mi355asr_beam_destroy(mi355asr_beam* d);
 int mi355asr_recognize(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
                        int32_t* ids_dev, int32_t* out_len_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- Ragged batches: utterances of different lengths in one call ----------------------------------------------
+ * wav_dev f32 [B, L] holds utterance b in its first wav_len[b] samples (the rest of the row is never read); wav_len_dev i32 [B]
+ * on the device, 1 <= wav_len[b] <= L.  Row b of every output equals what the call without lengths returns for
+ * wav[b, :wav_len[b]] alone: the STFT frames each utterance with its own TF 'SAME' padding, the dB maximum covers its own
+ * frames, the subsampling convs pad by its own lengths, attention sees only its T_b = ceil(ceil(ceil(wav_len[b] / hop) / 2) / 2)
+ * frames and the depthwise conv reads zeros past them.  Rows t >= T_b are written as defined values: encoder output 0, logits 0,
+ * frame argmax -1; ids are -1 padded as usual.  Workspace: that of [B, L] (mi355asr_workspace_bytes; ctc: ctc_workspace_bytes).
+ * Each call reads the lengths back to check them (synchronises `stream` once, at entry).
+ * Supported: the Melspectrogram frontend on the FFT STFT (mi355asr_stft_mode 1), chunk_size 0, add_wav_info 0, gemm_dtype 0,
+ * dmodel 144, reduction_factor 4, more than 16 encoder frames in a row of L samples (pad L when every utterance is shorter), and
+ * the default kernel switches; anything else returns MI355ASR_EINVAL with a message (mi355asr_last_error), checked before any
+ * launch except for kernel switches, which are checked where the block reaches them.
+ *   encoder_forward_ragged: enc_out_dev f32 [B, T(L), dmodel]; enc_len_dev i32 [B] receives T_b (may be NULL)
+ *   ctc_forward_ragged:     enc_dev [B, T, dmodel] with enc_len_dev i32 [B] (1 <= enc_len[b] <= T) frames per utterance
+ *   recognize_ragged:       the greedy collapse of utterance b stops at min(T_b, in_len[b]) (in_len_dev may be NULL) */
+int mi355asr_encoder_forward_ragged(mi355asr_model* m, const float* wav_dev, const int32_t* wav_len_dev, int32_t B, int32_t L,
+                                    float* enc_out_dev, int32_t* enc_len_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_ctc_forward_ragged(mi355asr_model* m, const float* enc_dev, const int32_t* enc_len_dev, int32_t B, int32_t T,
+                                float* logits_dev, int32_t* frame_argmax_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_recognize_ragged(mi355asr_model* m, const float* wav_dev, const int32_t* wav_len_dev, int32_t B, int32_t L,
+                              const int32_t* in_len_dev, int32_t* ids_dev, int32_t* out_len_dev, void* ws_dev, size_t ws_bytes,
+                              void* stream);
+
 /* Stage-level entry points (same kernels the calls above run; exposed so that the parity tests can
  * localise a mismatch to one reference layer):
  *   melspectrogram   Melspectrogram.call (time_frequency.py:173-189): wav [B,L] -> mel [B,F,n_mels]
@@ -327,6 +350,14 @@ int mi355asr_translator_workspace_bytes(const mi355asr_model* m, int32_t B, int3
 int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids_dev, const float* enc_dev, int32_t B,
                                 int32_t U, int32_t T, float* logits_dev, int32_t* argmax_dev, void* ws_dev,
                                 size_t ws_bytes, void* stream);
+/* ragged batches (see "Ragged batches" above): utterance b has tok_len_dev[b] tokens (1 <= tok_len[b] <= U; the solo call's
+ * width is its own decoded length) and enc_len_dev[b] encoder frames (1 <= enc_len[b] <= T); both i32 [B] on the device.
+ * Cross-attention keys past enc_len[b] are excluded, the ConvModule reads zeros from token row tok_len[b] on, and rows past
+ * tok_len[b] hold logits 0 / argmax -1.  Row b equals mi355asr_translator_forward on ids[b, :tok_len[b]] and
+ * enc[b, :enc_len[b]].  dmodel 144; U > 16 and T > 16 (pad both); workspace of mi355asr_translator_workspace_bytes(B, U, T). */
+int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids_dev, const int32_t* tok_len_dev,
+                                       const float* enc_dev, const int32_t* enc_len_dev, int32_t B, int32_t U, int32_t T,
+                                       float* logits_dev, int32_t* argmax_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ---- Voice-activity detector: waveform -> one score per 10 ms frame ------------------------------------------
  * replaces: VAD.inference on Inference/PythonInference/vad/models/vad.onnx (offline_asr_session.py OfflineVAD.vad,

@@ -129,6 +129,49 @@ class ASR:
         self.timings["offline_stt"] = time.time() - t0
         return self._finish(ctc_row, txt_row)
 
+    def offline_stt_batch(self, items, max_batch_samples=None):
+        """offline_stt_wave for every item of a list -- paths or 1-D waveforms -- in ragged batches: one encoder, CTC and
+        Translator call per batch (mi355asr_*_ragged), each row computed as if alone.  Returns [(phones, text), ...] in the
+        order of `items`, what [offline_stt_wave(w) for w in items] returns.  max_batch_samples bounds B x Lmax of a batch
+        (the workspace grows with it); None: one batch.  Offline Melspectrogram encoders of dmodel 144 only."""
+        import torch
+        waves = [np.asarray(self.speech_featurizer.load_wav(w) if isinstance(w, (str, os.PathLike)) else w,
+                            np.float32).reshape(-1) for w in items]
+        mc, sc = self.model_config, self.speech_config
+        # the length-aware attention kernels need more than 16 rows per utterance: pad the batch's L (and U) beyond that
+        min_L = 16 * mc["reduction_factor"] * int(sc["stride_ms"] * sc["sample_rate"] // 1000) + 1
+        out = [None] * len(waves)
+        order = sorted(range(len(waves)), key=lambda i: len(waves[i]))     # similar lengths together: less padding
+        batches, cur = [], []
+        for i in order:
+            L = max(min_L, max([len(waves[j]) for j in cur] + [len(waves[i])]))
+            if cur and max_batch_samples is not None and (len(cur) + 1) * L > max_batch_samples:
+                batches.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            batches.append(cur)
+        blank = self.phone_featurizer.num_classes - 1
+        for idx in batches:
+            lens = np.array([len(waves[i]) for i in idx], np.int32)
+            x = np.zeros((len(idx), max(min_L, int(lens.max()))), np.float32)
+            for r, i in enumerate(idx):
+                x[r, :lens[r]] = waves[i]
+            enc, enc_len = self.encoder(x, training=False, lengths=lens)
+            _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False, lengths=enc_len)
+            ids, tok = ctc_greedy_decode(frame_ids, enc_len, blank=blank)
+            tok_h = tok.cpu().numpy()
+            U = max(17, int(tok_h.max()))
+            ids = ids[:, :U].clamp_(min=0).contiguous()
+            # an utterance with nothing decoded gives an empty Translator row alone; here it rides along as one token
+            _, tr = self.translator([ids, enc], training=False, return_argmax=True, return_logits=False,
+                                    token_lengths=torch.from_numpy(np.maximum(tok_h, 1).astype(np.int32)), enc_lengths=enc_len)
+            ids_h, tr_h = ids.cpu().numpy(), tr.cpu().numpy()
+            for r, i in enumerate(idx):
+                n = int(tok_h[r])
+                out[i] = self._finish(ids_h[r, :n], tr_h[r, :n])
+        return out
+
     # test_asr.py:116-164
     def stream_stt(self, wav_path):
         import torch

@@ -857,6 +857,10 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
   const bool fused_env = fused_env_on();
   if (bo.pre_pp && (cross || skip_ff1 || !block_takes_pre(m, w, (size_t)M)))
     return fail(MI355ASR_ESTATE, "run_block: a layer in front of a block that cannot take it");
+  // (ragged batches: the fused kernels, or the layer-at-a-time fp32 launches of at most MI355ASR_SMALL_M rows)
+  if (bo.t_len && (d != 144 || use_gemm16(m) || (!fused_env && !gemm16_for(m, M))))
+    return fail(MI355ASR_EINVAL, "ragged batches: only the fp32 dmodel-144 block kernels apply lengths (dmodel %d%s%s)", d,
+                fused_env ? "" : ", MI355ASR_FUSED=0", use_gemm16(m) ? ", bf16 / layer-at-a-time GEMM mode" : "");
   if (gemm16_for(m, M)) {
     // one launch per dense layer (bf16.hip: bf16 or fp32 operands); LayerNorm / softmax / activations / depthwise conv in fp32
     auto g16 = [&](const float* x, int ldx, int K, const float* wp, const float* bias, int NT, float* y, int ldy) {
@@ -911,6 +915,11 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
       at.q = sc.qkv; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
       at.h2_sq = w.att_h2[0]; at.h2_sk = w.att_h2[1]; at.h2_sv = w.att_h2[2];      // q / k / v are the block's own projections (0: no bound known)
     }
+    if (bo.t_len) {
+      at.k_len = cross ? cross->k_len : bo.t_len;
+      if (!at.k_len || !attention_applies_lengths(hs, at))
+        return fail(MI355ASR_EINVAL, "ragged batches: no length-aware attention kernel for Tq = %d, Tk = %d", at.Tq, at.Tk);
+    }
     { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
     Gemm16Args op = g16(sc.ctx, d, d, w.out_wp, w.out_b, d / 16, sc.xa, d);
     op.res = sc.xb;
@@ -921,6 +930,7 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
     DwArgs dwa{};
     dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
     dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
+    dwa.t_len = bo.t_len;
     { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
     if (chain256) {
       Chain2Args ca{};
@@ -940,6 +950,8 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
   // round 6: the Translator's RBlock takes the fused kernels too -- its query projection (of LayerNorm(x1 + PE)) rides in the
   // ff_module_1 launch of the pair-pipelined kernel, keys / values come from the encoder output through their own projection
   const bool fused_cross = cross && ff1_qkv_pp_selected(w.ff1_slabs != nullptr, w.pp_ff1 != nullptr) && !bo.pre_pp && !skip_ff1 && !next;
+  if (bo.t_len && cross && (!fused_cross || !cross->k_len))
+    return fail(MI355ASR_EINVAL, "ragged batches: the Translator's cross-attention block needs the fused kernels and encoder lengths");
   if (d == 144 && fused_env && (!cross || fused_cross)) {
     // token-local runs of layers in one launch each (fused.hip); attention and the depthwise conv mix tokens
     const float qscale = 1.0f / std::sqrt((float)hs);
@@ -954,6 +966,7 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
       at.win_front = bo.win_front; at.win_back = bo.win_back;
       at.h2_sq = bw.att_h2[0]; at.h2_sk = bw.att_h2[1]; at.h2_sv = bw.att_h2[2];      // q / k / v are the block's own projections
       at.head_major = hm ? 1 : 0;
+      at.k_len = bo.t_len;
       return at;
     };
     auto qkv_head_major = [&](const BlockDev& bw) {
@@ -986,6 +999,7 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
       { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, kv, s), "cross-attention key/value projection"); }
       at.q = sc.qkv; at.ldq = 3 * d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc; at.head_major = 0;
       at.h2_sq = 0.f; at.h2_sk = 0.f; at.h2_sv = 0.f;          // no operand bounds for the encoder's rows: three exact terms
+      at.k_len = bo.t_len ? cross->k_len : nullptr;             // ragged batches: the keys are the utterance's encoder frames
     }
     OutGluArgs k2{};
     k2.ctx = sc.ctx; k2.x1 = sc.xb; k2.x2 = sc.xa; k2.u = sc.u;
@@ -996,10 +1010,16 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
     DwArgs dwa{};
     dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
     dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
+    dwa.t_len = bo.t_len;
+    // ragged batches: the attention launch, when there is one, must be a kernel that applies key lengths
+    if (bo.t_len && !attention_applies_lengths(hs, at))
+      return fail(MI355ASR_EINVAL, "ragged batches: no length-aware attention kernel for T = %d (needs T > 16 and the split kernels: "
+                  "MI355ASR_ATTN_SPLIT / MI355ASR_ATTN_LDS on)", T);
     // round 3: the depthwise conv rides in the prologue of the pair-pipelined tail kernel (no launch, dw never in HBM)
     const bool dw_fold = w.pp_tail && w.tail_slabs && tail_pp_selected() && pp_dw_fold_ok(T, ksz);
     TailFf2Args k4{};
     if (dw_fold) { k4.dw_u = sc.u; k4.dw_wd = w.dw_w; k4.dw_T = T; k4.dw_pad = dwa.pad_left; }
+    k4.dw_len = bo.t_len;
     k4.M = M; k4.pp_slabs = w.pp_tail;
     // round 4: so does out-projection + GLU (x2 and u never in HBM either): the block is attention + one launch
     const bool og_fold = dw_fold && pp_og_fold_ok(k4, k2);
@@ -1033,7 +1053,7 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
         const bool fuse_attn = ns1_attn_ok(hs, at);
         if (fuse_attn) {
           kg.attn = 1; kg.aq = at.q; kg.ak = at.k; kg.av = at.v; kg.a_T = at.Tk; kg.a_H = at.H; kg.a_ldq = at.ldq; kg.a_ldk = at.ldk;
-          kg.a_head_major = at.head_major; kg.a_sq = at.h2_sq; kg.a_sk = at.h2_sk; kg.a_sv = at.h2_sv;
+          kg.a_head_major = at.head_major; kg.a_sq = at.h2_sq; kg.a_sk = at.h2_sk; kg.a_sv = at.h2_sv; kg.a_klen = at.k_len;
         } else {
           PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention");
         }
@@ -1172,8 +1192,11 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
 }
 
 int run_mel(const mi355asr_model* m, const float* wav, int Bp, int Lb, int F, float* logp, float* pmax,
-            float* umax, float* mel, hipStream_t s) {
+            float* umax, float* mel, hipStream_t s, const int32_t* wav_len = nullptr) {
   const auto& c = m->cfg;
+  if (wav_len && (c.mel_layer_type != 0 || !m->fft_ok))
+    return fail(MI355ASR_EINVAL, "ragged batches: the Melspectrogram frontend on the FFT STFT only (%s)",
+                c.mel_layer_type == 1 ? "LEAF frontend" : c.mel_layer_type == 2 ? "Spectrogram layer" : "dense DFT STFT, stft_mode 0");
   if (c.mel_layer_type == 1) {
     // LEAF: Gabor conv + squared modulus + Gaussian pooling (partials in the log-power scratch), then PCEN + instance norm
     int nf, pl;
@@ -1208,6 +1231,7 @@ int run_mel(const mi355asr_model* m, const float* wav, int Bp, int Lb, int F, fl
     FftStftArgs fa{wav, logp, pmax, m->fft_w1p, m->fft_w2p, m->fft_twc, m->fft_tws, m->fft_win,
                    Bp, Lb, F, m->dm.hop, before, m->dm.LP, 1};
     fa.w1s = m->fft_w1s; fa.w2s = m->fft_w2s; fa.w1h = m->fft_w1h; fa.w2h = m->fft_w2h;
+    fa.wav_len = wav_len;
     { PROF(MI355ASR_K_STFT); LAUNCH_TRY(launch_fft_stft(fa, s), "stft (fft)"); }
     npart = F;
   } else {
@@ -1215,6 +1239,7 @@ int run_mel(const mi355asr_model* m, const float* wav, int Bp, int Lb, int F, fl
     LAUNCH_TRY(launch_stft(st, s), "stft");
   }
   UttMaxArgs um{pmax, umax, npart};
+  um.wav_len = wav_len; um.hop = m->dm.hop;
   { PROF(MI355ASR_K_UTT_MAX); LAUNCH_TRY(launch_utt_max(um, Bp, s), "utterance max"); }
   MelArgs me{};
   me.logp = logp; me.umax = umax; me.mel = mel; me.wp = m->mel_wp;
@@ -1228,7 +1253,7 @@ int run_mel(const mi355asr_model* m, const float* wav, int Bp, int Lb, int F, fl
 // mel_bounded: the features come from this handle's own frontend (|mel| <= 80 x the filters' L1 norm), which the two-term
 // fp16 kernel's operand scale relies on; features handed in by the caller take the three-term bf16 kernel
 int run_subsampling(const mi355asr_model* m, const float* mel, int Bp, int F, float* sub, float* out,
-                    hipStream_t s, bool mel_bounded, bool* defer_dense) {
+                    hipStream_t s, bool mel_bounded, bool* defer_dense, const int32_t* wav_len) {
   if (defer_dense) *defer_dense = false;
   const auto& c = m->cfg;
   const int d = c.dmodel;
@@ -1243,7 +1268,8 @@ int run_subsampling(const mi355asr_model* m, const float* mel, int Bp, int F, fl
   if (sa.w2h && mel_bounded) { sa.c1_mscale = m->c1_mscale; sa.c1_wscale = m->c1_wscale; }
   sa.B = Bp; sa.F = F; sa.NM = c.n_mels; sa.T1 = T1; sa.F1 = m->dm.F1; sa.T2 = T2; sa.F2 = m->dm.F2;
   sa.st1 = m->dm.st1; sa.pt1 = pt1; sa.pf1 = m->dm.pf1; sa.pt2 = pt2; sa.pf2 = m->dm.pf2;
-  { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling"); }
+  sa.wav_len = wav_len; sa.hop = m->dm.hop;
+  { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), wav_len ? "conv subsampling of a ragged batch" : "conv subsampling"); }
   if (use_gemm16(m)) {
     Gemm16Args lg{};
     lg.x = sub; lg.ldx = m->dm.F2 * d; lg.bias = m->lin_b; lg.y = out; lg.ldy = d;
@@ -1407,11 +1433,15 @@ bool stream256_args(const mi355asr_model* m, int B, int T, const float* x, float
 }
 
 int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const Plan& p, char* ws, float* enc_out,
-                 hipStream_t s) {
+                 hipStream_t s, const int32_t* wav_len, int32_t* enc_len) {
   float* logp = (float*)(ws + p.logp);
   float* mel = (float*)(ws + p.mel);
-  int rc = run_mel(m, wav, g.Bp, g.Lb, g.F, logp, (float*)(ws + p.pmax), (float*)(ws + p.umax), mel, s);
+  int rc = run_mel(m, wav, g.Bp, g.Lb, g.F, logp, (float*)(ws + p.pmax), (float*)(ws + p.umax), mel, s, wav_len);
   if (rc) return rc;
+  // ragged batches: the encoder frames of every utterance, into the words of the utterance maxima (read by the mel launch
+  // above, free from here on) and the caller's enc_len
+  int32_t* t_len = wav_len ? (int32_t*)(ws + p.umax) : nullptr;
+  if (wav_len) LAUNCH_TRY(launch_ragged_frames(wav_len, g.Bp, m->dm.hop, m->dm.st1, t_len, enc_len, s), "ragged frame counts");
   Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
              (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
   sc.h4 = (float*)(ws + p.h4);
@@ -1419,7 +1449,7 @@ int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const P
   const int nb = m->cfg.num_blocks;
   bool dense_deferred = false;
   const bool may_defer = nb > 0 && !m->cfg.add_wav_info && block_takes_pre(m, m->enc_blocks[0], (size_t)g.Bp * g.T);
-  rc = run_subsampling(m, mel, g.Bp, g.F, (float*)(ws + p.sub), sc.xa, s, true, may_defer ? &dense_deferred : nullptr);
+  rc = run_subsampling(m, mel, g.Bp, g.F, (float*)(ws + p.sub), sc.xa, s, true, may_defer ? &dense_deferred : nullptr, wav_len);
   if (rc) return rc;
   if (m->cfg.add_wav_info) {
     rc = run_wavpick(m, wav, g.Bp, g.Lb, g.T, sc.xa, (float*)(ws + p.wv), s);
@@ -1443,6 +1473,7 @@ int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const P
     BlockOpts bo;
     bo.ksz = m->cfg.kernel_size;
     bo.fc = m->cfg.fc_factor;
+    bo.t_len = t_len;
     if (i == 0 && dense_deferred) { bo.pre_x = (float*)(ws + p.sub); bo.pre_pp = m->lin_pp; bo.pre_sw = m->lin_pp_sw; bo.pre_chunks = m->dm.F2; }
     const bool skip = ff1_done;
     rc = run_block(m, m->enc_blocks[i], bo, sc, g.Bp, g.T, i == nb - 1 ? enc_out : nullptr, s, nullptr,
@@ -1450,12 +1481,24 @@ int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const P
     if (rc) return rc;
   }
   if (nb == 0) HIP_TRY(hipMemcpyAsync(enc_out, sc.xa, (size_t)g.Bp * g.T * m->cfg.dmodel * 4, hipMemcpyDeviceToDevice, s));
+  if (t_len) {
+    const int d = m->cfg.dmodel;
+    LAUNCH_TRY(launch_ragged_rows(t_len, g.Bp, g.T, enc_out, d, d, nullptr, s), "ragged encoder rows");
+  }
   return 0;
 }
 
 int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, char* ws, float* logits,
-             int32_t* amax, hipStream_t s) {
+             int32_t* amax, hipStream_t s, const int32_t* t_len) {
   const int d = m->cfg.dmodel;
+  // ragged batches: the rows past each utterance's frames get defined values once the head has run
+  auto ragged_out = [&]() -> int {
+    if (t_len) {
+      const int V = m->cfg.num_classes;
+      LAUNCH_TRY(launch_ragged_rows(t_len, B, T, logits, V, V, amax ? amax : (int32_t*)(ws + p.amax), s), "ragged CTC rows");
+    }
+    return 0;
+  };
   const int M = B * T;
   Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
              (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
@@ -1492,6 +1535,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     BlockOpts bo;
     bo.ksz = m->cfg.ctc_kernel_size;
     bo.fc = m->cfg.ctc_fc_factor;
+    bo.t_len = t_len;
     if (i == 0 && proj_fold) { bo.pre_x = enc; bo.pre_pp = m->proj_pp; bo.pre_sw = m->proj_pp_sw; bo.pre_chunks = 1; }
     if (i == m->cfg.ctc_num_blocks - 1 && head_it != m->head_of.end() && head_it->second.pp) {
       bo.head = &hdf; bo.head_pp = head_it->second.pp; bo.head_sw = head_it->second.pp_sw; bo.head_groups = head_it->second.groups; bo.head_done = &head_done;
@@ -1499,7 +1543,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     int rc = run_block(m, m->ctc_blocks[i], bo, sc, B, T, nullptr, s);
     if (rc) return rc;
   }
-  if (head_done) return 0;
+  if (head_done) return ragged_out();
   if (bf16) {
     Gemm16Args hd{};
     hd.x = sc.xa; hd.ldx = d; hd.bias = m->fc_b; hd.y = logits; hd.ldy = m->cfg.num_classes;
@@ -1510,7 +1554,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     hd.part_v = sc.h4;
     hd.part_i = reinterpret_cast<int32_t*>(sc.h4 + (size_t)hd.part_max * M);
     { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm16(m, E16_HEAD, false, hd, m->fc_wp, s), "ctc head"); }
-    return 0;
+    return ragged_out();
   }
   GemmArgs hd{};
   hd.x = sc.xa; hd.y = logits; hd.wp = m->fc_wp; hd.bias = m->fc_b;
@@ -1518,10 +1562,9 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
   hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
   {
     PROF(MI355ASR_K_CTC_HEAD);
-    if (try_head_ld(m, hd, s) == 0) return 0;
-    LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "ctc head");
+    if (try_head_ld(m, hd, s) != 0) LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "ctc head");
   }
-  return 0;
+  return ragged_out();                                 // (the class head is row-wise: only the rows past T_b need their values)
 }
 
 
@@ -2103,7 +2146,7 @@ int mi355asr_encoder_forward(mi355asr_model* m, const float* wav, int32_t B, int
   if (rc) return rc;
   const Plan p = make_plan(m, g.Bp, g.F, g.T);
   if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
-  return encoder_impl(m, wav, g, p, (char*)ws, enc_out, (hipStream_t)stream);
+  return encoder_impl(m, wav, g, p, (char*)ws, enc_out, (hipStream_t)stream, nullptr, nullptr);
 }
 
 int mi355asr_ctc_forward(mi355asr_model* m, const float* enc, int32_t B, int32_t T, float* logits, int32_t* amax,
@@ -2114,7 +2157,7 @@ int mi355asr_ctc_forward(mi355asr_model* m, const float* enc, int32_t B, int32_t
   if (!enc || !ws || B <= 0 || T <= 0) return fail(MI355ASR_EINVAL, "bad argument");
   const Plan p = make_plan(m, B, 16, T);
   if (ws_bytes < p.logp) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.logp);
-  return ctc_impl(m, enc, B, T, p, (char*)ws, logits, amax, (hipStream_t)stream);
+  return ctc_impl(m, enc, B, T, p, (char*)ws, logits, amax, (hipStream_t)stream, nullptr);
 }
 
 int mi355asr_ctc_greedy(const int32_t* frame_argmax, const int32_t* in_len, int32_t B, int32_t T, int32_t blank,
@@ -2262,13 +2305,109 @@ int mi355asr_recognize(mi355asr_model* m, const float* wav, int32_t B, int32_t L
   char* w = (char*)ws;
   hipStream_t s = (hipStream_t)stream;
   float* enc = (float*)(w + p.enc);
-  rc = encoder_impl(m, wav, g, p, w, enc, s);
+  rc = encoder_impl(m, wav, g, p, w, enc, s, nullptr, nullptr);
   if (rc) return rc;
   const int Ttot = g.T * g.nblk;
   int32_t* amax = (int32_t*)(w + p.amax);
-  rc = ctc_impl(m, enc, B, Ttot, p, w, nullptr, amax, s);
+  rc = ctc_impl(m, enc, B, Ttot, p, w, nullptr, amax, s, nullptr);
   if (rc) return rc;
   CollapseArgs ca{amax, in_len, ids, out_len, B, Ttot, m->cfg.num_classes - 1};
+  { PROF(MI355ASR_K_COLLAPSE); LAUNCH_TRY(launch_collapse(ca, s), "ctc collapse"); }
+  return 0;
+}
+
+// ---- ragged batches: utterances of different lengths in one call -------------------------------------------------------
+extern "C++" {
+namespace mi355 {
+// what the ragged entry points support: the Melspectrogram frontend on the FFT STFT, offline encoder, fp32 mode, dmodel 144
+int ragged_config_ok(const mi355asr_model* m) {
+  const auto& c = m->cfg;
+  const char* why = c.mel_layer_type == 1 ? "the LEAF frontend"
+                  : c.mel_layer_type != 0 ? "the Spectrogram layer"
+                  : c.chunk_size > 0      ? "the streaming encoder (chunk_size > 0)"
+                  : c.add_wav_info        ? "add_wav_info"
+                  : c.gemm_dtype != 0     ? "the bf16 GEMM mode"
+                  : c.dmodel != 144       ? "dmodel other than 144"
+                  : m->dm.st1 != 2        ? "reduction_factor other than 4"
+                  : !m->fft_ok            ? "the dense DFT STFT (stft_mode 0)"
+                                          : nullptr;
+  if (why) return fail(MI355ASR_EINVAL, "ragged batches do not support %s", why);
+  return 0;
+}
+// the lengths are device words: read them once (this synchronises the stream) and check 1 <= len[b] <= hi
+// the length-aware attention kernels take more than 16 rows per utterance (queries and keys): checked before anything is launched
+int ragged_rows_ok(int T, const char* what) {
+  if (T <= 16)
+    return fail(MI355ASR_EINVAL, "ragged batches: %s = %d rows per utterance, the length-aware attention kernels need more than 16 "
+                "(pad the batch: a row of more than 16 * reduction_factor * hop samples)", what, T);
+  return 0;
+}
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s) {
+  if (!len_dev) return fail(MI355ASR_EINVAL, "%s: null device pointer", what);
+  std::vector<int32_t> h((size_t)B);
+  HIP_TRY(hipMemcpyAsync(h.data(), len_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b)
+    if (h[b] < 1 || h[b] > hi) return fail(MI355ASR_EINVAL, "%s[%d] = %d lies outside [1, %d]", what, b, h[b], hi);
+  return 0;
+}
+}  // namespace mi355
+}  // extern "C++"
+
+int mi355asr_encoder_forward_ragged(mi355asr_model* m, const float* wav, const int32_t* wav_len, int32_t B, int32_t L,
+                                    float* enc_out, int32_t* enc_len, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_ready(m, true);
+  if (rc) return rc;
+  if ((rc = ragged_config_ok(m))) return rc;
+  if (!wav || !enc_out || !ws) return fail(MI355ASR_EINVAL, "null device pointer");
+  Geometry g;
+  if ((rc = geometry(m, B, L, &g))) return rc;
+  if ((rc = ragged_rows_ok(g.T, "T(L)"))) return rc;
+  const Plan p = make_plan(m, g.Bp, g.F, g.T);
+  if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ragged_check_lengths(wav_len, B, L, "wav_len", s))) return rc;
+  return encoder_impl(m, wav, g, p, (char*)ws, enc_out, s, wav_len, enc_len);
+}
+
+int mi355asr_ctc_forward_ragged(mi355asr_model* m, const float* enc, const int32_t* enc_len, int32_t B, int32_t T,
+                                float* logits, int32_t* amax, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_ready(m);
+  if (rc) return rc;
+  if (m->cfg.num_classes <= 0) return fail(MI355ASR_ESTATE, "model was created without a CTC head (num_classes=0)");
+  if (m->cfg.gemm_dtype != 0 || m->cfg.dmodel != 144)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support %s", m->cfg.gemm_dtype != 0 ? "the bf16 GEMM mode" : "dmodel other than 144");
+  if (!enc || !ws || B <= 0 || T <= 0) return fail(MI355ASR_EINVAL, "bad argument");
+  if ((rc = ragged_rows_ok(T, "T"))) return rc;
+  const Plan p = make_plan(m, B, 16, T);
+  if (ws_bytes < p.logp) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.logp);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s))) return rc;
+  return ctc_impl(m, enc, B, T, p, (char*)ws, logits, amax, s, enc_len);
+}
+
+int mi355asr_recognize_ragged(mi355asr_model* m, const float* wav, const int32_t* wav_len, int32_t B, int32_t L,
+                              const int32_t* in_len, int32_t* ids, int32_t* out_len, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_ready(m, true);
+  if (rc) return rc;
+  if (m->cfg.num_classes <= 0) return fail(MI355ASR_ESTATE, "model was created without a CTC head (num_classes=0)");
+  if ((rc = ragged_config_ok(m))) return rc;
+  if (!wav || !ids || !out_len || !ws) return fail(MI355ASR_EINVAL, "null device pointer");
+  Geometry g;
+  if ((rc = geometry(m, B, L, &g))) return rc;
+  if ((rc = ragged_rows_ok(g.T, "T(L)"))) return rc;
+  const Plan p = make_plan(m, g.Bp, g.F, g.T);
+  if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ragged_check_lengths(wav_len, B, L, "wav_len", s))) return rc;
+  char* w = (char*)ws;
+  float* enc = (float*)(w + p.enc);
+  if ((rc = encoder_impl(m, wav, g, p, w, enc, s, wav_len, nullptr))) return rc;
+  const int32_t* t_len = (const int32_t*)(w + p.umax);          // written by encoder_impl
+  int32_t* amax = (int32_t*)(w + p.amax);
+  if ((rc = ctc_impl(m, enc, B, g.T, p, w, nullptr, amax, s, t_len))) return rc;
+  CollapseArgs ca{amax, in_len, ids, out_len, B, g.T, m->cfg.num_classes - 1};
+  ca.t_len = t_len;
   { PROF(MI355ASR_K_COLLAPSE); LAUNCH_TRY(launch_collapse(ca, s), "ctc collapse"); }
   return 0;
 }
@@ -2296,7 +2435,7 @@ int mi355asr_conv_subsampling(mi355asr_model* m, const float* mel, int32_t B, in
   const int T = ceil_div(ceil_div(F, m->dm.st1), 2);
   const Plan p = make_plan(m, B, F, T);
   if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
-  return run_subsampling(m, mel, B, F, (float*)((char*)ws + p.sub), out, (hipStream_t)stream, false, nullptr);
+  return run_subsampling(m, mel, B, F, (float*)((char*)ws + p.sub), out, (hipStream_t)stream, false, nullptr, nullptr);
 }
 
 int mi355asr_conformer_block(mi355asr_model* m, int32_t stack, int32_t index, const float* x, int32_t B, int32_t T,

@@ -172,6 +172,60 @@ int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids, const flo
   return 0;
 }
 
+// ragged batches: token lengths tok_len [B] (rows of ids) and encoder lengths enc_len [B] (frames of enc), both on the device
+int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, const int32_t* tok_len, const float* enc,
+                                       const int32_t* enc_len, int32_t B, int32_t U, int32_t T, float* logits, int32_t* amax,
+                                       void* ws_, size_t ws_bytes, void* stream) {
+  if (!m || !m->is_translator) return fail(MI355ASR_EINVAL, "not a Translator handle");
+  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
+  if (m->cfg.dmodel != 144) return fail(MI355ASR_EINVAL, "ragged batches do not support dmodel other than 144 (dmodel %d)", m->cfg.dmodel);
+  if (!ids || !enc || !ws_) return fail(MI355ASR_EINVAL, "null argument");
+  if (B < 1 || U < 1 || T < 1) return fail(MI355ASR_EINVAL, "B, U, T must be positive (got %d, %d, %d)", B, U, T);
+  if (U > kMaxTokens) return fail(MI355ASR_EINVAL, "U=%d exceeds the positional-encoding table (%d rows)", U, kMaxTokens);
+  int rc = ragged_rows_ok(U, "U");
+  if (rc || (rc = ragged_rows_ok(T, "T"))) return rc;
+  const TransPlan p = make_trans_plan(m, B, U, T);
+  if (ws_bytes < p.total) return fail(MI355ASR_EINVAL, "workspace too small: %zu < %zu", ws_bytes, p.total);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ragged_check_lengths(tok_len, B, U, "tok_len", s))) return rc;
+  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s))) return rc;
+  char* ws = (char*)ws_;
+  const int d = m->cfg.dmodel, M = B * U;
+  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
+             (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
+  sc.h4 = (float*)(ws + p.h4);
+  EmbedArgs ea{ids, m->t_emb, sc.xa, M, m->tcfg.inp_classes, d};
+  LAUNCH_TRY(launch_embed(ea, s), "embedding");
+  CrossAttn cr{enc, T, (float*)(ws + p.kv), m->t_pe};
+  cr.k_len = enc_len;
+  BlockOpts bo = m->t_stack.opts;
+  bo.t_len = tok_len;                   // the ConvModule's depthwise conv reads zeros from token row tok_len[b] on
+  for (const auto& blk : m->t_stack.blocks)
+    if ((rc = run_block(m, blk, bo, sc, B, U, nullptr, s, &cr))) return rc;
+  // the class head is row-wise: the same kernels as mi355asr_translator_forward, then the rows past tok_len[b] get their values
+  GemmArgs hd{};
+  hd.x = sc.xa; hd.y = logits; hd.wp = m->t_stack.fc_wp; hd.bias = m->t_stack.fc_b;
+  hd.M = M; hd.NT = m->t_stack.NT_fc; hd.ldy = m->tcfg.tar_classes; hd.n_valid = m->tcfg.tar_classes; hd.eps = kLnEps;
+  hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
+  {
+    PROF(MI355ASR_K_CTC_HEAD);
+    if (try_head_ld(m, hd, s, (float*)(ws + p.hsplit)) == 0) {
+      if (hipGetLastError() != hipSuccess) return fail(MI355ASR_EHIP, "translator head launch failed");
+    } else if (gemm16_for(m, M)) {             // few rows: the layer-at-a-time head, as mi355asr_translator_forward takes it
+      Gemm16Args h16{};
+      h16.x = sc.xa; h16.ldx = d; h16.bias = hd.bias; h16.y = logits; h16.ldy = hd.ldy; h16.M = M; h16.K = d; h16.NT = hd.NT;
+      h16.n_valid = hd.n_valid; h16.eps = kLnEps; h16.argmax_out = hd.argmax_out;
+      h16.part_max = 8; h16.part_v = (float*)(ws + p.hsplit); h16.part_i = reinterpret_cast<int32_t*>(h16.part_v + (size_t)8 * M);
+      LAUNCH_TRY(launch_gemm16(m, E16_HEAD, false, h16, m->t_stack.fc_wp, s), "translator head");
+    } else {
+      LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "translator head");
+    }
+  }
+  const int V = m->tcfg.tar_classes;
+  LAUNCH_TRY(launch_ragged_rows(tok_len, B, U, logits, V, V, hd.argmax_out, s), "ragged Translator rows");
+  return 0;
+}
+
 // ---- stateful BeamDecoder ----------------------------------------------------------------------------------
 struct mi355asr_beam { void* st; int V, beam; };
 int mi355asr_beam_create(int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, mi355asr_beam** out) {

@@ -128,11 +128,13 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(AttnArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = lane >> 4, g4 = g * 4, c = lane & 15;
-  const int T = a.Tk, TQ = a.Tq;
+  const int TS = a.Tk, TQ = a.Tq;    // rows per utterance of k / v
   const int h = blockIdx.y, b = blockIdx.z;
+  // keys of this utterance: all TS, or (ragged batches) the first k_len[b] -- every mask below is against T
+  const int T = a.k_len ? min(a.k_len[b], TS) : TS;
   const int ld = a.ldk, D = a.D;
   // token-major: row (b T + t) of ld floats, head h at columns [36 h, 36 h + 36); head-major (round 5): row ((b H + h) T + t) of 36
-  const size_t khead = a.head_major ? ((size_t)b * a.H + h) * T * HS : (size_t)b * T * ld + h * HS;
+  const size_t khead = a.head_major ? ((size_t)b * a.H + h) * TS * HS : (size_t)b * TS * ld + h * HS;
   const float* __restrict__ kbase = a.k + khead;
   const float* __restrict__ vbase = a.v + khead;
 
@@ -302,10 +304,12 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
   constexpr float SP = TM == 2 ? 16384.f : 1.f;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = lane >> 4, g4 = g * 4, c = lane & 15;
-  const int T = a.Tk, TQ = a.Tq;
+  const int TS = a.Tk, TQ = a.Tq;    // rows per utterance of k / v
   const int h = blockIdx.y, b = blockIdx.z;
+  // keys of this utterance: all TS, or (ragged batches) the first k_len[b] -- every mask below is against T
+  const int T = a.k_len ? min(a.k_len[b], TS) : TS;
   const int ld = a.ldk, D = a.D;
-  const size_t khead = a.head_major ? ((size_t)b * a.H + h) * T * HS : (size_t)b * T * ld + h * HS;
+  const size_t khead = a.head_major ? ((size_t)b * a.H + h) * TS * HS : (size_t)b * TS * ld + h * HS;
   const float* __restrict__ kbase = a.k + khead;
   const float* __restrict__ vbase = a.v + khead;
   const int qt = blockIdx.x * LW + wv;

@@ -644,6 +644,11 @@ bool attention_takes_head_major(int HS, const AttnArgs& a) {
   return lds_env && split_env && attention_split_two_term(HS, a);
 }
 
+bool attention_applies_lengths(int HS, const AttnArgs& a) {
+  static const bool lds_env = mi355_env("MI355ASR_ATTN_LDS", 1) != 0;
+  static const bool split_env = mi355_env("MI355ASR_ATTN_SPLIT", 1) != 0;
+  return lds_env && split_env && attention_split_applicable(HS, a);
+}
 int launch_attention(int HS, const AttnArgs& a, hipStream_t s) {
   // short full-attention utterances (offline ConformerCTC): K / V^T staged in LDS (attention_lds.hip)
   // MI355ASR_ATTN_SPLIT=0: the fp32-MFMA LDS kernel of round 1 instead of the split-bf16 one (attention_split.hip);
@@ -652,6 +657,7 @@ int launch_attention(int HS, const AttnArgs& a, hipStream_t s) {
   static const bool split_env = mi355_env("MI355ASR_ATTN_SPLIT", 1) != 0;
   if (lds_env && split_env && attention_split_applicable(HS, a))
     return launch_attention_split(HS, a, s);
+  if (a.k_len) return -1;              // ragged batches: the split kernels are the ones that apply key lengths
   if (lds_env && split_env && attention_split64_applicable(HS, a))      // round 5: head size 64, operand bounds known, <= 288 keys
     return launch_attention_split64(HS, a, s);
   if (a.head_major) return -1;         // head-major q / k / v (round 5) are read by attention_split_kernel only
@@ -696,12 +702,13 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwArgs a) {
   const int tc = (idx / c4n) % tchunks;
   const int b = idx / (c4n * tchunks);
   const int t0 = tc * TT;
+  const int TV = a.t_len ? min(a.t_len[b], a.T) : a.T;          // ragged batches: rows at or past the utterance's length read 0
   const float* __restrict__ ub = a.u + (size_t)b * a.T * a.D + c4;
   f32x4 win[TT + K - 1];
 #pragma unroll
   for (int i = 0; i < TT + K - 1; ++i) {
     const int tt = t0 + i - a.pad_left;
-    win[i] = (tt >= 0 && tt < a.T) ? ldg4(ub + (size_t)tt * a.D) : splat4(0.f);
+    win[i] = (tt >= 0 && tt < TV) ? ldg4(ub + (size_t)tt * a.D) : splat4(0.f);
   }
   f32x4 acc[TT];
 #pragma unroll
@@ -747,6 +754,7 @@ __global__ __launch_bounds__(320) void dwconv_tile_kernel(DwArgs a) {
   __shared__ __attribute__((aligned(16))) float tile[ROWS * CB];
   __shared__ __attribute__((aligned(16))) float wt[K * CB];        // the K x CB taps of this channel block
   const int b = blockIdx.y, t0 = blockIdx.x * TT, c0 = blockIdx.z * CB;
+  const int TV = a.t_len ? min(a.t_len[b], a.T) : a.T;          // ragged batches: rows at or past the utterance's length read 0
   const float* __restrict__ ub = a.u + (size_t)b * a.T * a.D + c0;
   // all global loads first, then the LDS writes (a load -> write loop costs one L2 round trip per iteration)
   constexpr int NT = ((CB / 4) * 8 + 63) / 64 * 64, NL = (ROWS * C4 + NT - 1) / NT, NW = (K * C4 + NT - 1) / NT;
@@ -762,7 +770,7 @@ __global__ __launch_bounds__(320) void dwconv_tile_kernel(DwArgs a) {
     const int i = threadIdx.x + k * NT;
     const int r = i / C4, c = i - r * C4;
     const int tt = t0 + r - a.pad_left;
-    stage[k] = (i < ROWS * C4 && tt >= 0 && tt < a.T) ? ldg4(ub + (size_t)tt * a.D + 4 * c) : splat4(0.f);
+    stage[k] = (i < ROWS * C4 && tt >= 0 && tt < TV) ? ldg4(ub + (size_t)tt * a.D + 4 * c) : splat4(0.f);
   }
 #pragma unroll
   for (int k = 0; k < NL; ++k) {
@@ -814,6 +822,7 @@ static int launch_dwconv_tile(const DwArgs& a, hipStream_t s) {
 }
 
 int launch_dwconv(int K, const DwArgs& a, hipStream_t s) {
+  if (a.t_len && !(K == 32 && a.D == 144)) return -1;   // ragged batches: dwconv_tile_kernel<32, 144> / dwconv_kernel<32, 8> only
   if (a.T * a.B >= 2048) {                  // LDS-tiled kernel; below: the first-generation kernel (window re-read from L2 per thread)
     if (K == 32 && a.D == 144) return launch_dwconv_tile<32, 144>(a, s);
     if (K == 32 && a.D % 128 == 0) return launch_dwconv_tile<32, 128>(a, s);

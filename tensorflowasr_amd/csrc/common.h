@@ -28,6 +28,15 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // everything in <= 256 architectural VGPRs (no AGPR half, hence no v_accvgpr_read/write shuffling) and gives
 // every SIMD a second wave whose MFMAs cover the first one's address arithmetic and load issue.
 
+// Ragged batches: the geometry of ONE utterance of n input rows (samples, mel frames, conv1 rows) under TF 'SAME' padding --
+// out = ceil(n / s), before = max((out - 1) s + k - n, 0) / 2 -- the rule the host's same_pad applies to a whole batch
+__host__ __device__ __forceinline__ void ragged_same_pad(int n, int k, int s, int* out, int* before) {
+  const int o = (n + s - 1) / s;
+  const int tot = (o - 1) * s + k - n;
+  *out = o;
+  *before = (tot > 0 ? tot : 0) / 2;
+}
+
 // D(16x16) += A(16x4) * B(4x16); lane supplies A[i=lane&15][k=lane>>4] and B[k=lane>>4][j=lane&15];
 // result reg r of lane holds D[row = 4*(lane>>4)+r][col = lane&15]  (cdna_hip_programming.md §3).
 DEV f32x4 mfma4(float a, float b, f32x4 c) {

@@ -69,7 +69,14 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void fft_stft_kernel(FftStftArgs 
   for (int fidx = wid; fidx < total; fidx += nwaves) {
     const int b = fidx / a.F, f = fidx - b * a.F;
     const float* __restrict__ wav = a.wav + (size_t)b * L;
-    const int base = f * a.hop - a.pad_left;
+    // ragged batches: this utterance's own length and SAME framing (a.wav_len: uniform per frame, one scalar load)
+    int Lv = L, pl = a.pad_left;
+    if (a.wav_len) {
+      int fo;
+      Lv = a.wav_len[b];
+      ragged_same_pad(Lv, 1024, a.hop, &fo, &pl);
+    }
+    const int base = f * a.hop - pl;
     // ---- stage-1 operand: xw[32*n1 + n2], zero outside the signal (TF SAME / left-padded VALID framing)
     f32x4 xf[2][2];
 #pragma unroll
@@ -77,8 +84,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void fft_stft_kernel(FftStftArgs 
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int s0 = base + 32 * (16 * kb + g4) + 16 * rt + c;
-        const bool o0 = (unsigned)(s0) < (unsigned)L, o1 = (unsigned)(s0 + 32) < (unsigned)L;
-        const bool o2 = (unsigned)(s0 + 64) < (unsigned)L, o3 = (unsigned)(s0 + 96) < (unsigned)L;
+        const bool o0 = (unsigned)(s0) < (unsigned)Lv, o1 = (unsigned)(s0 + 32) < (unsigned)Lv;
+        const bool o2 = (unsigned)(s0 + 64) < (unsigned)Lv, o3 = (unsigned)(s0 + 96) < (unsigned)Lv;
         f32x4 v;
         v.x = wav[o0 ? s0 : 0]; v.y = wav[o1 ? s0 + 32 : 0]; v.z = wav[o2 ? s0 + 64 : 0]; v.w = wav[o3 ? s0 + 96 : 0];
         v.x = o0 ? v.x : 0.f; v.y = o1 ? v.y : 0.f; v.z = o2 ? v.z : 0.f; v.w = o3 ? v.w : 0.f;
@@ -340,7 +347,14 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
   for (int fidx = wid; fidx < total; fidx += nwaves) {
     const int b = fidx / a.F, f = fidx - b * a.F;
     const float* __restrict__ wav = a.wav + (size_t)b * L;
-    const int base = f * a.hop - a.pad_left;
+    // ragged batches: this utterance's own length and SAME framing (a.wav_len: uniform per frame, one scalar load)
+    int Lv = L, pl = a.pad_left;
+    if (a.wav_len) {
+      int fo;
+      Lv = a.wav_len[b];
+      ragged_same_pad(Lv, 1024, a.hop, &fo, &pl);
+    }
+    const int base = f * a.hop - pl;
     // ---- stage-1 operand: xw[32*n1 + n2], zero outside the signal (TF SAME / left-padded VALID framing)
     Split8 xs[2];
     float un1[2];                              // two-term: 1 / (stage scale x column scale) of the stage-1 accumulators
@@ -350,8 +364,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int s0 = base + 32 * (16 * kb + g4) + 16 * rt + c;
-        const bool o0 = (unsigned)(s0) < (unsigned)L, o1 = (unsigned)(s0 + 32) < (unsigned)L;
-        const bool o2 = (unsigned)(s0 + 64) < (unsigned)L, o3 = (unsigned)(s0 + 96) < (unsigned)L;
+        const bool o0 = (unsigned)(s0) < (unsigned)Lv, o1 = (unsigned)(s0 + 32) < (unsigned)Lv;
+        const bool o2 = (unsigned)(s0 + 64) < (unsigned)Lv, o3 = (unsigned)(s0 + 96) < (unsigned)Lv;
         f32x4 v;
         if constexpr (FDG & 1) v = f32x4{(float)(s0 & 7), (float)(s0 & 3), 1.f, (float)c};
         else { v.x = wav[o0 ? s0 : 0]; v.y = wav[o1 ? s0 + 32 : 0]; v.z = wav[o2 ? s0 + 64 : 0]; v.w = wav[o3 ? s0 + 96 : 0]; }

@@ -109,7 +109,9 @@ int launch_stft(const StftArgs& a, hipStream_t s) {
 __global__ void utt_max_kernel(UttMaxArgs a) {
   const int b = blockIdx.x;
   float mx = -INFINITY;
-  for (int i = threadIdx.x; i < a.n; i += 64) mx = fmaxf(mx, a.pmax[(size_t)b * a.n + i]);
+  // ragged batches: only this utterance's own frames (a.pmax holds one maximum per frame then)
+  const int n = a.wav_len ? min((a.wav_len[b] + a.hop - 1) / a.hop, a.n) : a.n;
+  for (int i = threadIdx.x; i < n; i += 64) mx = fmaxf(mx, a.pmax[(size_t)b * a.n + i]);
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
   if (threadIdx.x == 0) a.umax[b] = mx;
@@ -407,6 +409,7 @@ static int launch_subconv_cols(int D, const SubConvArgs& a, hipStream_t s) {
 }
 
 int launch_subconv(int D, const SubConvArgs& a, hipStream_t s) {
+  if (a.wav_len && a.st1 != 2) return -1;                           // ragged batches: the two kernels of reduction_factor 4 only
   if (a.st1 != 2) {                                                 // reduction_factor 2 / 6 / 8: one general kernel
     if (D % 16) return -1;
     note_scheme(SCHEME_F32);
@@ -420,6 +423,7 @@ int launch_subconv(int D, const SubConvArgs& a, hipStream_t s) {
   if (!f32k && launch_subconv_split(D, a, s) == 0) return 0;       // dmodel 144 / 256 / 512 with the split pack
   note_scheme(SCHEME_F32);
   if (D == 144) return launch_subconv144(a, s);
+  if (a.wav_len) return -1;
   if (D % 128 == 0) return launch_subconv_cols<8, 2>(D, a, s);
   return -1;
 }
@@ -485,6 +489,7 @@ __global__ __launch_bounds__(64) void collapse_kernel(CollapseArgs a) {
   const int T = a.T;
   int n = a.in_len ? a.in_len[b] : T;
   n = max(0, min(n, T));
+  if (a.t_len) n = min(n, a.t_len[b]);
   const int32_t* __restrict__ src = a.frame_ids + (size_t)b * T;
   int32_t* dst = a.ids + (size_t)b * T;
   int count = 0;
@@ -508,6 +513,44 @@ __global__ __launch_bounds__(64) void collapse_kernel(CollapseArgs a) {
 
 int launch_collapse(const CollapseArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(collapse_kernel, dim3(a.B), dim3(64), 0, s, a);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Ragged batches: per-utterance encoder frame counts, and the defined values of the rows past them.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void ragged_frames_kernel(const int32_t* __restrict__ wav_len, int B, int hop, int st1,
+                                                           int32_t* t_len, int32_t* t_out) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  int F, T1, T, pad;
+  ragged_same_pad(wav_len[b], 1, hop, &F, &pad);
+  ragged_same_pad(F, 3, st1, &T1, &pad);
+  ragged_same_pad(T1, 3, 2, &T, &pad);
+  t_len[b] = T;
+  if (t_out) t_out[b] = T;
+}
+int launch_ragged_frames(const int32_t* wav_len, int B, int hop, int st1, int32_t* t_len, int32_t* t_out, hipStream_t s) {
+  if (B <= 0 || !wav_len || !t_len) return -1;
+  hipLaunchKernelGGL(ragged_frames_kernel, dim3((B + 63) / 64), dim3(64), 0, s, wav_len, B, hop, st1, t_len, t_out);
+  return 0;
+}
+
+// one workgroup per row: rows of the utterance's own frames leave at once
+__global__ __launch_bounds__(256) void ragged_rows_kernel(const int32_t* __restrict__ t_len, int T, float* x, int ld, int n,
+                                                          int32_t* ids) {
+  const int r = blockIdx.x, b = r / T, t = r - b * T;
+  if (t < t_len[b]) return;
+  if (x) {
+    float* row = x + (size_t)r * ld;
+    for (int c = threadIdx.x; c < n; c += 256) row[c] = 0.f;
+  }
+  if (ids && threadIdx.x == 0) ids[r] = -1;
+}
+int launch_ragged_rows(const int32_t* t_len, int B, int T, float* x, int ld, int n, int32_t* ids, hipStream_t s) {
+  if (B <= 0 || T <= 0 || !t_len) return -1;
+  if (!x && !ids) return 0;
+  hipLaunchKernelGGL(ragged_rows_kernel, dim3((unsigned)(B * T)), dim3(256), 0, s, t_len, T, x, ld, n, ids);
   return 0;
 }
 

@@ -400,11 +400,13 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
   // and was bound by four serial load latencies: no faster than the separate launch).
   const int gq = lane >> 4, g4 = gq * 4, c = lane & 15;
   const int T = g.a_T, H = g.a_H, ld = g.a_ldk;
+  // keys of this utterance: T, or (ragged batches) the first a_klen[b]; T stays the row count of q / k / v
+  const int TK = g.a_klen ? min(g.a_klen[b], T) : T;
   const float sq = g.a_sq, sk = g.a_sk, sv = g.a_sv;
   constexpr float SP = 16384.f, LOG2E = 1.4426950408889634f;
   const unsigned uld = (unsigned)ld;
   const int tq = min(f0 + c, T - 1);
-  const int nkt = (T + 15) / 16;
+  const int nkt = (TK + 15) / 16;
   const bool have = 2 * w < nkt;                         // this wave's pair holds at least one real key
   const f32x4 inv_qk = splat4(1.0f / (sq * sk));
 #pragma unroll 1
@@ -423,7 +425,7 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
       for (int k2 = 0; k2 < 2; ++k2) {
         const int skey = 16 * (2 * w + k2) + c;
         const unsigned ko = (unsigned)min(skey, T - 1) * uld;
-        const bool ok = skey < T;
+        const bool ok = skey < TK;
         klo[hh][k2] = ok ? *reinterpret_cast<const f32x4*>(kbase + ko + 8u * gq) : splat4(0.f);
         khi[hh][k2] = ok ? *reinterpret_cast<const f32x4*>(kbase + ko + 8u * gq + 4u) : splat4(0.f);
         ktl[hh][k2] = ok ? kbase[ko + 32u + gq] : 0.f;
@@ -435,7 +437,7 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int dk = 16 * (j >> 2) + (j & 3);
-          ve[hh][ot][j] = (f < A_HS && key0 + dk < T) ? vbase[vo + (unsigned)dk * uld] : 0.f;      // padding features / keys: exact zeros
+          ve[hh][ot][j] = (f < A_HS && key0 + dk < TK) ? vbase[vo + (unsigned)dk * uld] : 0.f;      // padding features / keys: exact zeros
         }
       }
     }
@@ -458,10 +460,10 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
           acc = ns_mfma(kf.t[0], qf.t[0], acc);
           sc[k2] = mfma4(ktl[hh][k2] * sk, qt, acc) * inv_qk;
           const int kb = 16 * kt + g4;
-          sc[k2].x = (kb + 0 < T) ? sc[k2].x : -INFINITY;
-          sc[k2].y = (kb + 1 < T) ? sc[k2].y : -INFINITY;
-          sc[k2].z = (kb + 2 < T) ? sc[k2].z : -INFINITY;
-          sc[k2].w = (kb + 3 < T) ? sc[k2].w : -INFINITY;
+          sc[k2].x = (kb + 0 < TK) ? sc[k2].x : -INFINITY;
+          sc[k2].y = (kb + 1 < TK) ? sc[k2].y : -INFINITY;
+          sc[k2].z = (kb + 2 < TK) ? sc[k2].z : -INFINITY;
+          sc[k2].w = (kb + 3 < TK) ? sc[k2].w : -INFINITY;
           mw = fmaxf(mw, fmaxf(fmaxf(sc[k2].x, sc[k2].y), fmaxf(sc[k2].z, sc[k2].w)));
         }
         mw = group_max(mw);                            // finite: key tile 2 w holds at least one real key
@@ -598,6 +600,7 @@ DEV void ns1_dwconv(Ns1DwLds& S, const TailFf2Args& a, f32x4 (&xs)[KB], int lane
   constexpr int NT_ = NW * 64;
   const int tid = threadIdx.x;
   const int T = a.dw_T, f0 = blockIdx.x * 16 - a.dw_pad;
+  const int TV = a.dw_len ? min(a.dw_len[blockIdx.y], T) : T;    // ragged batches: rows at or past the utterance's length read 0
   const float* __restrict__ ub = a.dw_u + (size_t)blockIdx.y * T * D;
   // every global load first, then the LDS writes (one memory latency for the window and the taps, not one per loop iteration)
   constexpr int NWIN = N1_ROWS * (D / 4), NTAP = N1_K * (D / 4), RW = (NWIN + NT_ - 1) / NT_, RT_ = (NTAP + NT_ - 1) / NT_;
@@ -605,7 +608,7 @@ DEV void ns1_dwconv(Ns1DwLds& S, const TailFf2Args& a, f32x4 (&xs)[KB], int lane
 #pragma unroll
   for (int k = 0; k < RW; ++k) {
     const int i = tid + k * NT_, r = i / (D / 4), c4 = i - r * (D / 4), f = f0 + r;
-    sw[k] = (i < NWIN && f >= 0 && f < T) ? ldg4(ub + (size_t)f * D + 4 * c4) : splat4(0.f);
+    sw[k] = (i < NWIN && f >= 0 && f < TV) ? ldg4(ub + (size_t)f * D + 4 * c4) : splat4(0.f);
   }
 #pragma unroll
   for (int k = 0; k < RT_; ++k) {

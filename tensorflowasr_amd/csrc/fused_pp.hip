@@ -519,6 +519,7 @@ DEV void pp_dw_prologue(float* scratch, const TailFf2Args& a, f32x4 (&xs)[KB]) {
   float* wt = scratch + DW_ROWS * D;            // [DW_K][D]
   const int tid = threadIdx.x;
   const int T = a.dw_T, f0 = blockIdx.x * 64 - a.dw_pad;        // utterance frame of window row 0
+  const int TV = a.dw_len ? min(a.dw_len[blockIdx.y], T) : T;    // ragged batches: rows at or past the utterance's length read 0
   constexpr int NL = (DW_ROWS * DW_C4 + DW_WORK - 1) / DW_WORK, NW = (DW_K * DW_C4 + DW_WORK - 1) / DW_WORK;
   if (tid < DW_WORK) {
     f32x4 wstage[NW];
@@ -530,7 +531,7 @@ DEV void pp_dw_prologue(float* scratch, const TailFf2Args& a, f32x4 (&xs)[KB]) {
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
         const int i = tid + k * DW_WORK, r = i / DW_C4, c4 = i - r * DW_C4, f = f0 + r;
-        stage[k] = (i < DW_ROWS * DW_C4 && f >= 0 && f < T) ? ldg4(ub + (size_t)f * D + 4 * c4) : splat4(0.f);
+        stage[k] = (i < DW_ROWS * DW_C4 && f >= 0 && f < TV) ? ldg4(ub + (size_t)f * D + 4 * c4) : splat4(0.f);
       }
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
@@ -772,7 +773,9 @@ __global__ __launch_bounds__(LD_THREADS) void pp_block_kernel(TailFf2Args a, Ff1
     PpPool pl;
     pp_prime<DG>(pl, st);
     pp_pool_land(pl);
-    pp_og_tile<DG>(g, pg, st, pl, xs, y, c.lane, frame0, T, f0, scratch);      // y = x2 rows of this wave's tile
+    // (ragged batches: the window rows at or past the utterance's own length are the zeros of its padding)
+    const int TV = a.dw_len ? min(a.dw_len[blockIdx.y], T) : T;
+    pp_og_tile<DG>(g, pg, st, pl, xs, y, c.lane, frame0, TV, f0, scratch);     // y = x2 rows of this wave's tile
     pp_dw_prologue<true>(scratch, a, xs);                // waves 0..3: xs = depthwise output rows of the wave's own frames
     if (wv >= WAVES_PER_BLOCK) {                         // the halo waves join the loaders
       const PpLoader<PP_RING, DG> ld{ring, s1, s2, N1, total_rt, wv - WAVES_PER_BLOCK, (int)(threadIdx.x & 63), s0, NOG};

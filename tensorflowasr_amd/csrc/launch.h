@@ -73,6 +73,8 @@ struct AttnArgs {
   // [min(max(i-win_front,0), T-win_back), max(min(i+win_back,T), win_back)]; win_front < 0 = full attention
   // (band attention is self-attention only: Tq == Tk == T)
   int win_front, win_back;
+  // ragged batches: keys t >= k_len[b] of utterance b are excluded from the softmax (nullptr: all Tk keys); [B] on the device
+  const int32_t* k_len = nullptr;
   // two-term fp16 scheme of attention_split_kernel: powers of two with bound(|q| log2 e) * h2_sq, bound(|k|) * h2_sk,
   // bound(|v|) * h2_sv <= 2^15 (api.hip derives the bounds from the q / k / v weights and the LayerNorm in front of them);
   // 0 = unknown bounds (stage calls on caller-supplied q / k / v): the three-term bf16 kernel
@@ -89,6 +91,7 @@ struct DwArgs {
   float* y;         // [B, T, D]
   const float* wd;  // [K, D]
   int B, T, D, pad_left;
+  const int32_t* t_len = nullptr;   // ragged batches: rows t >= t_len[b] of u read as zeros (nullptr: T)
 };
 
 // frontend / subsampling (frontend.hip)
@@ -112,6 +115,9 @@ struct FftStftArgs {
   const float* window;  // [1024]
   int B, L, F, hop, pad_left, LP;
   int db10;
+  // ragged batches: utterance b is wav_len[b] samples long -- its own SAME framing (pad_left of its length), samples at or past
+  // wav_len[b] read as zeros (nullptr: every row is L samples, framed with pad_left); n_dft = 1024
+  const int32_t* wav_len = nullptr;
   // the two DFT-32 stage matrices as split-bf16 fragments (pack_split32: [steps][tiles][3 terms][64 lanes][8]) for the bf16
   // matrix pipe (fft_stft_split_kernel, round 3), or null
   const float* w1s = nullptr;   // stage 1: K = 32 (n1), 64 columns -> [1][4][3][64][8]
@@ -119,7 +125,12 @@ struct FftStftArgs {
   const float *w1h = nullptr, *w2h = nullptr;   // the same two matrices times 2^14 as hi + lo fp16 terms ([..][2][64][8]; two-term scheme)
 };
 int launch_fft_stft(const FftStftArgs& a, hipStream_t s);
-struct UttMaxArgs { const float* pmax; float* umax; int n; };
+struct UttMaxArgs {
+  const float* pmax; float* umax; int n;
+  // ragged batches (per-frame maxima only): utterance b covers ceil(wav_len[b] / hop) frames of its n (nullptr: all n)
+  const int32_t* wav_len = nullptr;
+  int hop = 0;
+};
 struct MelArgs {
   const float* logp;  // [B, F, LP]
   const float* umax;  // [B] or nullptr (no max-normalisation / floor: 'valid' chunk frontend)
@@ -162,6 +173,10 @@ struct SubConvArgs {
   int B, F, NM, T1, F1, T2, F2;
   int st1;            // conv1 time stride (reduction_factor/2)
   int pt1, pf1, pt2, pf2;  // pad-before of conv1 (time,freq) and conv2 (time,freq)
+  // ragged batches: utterance b has ceil(wav_len[b] / hop) mel frames; F, T1, pt1, pt2 of that length replace the batch's, rows past
+  // them read as zeros (nullptr: the batch geometry above)
+  const int32_t* wav_len = nullptr;
+  int hop = 0;
 };
 struct StreamGemmArgs {
   const float* x;     // [M, K]
@@ -176,6 +191,7 @@ struct CollapseArgs {
   int32_t* ids;              // [B, T] padded with -1
   int32_t* out_len;          // [B]
   int B, T, blank;
+  const int32_t* t_len = nullptr;  // ragged batches: [B] frames of each utterance; the collapse stops at min(in_len, t_len)
 };
 
 struct PickArgs {
@@ -359,6 +375,7 @@ struct OutGluArgs {
   const float *aq = nullptr, *ak = nullptr, *av = nullptr;
   int a_T = 0, a_H = 0, a_ldq = 0, a_ldk = 0, a_head_major = 0;
   float a_sq = 0.f, a_sk = 0.f, a_sv = 0.f;
+  const int32_t* a_klen = nullptr;   // ragged batches: AttnArgs::k_len of that attention
 };
 struct TailFf2Args {
   const float* dw; const float* x2; float* y;
@@ -375,6 +392,7 @@ struct TailFf2Args {
   const float* dw_u = nullptr;
   const float* dw_wd = nullptr;
   int dw_T = 0, dw_pad = 0;
+  const int32_t* dw_len = nullptr;   // ragged batches: rows t >= dw_len[b] of u (the GLU output) read as zeros (nullptr: dw_T)
   // round 4: the class head behind the block (the CTC decoder's last block; out-projection + GLU kernels without a next block):
   // logits = y W + b over head_groups column groups of nine tiles from the two-term stream head_pp (pp_head_kernel's loop),
   // per-frame arg-max / maximum and / or the logits; y itself is stored only if `y` is set
@@ -439,6 +457,7 @@ bool attention_lds_applicable(int HS, const AttnArgs& a);
 int launch_attention_lds(int HS, const AttnArgs& a, hipStream_t s);
 bool attention_split_applicable(int HS, const AttnArgs& a);
 bool attention_split_two_term(int HS, const AttnArgs& a);
+bool attention_applies_lengths(int HS, const AttnArgs& a);   // blocks.hip: launch_attention would take a kernel that reads a.k_len
 bool attention_takes_head_major(int HS, const AttnArgs& a);   // blocks.hip: launch_attention's own switches included   // the two-term kernel would take this launch (head-major operands allowed)
 int launch_attention_split(int HS, const AttnArgs& a, hipStream_t s);
 bool attention_split64_applicable(int HS, const AttnArgs& a);   // attention_split64.hip: head size 64, two fp16 terms, <= 288 keys
@@ -455,3 +474,7 @@ int launch_subconv144(const SubConvArgs& a, hipStream_t s);
 int launch_subconv_split(int d, const SubConvArgs& a, hipStream_t s);   // split-bf16 ring kernel (dmodel 144 / 256 / 512); -1: not supported, nothing launched
 int launch_stream_gemm(int D, const StreamGemmArgs& a, hipStream_t s);
 int launch_collapse(const CollapseArgs& a, hipStream_t s);
+// ragged batches (frontend.hip): t_len[b] (and t_out[b], if set) = encoder frames of a wav_len[b]-sample utterance
+int launch_ragged_frames(const int32_t* wav_len, int B, int hop, int st1, int32_t* t_len, int32_t* t_out, hipStream_t s);
+// rows t >= t_len[b] of [B, T] row-major outputs get defined values: x (ld floats per row, the first n written) 0, ids -1
+int launch_ragged_rows(const int32_t* t_len, int B, int T, float* x, int ld, int n, int32_t* ids, hipStream_t s);

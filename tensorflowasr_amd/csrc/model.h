@@ -100,6 +100,9 @@ struct BlockOpts {
   float head_sw = 1.f;
   int head_groups = 0;
   bool* head_done = nullptr;
+  // ragged batches: utterance b has t_len[b] of the T frames ([B] on the device): its attention sees only those keys and its
+  // depthwise conv reads zeros from frame t_len[b] on.  Only the dmodel-144 fused kernels apply it; run_block refuses the rest.
+  const int32_t* t_len = nullptr;
 };
 
 struct StackDev {
@@ -289,6 +292,7 @@ struct CrossAttn {
   int T_enc;
   float* kv;          // scratch [B * T_enc, 2d]
   const float* pe;    // [>= T, d]
+  const int32_t* k_len = nullptr;   // ragged batches: encoder frames of each utterance ([B] on the device): keys past them are excluded
 };
 
 struct StackOff {
@@ -336,7 +340,10 @@ int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, cons
 int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int B, int T, float* out,
               hipStream_t s, const CrossAttn* cross = nullptr, const BlockDev* next = nullptr, bool* ff1_done = nullptr,
               bool skip_ff1 = false);
-bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);   // run_block(w, M rows) can take BlockOpts::pre_*
+bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);
+// ragged batches (api.hip): more than 16 rows per utterance, or EINVAL; the device lengths read back and held to [1, hi]
+int ragged_rows_ok(int T, const char* what);
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s);   // run_block(w, M rows) can take BlockOpts::pre_*
 void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V);   // api_chunk.hip
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip

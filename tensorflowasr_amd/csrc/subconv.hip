@@ -106,7 +106,15 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void subconv144_kernel(SubConvArg
     const int b = p / (a.T2 * a.F2);
     const int r = p % (a.T2 * a.F2);
     const int t2 = r / a.F2, f2 = r % a.F2;
-    const int tm0 = 4 * t2 - 2 * a.pt2 - a.pt1;
+    // ragged batches: this utterance's own F, T1 and SAME top paddings (see subconv_split_ring_kernel)
+    int F = a.F, T1 = a.T1, pt1 = a.pt1, pt2 = a.pt2;
+    if (a.wav_len) {
+      int t2_;
+      F = (a.wav_len[b] + a.hop - 1) / a.hop;
+      ragged_same_pad(F, 3, a.st1, &T1, &pt1);
+      ragged_same_pad(T1, 3, 2, &t2_, &pt2);
+    }
+    const int tm0 = 4 * t2 - 2 * pt2 - pt1;
     const int fm0 = 4 * f2 - 2 * a.pf2 - a.pf1;
     const float* __restrict__ mb = a.mel + (size_t)b * a.F * a.NM;
 #pragma unroll
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void subconv144_kernel(SubConvArg
 #pragma unroll
       for (int j = 0; j < 7; ++j) {
         const int fm = fm0 + j;
-        cx.win[i][j] = (tm >= 0 && tm < a.F && fm >= 0 && fm < a.NM) ? mb[(size_t)tm * a.NM + fm] : 0.f;
+        cx.win[i][j] = (tm >= 0 && tm < F && fm >= 0 && fm < a.NM) ? mb[(size_t)tm * a.NM + fm] : 0.f;
       }
     }
     cx.valid = 0;
@@ -123,8 +131,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void subconv144_kernel(SubConvArg
     for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
       for (int kf = 0; kf < 3; ++kf) {
-        const int t1 = 2 * t2 + kt - a.pt2, f1 = 2 * f2 + kf - a.pf2;
-        const unsigned ok = (unsigned)((t1 >= 0) & (t1 < a.T1) & (f1 >= 0) & (f1 < a.F1));
+        const int t1 = 2 * t2 + kt - pt2, f1 = 2 * f2 + kf - a.pf2;
+        const unsigned ok = (unsigned)((t1 >= 0) & (t1 < T1) & (f1 >= 0) & (f1 < a.F1));
         cx.valid |= ok << (kt * 3 + kf);
       }
   }
@@ -611,6 +619,14 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g4 = (lane >> 4) * 4, c = lane & 15;
   const int b = blockIdx.y, r0 = blockIdx.x * (SCW * 16 * RTN), PU = a.T2 * a.F2;
+  // ragged batches: this utterance's mel frames F, conv1 rows T1 and both SAME top paddings (a.wav_len; else the batch's)
+  int F = a.F, T1 = a.T1, pt1 = a.pt1, pt2 = a.pt2;
+  if (a.wav_len) {
+    int t2_;
+    F = (a.wav_len[b] + a.hop - 1) / a.hop;
+    ragged_same_pad(F, 3, a.st1, &T1, &pt1);
+    ragged_same_pad(T1, 3, 2, &t2_, &pt2);
+  }
   const u32x4* __restrict__ wg = reinterpret_cast<const u32x4*>(TM == 2 ? a.w2h : a.w2s) + (size_t)blockIdx.z * NK32 * SLABF;
   float s1 = TM == 2 ? a.h_scale : 1.f;
   if (TM == 2 && a.h_melmax) {                   // features without a static bound: the scale from the UTTERANCE's own maximum
@@ -640,7 +656,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   }
   // mel patch: rows tm_base .. + rows, bins fm_base .. + RS (zero outside the utterance / the mel range)
   const int t2a = r0 / a.F2;
-  const int tm_base = 4 * t2a - 2 * a.pt2 - a.pt1, fm_base = -2 * a.pf2 - a.pf1;
+  const int tm_base = 4 * t2a - 2 * pt2 - pt1, fm_base = -2 * a.pf2 - a.pf1;
   const float* __restrict__ mbp = a.mel + (size_t)b * a.F * a.NM;
   const int RSL = 4 * RS.seg;                    // bins per patch row (4 (F2 + 1): the last window reaches bin 4 F2 + 3)
   const unsigned plane = (unsigned)rows * C1_ROWB;                                        // C1M: bytes of one fp16 plane
@@ -652,7 +668,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     for (int i = threadIdx.x; i < rows * RD; i += SCT) {
       const int rr = i / RD, jp = i - rr * RD;
       const int tm = tm_base + rr, fm = fm_base + 2 * jp;
-      const bool okr = tm >= 0 && tm < a.F;
+      const bool okr = tm >= 0 && tm < F;
       const float v0 = (okr && fm >= 0 && fm < a.NM) ? mbp[(size_t)tm * a.NM + fm] * sm : 0.f;
       const float v1 = (okr && fm + 1 >= 0 && fm + 1 < a.NM) ? mbp[(size_t)tm * a.NM + fm + 1] * sm : 0.f;
       const unsigned h = pk_f16(v0, v1);
@@ -666,7 +682,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     const int rr = i / RSL, jj = i - rr * RSL;
     const int tm = tm_base + rr, fm = fm_base + jj;
     melp[MI355ASR_CONV1_V2 ? rr * RS.row + jj : rr * RS.row + (jj & 3) * RS.seg + (jj >> 2)] =
-        (tm >= 0 && tm < a.F && fm >= 0 && fm < a.NM) ? mbp[(size_t)tm * a.NM + fm] : 0.f;
+        (tm >= 0 && tm < F && fm >= 0 && fm < a.NM) ? mbp[(size_t)tm * a.NM + fm] : 0.f;
   }
   }
   {
@@ -694,8 +710,8 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
       for (int kf = 0; kf < 3; ++kf) {
-        const int t1 = 2 * t2 + kt - a.pt2, f1 = 2 * f2 + kf - a.pf2;
-        vm |= (unsigned)((t1 >= 0) & (t1 < a.T1) & (f1 >= 0) & (f1 < a.F1)) << (kt * 3 + kf);
+        const int t1 = 2 * t2 + kt - pt2, f1 = 2 * f2 + kf - a.pf2;
+        vm |= (unsigned)((t1 >= 0) & (t1 < T1) & (f1 >= 0) & (f1 < a.F1)) << (kt * 3 + kf);
       }
     sl.valid[rt] = vm;
   }

@@ -57,6 +57,53 @@ def default_weights(names_and_shapes, rng, sample_rate=16000, n_dft=1024, n_mels
     return w
 
 
+def ragged_geometry(L, hop=160, n_dft=1024, reduction_factor=4):
+    """The per-utterance shapes of a ragged batch (include/mi355asr.h): an utterance of L samples has F = ceil(L / hop) mel
+    frames framed with pad_left zeros in front (TF 'SAME'), T1 = ceil(F / (reduction_factor / 2)) conv1 rows with pt1 zero rows
+    on top, T = ceil(T1 / 2) encoder frames with pt2 zero rows on top of conv2 -- what the kernels derive from wav_len."""
+    def same(n, k, s):
+        o = -(-n // s)
+        return o, max((o - 1) * s + k - n, 0) // 2
+    F, pad_left = same(int(L), n_dft, hop)
+    T1, pt1 = same(F, 3, reduction_factor // 2)
+    T, pt2 = same(T1, 3, 2)
+    return dict(F=F, pad_left=pad_left, T1=T1, pt1=pt1, T=T, pt2=pt2)
+
+
+def _lengths(h, lengths, B, what):
+    """[B] lengths of a ragged batch as a contiguous int32 device tensor"""
+    t = h.to_device(lengths, torch.int32).reshape(-1).contiguous()
+    if t.numel() != B:
+        raise ValueError("%s: %d entries for a batch of %d" % (what, t.numel(), B))
+    return t
+
+
+def _encoder_ragged(h, x, lengths, dmodel):
+    """mi355asr_encoder_forward_ragged on the handle: wav x [B, L] on the device -> (enc [B, T, dmodel], enc_lengths [B])"""
+    B, L = x.shape
+    T = h.out_frames(L)[1]
+    out = torch.empty((B, T, dmodel), dtype=torch.float32, device=h.device)
+    ws, n = h.ws_for_wave(B, L)
+    wl = _lengths(h, lengths, B, "lengths")
+    el = torch.empty((B,), dtype=torch.int32, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(h.lib.mi355asr_encoder_forward_ragged(h.ptr, _p(x), _p(wl), B, L, _p(out), _p(el), _p(ws), n, h._stream()))
+    return out, el
+
+
+def _ctc_ragged(h, x, lengths, num_classes, return_logits=True):
+    """mi355asr_ctc_forward_ragged on the handle: enc x [B, T, d] -> (logits [B, T, V] or None, frame argmax [B, T])"""
+    B, T, _ = x.shape
+    logits = torch.empty((B, T, num_classes), dtype=torch.float32, device=h.device) if return_logits else None
+    amax = torch.empty((B, T), dtype=torch.int32, device=h.device)
+    ws, n = h.ws_for_frames(B, T)
+    tl = _lengths(h, lengths, B, "lengths")
+    with torch.cuda.device(h.device):
+        _lib.check(h.lib.mi355asr_ctc_forward_ragged(h.ptr, _p(x), _p(tl), B, T, _p(logits) if return_logits else None, _p(amax),
+                                                     _p(ws), n, h._stream()))
+    return logits, amax
+
+
 class _Handle:
     """Owns one `mi355asr_model*` plus its device workspace."""
 
@@ -372,14 +419,19 @@ class ConformerEncoder(_ModelBase):
                                self.n_mels, leaf=self.mel_layer_type == "leaf", add_wav_info=self.add_wav_info,
                                spectrogram=self.mel_layer_type == "Spectrogram")
 
-    def __call__(self, inputs, training=False, **kwargs):
-        """wav [B, L, 1] (or [B, L]) float32 -> torch.Tensor [B, T, dmodel] on the device."""
+    def __call__(self, inputs, training=False, lengths=None, **kwargs):
+        """wav [B, L, 1] (or [B, L]) float32 -> torch.Tensor [B, T, dmodel] on the device.
+        lengths ([B] samples per utterance, 1 <= lengths[b] <= L): a ragged batch -- returns (enc, enc_lengths), row b being
+        what the call on wav[b, :lengths[b]] alone returns in its first enc_lengths[b] frames, zeros after them
+        (mi355asr_encoder_forward_ragged)."""
         if training:
             raise NotImplementedError("inference path only (training=False)")
         h = self._h
         if not h.built:
             self._build()
         x = _wave2d(h, inputs)
+        if lengths is not None:
+            return _encoder_ragged(h, x, lengths, self.dmodel)
         B, L = x.shape
         _, T = h.out_frames(L)
         out = torch.empty((B, T, self.dmodel), dtype=torch.float32, device=h.device)
@@ -469,10 +521,12 @@ class CTCDecoder(_ModelBase):
         return _ctc_shapes(self.dmodel, self.num_heads, self.head_size, self.kernel_size, self.num_blocks,
                            self.num_classes)
 
-    def __call__(self, inputs, training=None, mask=None, return_argmax=False, return_logits=True):
+    def __call__(self, inputs, training=None, mask=None, return_argmax=False, return_logits=True, lengths=None):
         """enc [B, T, dmodel] -> logits [B, T, num_classes] (torch, on device).  return_argmax: (logits, per-frame argmax);
         with return_logits=False the logits are never written (mi355asr_ctc_forward takes NULL: the class head keeps only its
-        running argmax -- what a greedy decode needs) and the first element is None."""
+        running argmax -- what a greedy decode needs) and the first element is None.
+        lengths ([B] frames per utterance): a ragged batch (mi355asr_ctc_forward_ragged) -- rows past lengths[b] hold logits 0
+        and argmax -1."""
         if training:
             raise NotImplementedError("inference path only")
         h = self._h
@@ -484,6 +538,9 @@ class CTCDecoder(_ModelBase):
             raise ValueError("nothing to return: return_logits=False needs return_argmax=True")
         logits = torch.empty((B, T, self.num_classes), dtype=torch.float32, device=h.device) if return_logits else None
         amax = torch.empty((B, T), dtype=torch.int32, device=h.device)
+        if lengths is not None:
+            logits, amax = _ctc_ragged(h, x, lengths, self.num_classes, return_logits)
+            return (logits, amax) if return_argmax else logits
         ws, n = h.ws_for_frames(B, T)
         with torch.cuda.device(h.device):
             _lib.check(h.lib.mi355asr_ctc_forward(h.ptr, _p(x), B, T, _p(logits) if return_logits else None, _p(amax), _p(ws), n, h._stream()))
@@ -521,19 +578,25 @@ class Translator(_ModelBase):
         s["fully_connected/bias"] = (self.tar_classes,)
         return s
 
-    def __call__(self, x, training=None, mask=None, return_argmax=False, return_logits=True):
+    def __call__(self, x, training=None, mask=None, return_argmax=False, return_logits=True, token_lengths=None,
+                 enc_lengths=None):
         """x = [ids int [B, U], enc float [B, T, dmodel]] -> logits [B, U, tar_classes] (torch, on device).  return_argmax:
         (logits, per-token argmax); with return_logits=False the logits are never written (the class head keeps its running
-        argmax only -- what offline_stt consumes, test_asr.py:203-205): (None, argmax)."""
+        argmax only -- what offline_stt consumes, test_asr.py:203-205): (None, argmax).
+        token_lengths / enc_lengths ([B] each, both or neither): a ragged batch (mi355asr_translator_forward_ragged) -- row b is
+        what the call on ids[b, :token_lengths[b]] and enc[b, :enc_lengths[b]] returns; rows past token_lengths[b] hold
+        logits 0 and argmax -1."""
         if training:
             raise NotImplementedError("inference path only")
         ids, enc = x
-        return self._forward(ids, enc, return_argmax, return_logits)
+        if (token_lengths is None) != (enc_lengths is None):
+            raise ValueError("a ragged Translator call takes token_lengths and enc_lengths together")
+        return self._forward(ids, enc, return_argmax, return_logits, token_lengths, enc_lengths)
 
     def set_inference_func(self):
         self.inference = lambda inputs, enc: self._forward(inputs, enc, False)
 
-    def _forward(self, ids, enc, return_argmax, return_logits=True):
+    def _forward(self, ids, enc, return_argmax, return_logits=True, token_lengths=None, enc_lengths=None):
         h = self._h
         if not h.built:
             self._build()
@@ -555,8 +618,14 @@ class Translator(_ModelBase):
         _lib.check(h.lib.mi355asr_translator_workspace_bytes(h.ptr, B, U, T, ctypes.byref(n)))
         ws = h.workspace(n.value)
         with torch.cuda.device(h.device):
-            _lib.check(h.lib.mi355asr_translator_forward(h.ptr, _p(idt), _p(e), B, U, T, _p(logits) if return_logits else None, _p(amax),
-                                                         _p(ws), n.value, h._stream()))
+            if token_lengths is not None:
+                tl, el = _lengths(h, token_lengths, B, "token_lengths"), _lengths(h, enc_lengths, B, "enc_lengths")
+                _lib.check(h.lib.mi355asr_translator_forward_ragged(h.ptr, _p(idt), _p(tl), _p(e), _p(el), B, U, T,
+                                                                    _p(logits) if return_logits else None, _p(amax), _p(ws),
+                                                                    n.value, h._stream()))
+            else:
+                _lib.check(h.lib.mi355asr_translator_forward(h.ptr, _p(idt), _p(e), B, U, T, _p(logits) if return_logits else None,
+                                                             _p(amax), _p(ws), n.value, h._stream()))
         return (logits, amax) if return_argmax else logits
 
 
@@ -656,13 +725,16 @@ class ConformerCTC(_ModelBase):
         self._lens = torch.empty((B,), dtype=torch.int32, device=h.device)
         return T
 
-    def recognize(self, wav, input_length=None, reuse_buffers=False, out=None):
+    def recognize(self, wav, input_length=None, reuse_buffers=False, out=None, wav_lengths=None):
         """wav [B,L(,1)] on device -> (ids int32 [B,T] padded -1, lengths int32 [B]).  Asynchronous.
         reuse_buffers=True returns the model's own pre-allocated output tensors (no allocation, no copy -- what the
         C-ABI call writes into); the NEXT recognize() of the same shape overwrites them, so only use it when the
         results are consumed before the next call.  out=(ids, lens): the C-ABI call writes into these contiguous int32
         device tensors of shapes [B, T] and [B] instead (a caller that keeps several batches in flight, e.g. while
-        their ids travel over RCCL, rotates its own buffers)."""
+        their ids travel over RCCL, rotates its own buffers).
+        wav_lengths ([B] samples per utterance): a ragged batch (mi355asr_recognize_ragged) -- row b is what the call on
+        wav[b, :wav_lengths[b]] alone returns (its collapse stops at its own frames, or input_length[b] if smaller).  A ragged
+        call is not asynchronous: it reads the lengths back once to check them."""
         h = self._h
         if not h.built:
             self._build()
@@ -681,17 +753,27 @@ class ConformerCTC(_ModelBase):
                                     tuple(o_ids.shape) == (B, T) and o_lens.is_cuda and o_lens.dtype == torch.int32 and
                                     o_lens.is_contiguous() and tuple(o_lens.shape) == (B,)):
             raise ValueError("out=(ids, lens): contiguous int32 device tensors of shapes [%d, %d] and [%d]" % (B, T, B))
+        wl = None if wav_lengths is None else _lengths(h, wav_lengths, B, "wav_lengths")
         with torch.cuda.device(h.device):
-            _lib.check(h.lib.mi355asr_recognize(h.ptr, _p(x), B, L, _p(il), _p(o_ids), _p(o_lens), _p(ws), n,
-                                                h._stream()))
+            if wl is not None:
+                _lib.check(h.lib.mi355asr_recognize_ragged(h.ptr, _p(x), _p(wl), B, L, _p(il), _p(o_ids), _p(o_lens), _p(ws),
+                                                           n, h._stream()))
+            else:
+                _lib.check(h.lib.mi355asr_recognize(h.ptr, _p(x), B, L, _p(il), _p(o_ids), _p(o_lens), _p(ws), n,
+                                                    h._stream()))
         if reuse_buffers or out is not None:
             return o_ids, o_lens
         return self._ids.clone(), self._lens.clone()
 
     __call__ = recognize
 
-    def encode(self, wav):
+    def encode(self, wav, lengths=None):
+        """lengths: a ragged batch -- returns (enc, enc_lengths) as ConformerEncoder(x, lengths=...) does"""
         h = self._h
+        if lengths is not None:
+            if not h.built:
+                self._build()
+            return _encoder_ragged(h, _wave2d(h, wav), lengths, self.dmodel)
         x = _wave2d(h, wav)
         B, L = x.shape
         T = h.out_frames(L)[1]
@@ -701,8 +783,12 @@ class ConformerCTC(_ModelBase):
             _lib.check(h.lib.mi355asr_encoder_forward(h.ptr, _p(x), B, L, _p(out), _p(ws), n, h._stream()))
         return out
 
-    def ctc_logits(self, enc, return_argmax=False):
+    def ctc_logits(self, enc, return_argmax=False, lengths=None):
+        """lengths ([B] frames per utterance): a ragged batch (mi355asr_ctc_forward_ragged)"""
         h = self._h
+        if lengths is not None:
+            logits, amax = _ctc_ragged(h, h.to_device(enc), lengths, self.num_classes)
+            return (logits, amax) if return_argmax else logits
         x = h.to_device(enc)
         B, T, _ = x.shape
         logits = torch.empty((B, T, self.num_classes), dtype=torch.float32, device=h.device)

@@ -5,8 +5,9 @@ recognition per segment.
     for r in session.send('long.wav'):
         print(r['sentence_begin_time'], r['sentence_end_time'], r['best_text'])
 
-Each segment is decoded as its own utterance (`ASR.offline_stt_wave` on the slice): the encoder has no mask, so
-padding segments into one batch would change their results.  Punctuation (the reference's Punc model) is not
+Each segment is decoded as its own utterance (`ASR.offline_stt_wave` on the slice): zero-padding segments into one plain
+batch would change their results.  `ASR.offline_stt_batch(segments)` decodes segments of different lengths in ragged
+batches (mi355asr_*_ragged) with the per-segment results, for callers that batch them.  Punctuation (the reference's Punc model) is not
 applied; `best_text` is the Translator's text.  The segmentation is the reference's OfflineVAD (vad.py), including
 its behaviour of returning at most one segment, from the first speech onset to the end of the recording."""
 import numpy as np
