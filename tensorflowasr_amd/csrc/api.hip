@@ -466,21 +466,6 @@ void put_head_slabs(ArenaBuilder& ab, size_t p16_off, const std::function<float(
   const size_t o_pp = ab.put(pp);
   ab.head_pairs.push_back({p16_off, o_st, groups, o_pp, sw, ab.put(plain)});
 }
-int try_head_ld(const mi355asr_model* m, const GemmArgs& hd, hipStream_t s, float* split_scratch) {
-  // a launch of the ring kernel costs as much for 250 rows as for 16 000: from 2048 rows on
-  if (m->cfg.gemm_dtype != 0 || m->head_of.empty()) return -1;
-  const auto it = m->head_of.find(hd.wp);
-  if (it == m->head_of.end()) return -1;
-  // round 6, small batches: one 16-token tile per workgroup, the column tiles split over its waves (fused_ns.hip)
-  if (launch_ns1_head(hd, it->second.ns, it->second.pp_sw, it->second.groups, s) == 0) return 0;
-  if (hd.M < 2048) return -1;
-  // few rows and many classes (the Translator's 144 -> 9160 over ~6 000 rows is 93 row workgroups): the column groups split over
-  // several workgroups per row tile, the per-range arg-max pairs combined by a second small launch (split_scratch: 16 M words)
-  if ((split_scratch || (!hd.argmax_out && !hd.maxval_out)) && launch_pp_head_split(hd, it->second.pp, it->second.pp_sw, it->second.groups, pp_head_ranges(hd.M, it->second.groups), split_scratch, s) == 0) return 0;
-  if (launch_pp_head(hd, it->second.pp, it->second.pp_sw, it->second.groups, s) == 0) return 0;
-  return launch_head_ld(hd, it->second.slabs, it->second.groups, s);
-}
-
 BlockOff pack_block(mi355asr_model* m, ArenaBuilder& ab, const std::string& p, int d, int H, int hs, int k,
                     bool keras_mha) {
   auto T = [&](const std::string& n) -> const std::vector<float>& { return m->host[n].data; };
@@ -738,24 +723,6 @@ BlockDev resolve(const BlockOff& o, const float* base) {
   return b;
 }
 
-// Layer-at-a-time GEMM family (bf16.hip) instead of the fused / chained fp32 kernels: in bf16 mode, and in fp32 for
-// dmodel values those kernels are not instantiated for (e.g. 512 = ConformerL).
-bool use_gemm16(const mi355asr_model* m) {
-  static const bool force = mi355_env("MI355ASR_GEMM16", 0) != 0;
-  // dmodel 256 with slab rings (gemm_ring.hip): one launch per dense layer on the split-bf16 pipe beats the fp32 chains
-  return force || m->cfg.gemm_dtype == 1 || (m->cfg.dmodel != 144 && m->cfg.dmodel != 256) ||
-         (m->cfg.dmodel == 256 && !m->ring_of.empty());
-}
-// Very few rows (one streaming chunk of 13 frames, the Translator's token stream): the fused kernels give each 16-row tile
-// to ONE wave that walks a whole run of layers serially -- a fused launch takes as long for 16 rows as for 16 000 -- and one
-// launch per layer with K / column splitting is as fast.  From a few tiles on the fused path wins: round 4 measured ONE
-// utterance (ms per recognize(), fused vs layer-at-a-time) 10 s / 250 rows 1.234 vs 1.386, 5 s / 125 rows 1.143 vs 1.263,
-// 2 s / 50 rows 1.118 vs 1.224, and B = 2, 3 at 10 s 1.241 / 1.252 vs 1.513 / 1.651 (profiles/r04_batch_sweep.md; the
-// round-2 ring kernels had crossed at ~800 rows, which is where this threshold stood until round 4).  MI355ASR_SMALL_M overrides.
-bool gemm16_for(const mi355asr_model* m, size_t M) {
-  static const long small_m = mi355_env("MI355ASR_SMALL_M", 48);
-  return use_gemm16(m) || (long)M <= small_m;
-}
 int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, const float* wp, hipStream_t s) {
   // long batches of dmodel 256 / 512: the same layer with the weights as a slab ring shared by eight waves
   // (gemm_ring.hip): fp32 operands exactly split into three bf16 terms, or one bf16 term in bf16 mode
@@ -832,364 +799,6 @@ int geometry(const mi355asr_model* m, int B, int L, Geometry* g) {
 }
 
 // ---- launch sequences ---------------------------------------------------------------------------------
-
-// One ConformerBlock (conformer_blocks.py:259-265).  Input in sc.xa, output to `out` (or sc.xa if null).
-// Input in sc.xa; output to `out`, or (out == nullptr) left in sc.xa -- the fused path ping-pongs xa/xb by swapping
-// the two pointers in `sc` instead of copying.
-// RBlock of the Translator (conformer_blocks.py:455-463, 496-503): the attention is a cross-attention with
-// q = LN(x + PE) and k = v = the encoder output (T_enc frames per utterance), everything else is a ConformerBlock.
-
-static bool fused_env_on() {
-  static const bool on = mi355_env("MI355ASR_FUSED", 1) != 0;
-  return on;
-}
-bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M) {
-  return m->cfg.dmodel == 144 && fused_env_on() && !gemm16_for(m, M) && w.pp_ff1 && w.ff1_slabs && ff1_pre_selected();
-}
-
-int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int B, int T,
-              float* out, hipStream_t s, const CrossAttn* cross, const BlockDev* next, bool* ff1_done, bool skip_ff1) {
-  if (ff1_done) *ff1_done = false;
-  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size;
-  const int ksz = bo.ksz;
-  const float fc = bo.fc;
-  const int M = B * T;
-  const bool fused_env = fused_env_on();
-  if (bo.pre_pp && (cross || skip_ff1 || !block_takes_pre(m, w, (size_t)M)))
-    return fail(MI355ASR_ESTATE, "run_block: a layer in front of a block that cannot take it");
-  // (ragged batches: the fused kernels, or the layer-at-a-time fp32 launches of at most MI355ASR_SMALL_M rows)
-  if (bo.t_len && (d != 144 || use_gemm16(m) || (!fused_env && !gemm16_for(m, M))))
-    return fail(MI355ASR_EINVAL, "ragged batches: only the fp32 dmodel-144 block kernels apply lengths (dmodel %d%s%s)", d,
-                fused_env ? "" : ", MI355ASR_FUSED=0", use_gemm16(m) ? ", bf16 / layer-at-a-time GEMM mode" : "");
-  if (gemm16_for(m, M)) {
-    // one launch per dense layer (bf16.hip: bf16 or fp32 operands); LayerNorm / softmax / activations / depthwise conv in fp32
-    auto g16 = [&](const float* x, int ldx, int K, const float* wp, const float* bias, int NT, float* y, int ldy) {
-      Gemm16Args g{};
-      g.x = x; g.ldx = ldx; g.K = K; g.wp = wp; g.bias = bias; g.NT = NT; g.y = y; g.ldy = ldy;
-      g.M = M; g.n_valid = 16 * NT; g.eps = kLnEps; g.scale = 1.0f;
-      return g;
-    };
-    // round 4: bf16 mode, dmodel 256: FFModule and ConvModule tail as ONE launch each (bf16.hip: chain256_bf16_kernel; the
-    // hidden activation stays in LDS) -- MI355ASR_CHAIN256=0: one gemm16 / gemm_ring launch per layer
-    static const bool chain_env = mi355_env("MI355ASR_CHAIN256", 1) != 0;
-    auto ring = [&](const float* wp) -> const float* { const auto it = m->ring_of.find(wp); return it == m->ring_of.end() ? nullptr : it->second; };
-    const float* cr[6] = {ring(w.ff_w1p[0]), ring(w.ff_w2p[0]), ring(w.ff_w1p[1]), ring(w.ff_w2p[1]), ring(w.pc_w1p), ring(w.pw2_wp)};
-    const bool chain256 = m->cfg.gemm_dtype == 1 && d == 256 && chain_env && !cross && cr[0] && cr[1] && cr[2] && cr[3] && cr[4] && cr[5];
-    auto ffn = [&](int i, const float* x, float* y, const float* fg, const float* fb) -> int {
-      if (chain256) {
-        Chain2Args ca{};
-        ca.x = x; ca.res = x; ca.y = y; ca.ln_g = w.ff_ln_g[i]; ca.ln_b = w.ff_ln_b[i];
-        ca.w1p = cr[2 * i]; ca.b1 = w.ff_b1[i]; ca.w2p = cr[2 * i + 1]; ca.b2 = w.ff_b2[i];
-        ca.fln_g = fg; ca.fln_b = fb; ca.scale = fc; ca.eps = kLnEps; ca.M = M;
-        PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain256_bf16(0, ca, s), "ff module");
-        return 0;
-      }
-      Gemm16Args a1 = g16(x, d, d, w.ff_w1p[i], w.ff_b1[i], 4 * d / 16, sc.h4, 4 * d);
-      a1.ln_g = w.ff_ln_g[i]; a1.ln_b = w.ff_ln_b[i];
-      { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_gemm16(m, E16_SWISH, true, a1, w.ff_w1p[i], s), "ffn1"); }
-      Gemm16Args a2 = g16(sc.h4, 4 * d, 4 * d, w.ff_w2p[i], w.ff_b2[i], d / 16, y, d);
-      a2.res = x; a2.scale = fc; a2.fln_g = fg; a2.fln_b = fb;
-      { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_gemm16(m, E16_RES, false, a2, w.ff_w2p[i], s), "ffn2"); }
-      return 0;
-    };
-    int rc = ffn(0, sc.xa, sc.xb, nullptr, nullptr);
-    if (rc) return rc;
-    AttnArgs at{};
-    at.ctx = sc.ctx; at.B = B; at.Tq = T; at.H = H; at.D = d;
-    at.win_front = bo.win_front; at.win_back = bo.win_back;
-    if (cross) {
-      // RBlock: q = (LN(xb + PE) Wq) / sqrt(hs) ; [k | v] = enc [Wk | Wv]
-      AddPeArgs pa{sc.xb, cross->pe, sc.u, B, T, d};
-      { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_add_pe(pa, s), "positional encoding"); }
-      Gemm16Args q = g16(sc.u, d, d, w.xq_wp, w.qkv_b, d / 16, sc.qkv, d);
-      q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-      { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm16(m, E16_QKV, true, q, w.xq_wp, s), "cross-attention query projection"); }
-      Gemm16Args kv = g16(cross->enc, d, d, w.xkv_wp, w.qkv_b, 2 * d / 16, cross->kv, 2 * d);
-      kv.M = B * cross->T_enc;
-      { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm16(m, E16_BIAS, false, kv, w.xkv_wp, s), "cross-attention key/value projection"); }
-      at.q = sc.qkv; at.ldq = d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc;
-    } else {
-      Gemm16Args q = g16(sc.xb, d, d, w.qkv_wp, w.qkv_b, 3 * d / 16, sc.qkv, 3 * d);
-      q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-      { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm16(m, E16_QKV, true, q, w.qkv_wp, s), "qkv"); }
-      at.q = sc.qkv; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
-      at.h2_sq = w.att_h2[0]; at.h2_sk = w.att_h2[1]; at.h2_sv = w.att_h2[2];      // q / k / v are the block's own projections (0: no bound known)
-    }
-    if (bo.t_len) {
-      at.k_len = cross ? cross->k_len : bo.t_len;
-      if (!at.k_len || !attention_applies_lengths(hs, at))
-        return fail(MI355ASR_EINVAL, "ragged batches: no length-aware attention kernel for Tq = %d, Tk = %d", at.Tq, at.Tk);
-    }
-    { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
-    Gemm16Args op = g16(sc.ctx, d, d, w.out_wp, w.out_b, d / 16, sc.xa, d);
-    op.res = sc.xb;
-    { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm16(m, E16_RES, false, op, w.out_wp, s), "attention out"); }
-    Gemm16Args gl = g16(sc.xa, d, d, w.pw1_wp, w.pw1_b, 2 * d / 16, sc.u, d);
-    gl.ln_g = w.cv_ln_g; gl.ln_b = w.cv_ln_b; gl.n_valid = d;
-    { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm16(m, E16_GLU, true, gl, w.pw1_wp, s), "pw_conv_1 + GLU"); }
-    DwArgs dwa{};
-    dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-    dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
-    dwa.t_len = bo.t_len;
-    { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
-    if (chain256) {
-      Chain2Args ca{};
-      ca.x = sc.dw; ca.res = sc.xa; ca.y = sc.xb; ca.w1p = cr[4]; ca.b1 = w.pc_b1; ca.aff_s = w.bn_s; ca.aff_t = w.bn_t;
-      ca.w2p = cr[5]; ca.b2 = w.pw2_b; ca.scale = 1.0f; ca.eps = kLnEps; ca.M = M;
-      { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain256_bf16(1, ca, s), "conv module tail"); }
-      return ffn(1, sc.xb, out ? out : sc.xa, w.ln_g, w.ln_b);
-    }
-    Gemm16Args pc = g16(sc.dw, d, d, w.pc_w1p, w.pc_b1, 2 * d / 16, sc.h4, 2 * d);
-    pc.aff_s = w.bn_s; pc.aff_t = w.bn_t;
-    { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_gemm16(m, E16_AFFSWISH, false, pc, w.pc_w1p, s), "pointwise + BN + swish"); }
-    Gemm16Args p2 = g16(sc.h4, 2 * d, 2 * d, w.pw2_wp, w.pw2_b, d / 16, sc.xb, d);
-    p2.res = sc.xa;
-    { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_gemm16(m, E16_RES, false, p2, w.pw2_wp, s), "pw_conv_2"); }
-    return ffn(1, sc.xb, out ? out : sc.xa, w.ln_g, w.ln_b);
-  }
-  // round 6: the Translator's RBlock takes the fused kernels too -- its query projection (of LayerNorm(x1 + PE)) rides in the
-  // ff_module_1 launch of the pair-pipelined kernel, keys / values come from the encoder output through their own projection
-  const bool fused_cross = cross && ff1_qkv_pp_selected(w.ff1_slabs != nullptr, w.pp_ff1 != nullptr) && !bo.pre_pp && !skip_ff1 && !next;
-  if (bo.t_len && cross && (!fused_cross || !cross->k_len))
-    return fail(MI355ASR_EINVAL, "ragged batches: the Translator's cross-attention block needs the fused kernels and encoder lengths");
-  if (d == 144 && fused_env && (!cross || fused_cross)) {
-    // token-local runs of layers in one launch each (fused.hip); attention and the depthwise conv mix tokens
-    const float qscale = 1.0f / std::sqrt((float)hs);
-    // round 5: q / k / v of a block travel head-major ([B, H, T, 36] planes) whenever their producer is a pair-pipelined kernel and
-    // their consumer the two-term attention_split_kernel -- a pure function of the shapes, the switches and the block's weights, so
-    // the producer (this block's own ff_module_1 launch, or the previous block's tail) and the consumer agree without a flag
-    // being passed between launches.  MI355ASR_QKV_HEAD_MAJOR=0: token-major rows as before.
-    auto attn_args = [&](const BlockDev& bw, bool hm) {
-      AttnArgs at{};
-      at.q = sc.qkv; at.k = sc.qkv + (hm ? (size_t)M * d : (size_t)d); at.v = sc.qkv + (hm ? 2 * (size_t)M * d : 2 * (size_t)d); at.ctx = sc.ctx;
-      at.B = B; at.Tq = T; at.Tk = T; at.H = H; at.D = d; at.ldq = hm ? hs : 3 * d; at.ldk = hm ? hs : 3 * d;
-      at.win_front = bo.win_front; at.win_back = bo.win_back;
-      at.h2_sq = bw.att_h2[0]; at.h2_sk = bw.att_h2[1]; at.h2_sv = bw.att_h2[2];      // q / k / v are the block's own projections
-      at.head_major = hm ? 1 : 0;
-      at.k_len = bo.t_len;
-      return at;
-    };
-    auto qkv_head_major = [&](const BlockDev& bw) {
-      static const bool on = mi355_env("MI355ASR_QKV_HEAD_MAJOR", 1) != 0;
-      return on && !cross && ff1_qkv_pp_selected(bw.ff1_slabs != nullptr, bw.pp_ff1 != nullptr) && attention_takes_head_major(hs, attn_args(bw, true));
-    };
-    auto ff1_args = [&](const BlockDev& bw, const float* x0, float* x1) {
-      Ff1QkvArgs k1{};
-      k1.x0 = x0; k1.x1 = x1; k1.qkv = sc.qkv;
-      k1.ff_ln_g = bw.ff_ln_g[0]; k1.ff_ln_b = bw.ff_ln_b[0]; k1.ff_w1p = bw.ff_w1p[0]; k1.ff_b1 = bw.ff_b1[0];
-      k1.ff_w2p = bw.ff_w2p[0]; k1.ff_b2 = bw.ff_b2[0];
-      k1.att_ln_g = bw.att_ln_g; k1.att_ln_b = bw.att_ln_b; k1.qkv_wp = bw.qkv_wp; k1.qkv_b = bw.qkv_b;
-      k1.fc = fc; k1.qscale = qscale; k1.eps = kLnEps; k1.M = M; k1.slabs = bw.ff1_slabs; k1.pp_slabs = bw.pp_ff1; k1.pp_sc = bw.pp_ff1_sc; k1.pp_sw_qkv = bw.pp_sw_qkv;
-      k1.ns_w1 = bw.ns_ff1_w1; k1.ns_w2 = bw.ns_ff1_w2; k1.ns_qkv = bw.ns_qkv;
-      if (qkv_head_major(bw)) { k1.qkv_T = T; k1.qkv_H = H; }
-      return k1;
-    };
-    if (!skip_ff1) {
-      Ff1QkvArgs k1 = ff1_args(w, sc.xa, sc.xb);
-      if (bo.pre_pp) { k1.pre_x = bo.pre_x; k1.pre_pp = bo.pre_pp; k1.pre_sw = bo.pre_sw; k1.pre_chunks = bo.pre_chunks; }
-      if (cross) { k1.xq_pe = cross->pe; k1.xq_U = T; }
-      PROF(MI355ASR_K_FF1_QKV); LAUNCH_TRY(launch_ff1_qkv(k1, s), "ff_module_1 + qkv");
-    }
-    AttnArgs at = attn_args(w, qkv_head_major(w));
-    if (cross) {
-      // [k | v] = enc [Wk | Wv]  [B * T_enc, 2 d]; q sits at columns 0..143 of the [M, 3 d] rows the ff_module_1 launch wrote
-      GemmArgs kv{};
-      kv.x = cross->enc; kv.y = cross->kv; kv.wp = w.xkv_wp; kv.bias = w.qkv_b;   // qkv_b: 3d zeros (no bias)
-      kv.M = B * cross->T_enc; kv.NT = 2 * d / 16; kv.ldy = 2 * d; kv.n_valid = 2 * d; kv.eps = kLnEps;
-      { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, kv, s), "cross-attention key/value projection"); }
-      at.q = sc.qkv; at.ldq = 3 * d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc; at.head_major = 0;
-      at.h2_sq = 0.f; at.h2_sk = 0.f; at.h2_sv = 0.f;          // no operand bounds for the encoder's rows: three exact terms
-      at.k_len = bo.t_len ? cross->k_len : nullptr;             // ragged batches: the keys are the utterance's encoder frames
-    }
-    OutGluArgs k2{};
-    k2.ctx = sc.ctx; k2.x1 = sc.xb; k2.x2 = sc.xa; k2.u = sc.u;
-    k2.out_wp = w.out_wp; k2.out_b = w.out_b; k2.cv_ln_g = w.cv_ln_g; k2.cv_ln_b = w.cv_ln_b;
-    k2.pw1_wp = w.pw1_wp; k2.pw1_b = w.pw1_b; k2.eps = kLnEps; k2.M = M;
-    k2.og_slabs = w.og_slabs; k2.pp_slabs = w.pp_og; k2.pp_sw_out = w.pp_sw_out; k2.pp_sw_pw1 = w.pp_sw_pw1;
-    k2.ns_out = w.ns_out; k2.ns_pw1 = w.ns_pw1;
-    DwArgs dwa{};
-    dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-    dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
-    dwa.t_len = bo.t_len;
-    // ragged batches: the attention launch, when there is one, must be a kernel that applies key lengths
-    if (bo.t_len && !attention_applies_lengths(hs, at))
-      return fail(MI355ASR_EINVAL, "ragged batches: no length-aware attention kernel for T = %d (needs T > 16 and the split kernels: "
-                  "MI355ASR_ATTN_SPLIT / MI355ASR_ATTN_LDS on)", T);
-    // round 3: the depthwise conv rides in the prologue of the pair-pipelined tail kernel (no launch, dw never in HBM)
-    const bool dw_fold = w.pp_tail && w.tail_slabs && tail_pp_selected() && pp_dw_fold_ok(T, ksz);
-    TailFf2Args k4{};
-    if (dw_fold) { k4.dw_u = sc.u; k4.dw_wd = w.dw_w; k4.dw_T = T; k4.dw_pad = dwa.pad_left; }
-    k4.dw_len = bo.t_len;
-    k4.M = M; k4.pp_slabs = w.pp_tail;
-    // round 4: so does out-projection + GLU (x2 and u never in HBM either): the block is attention + one launch
-    const bool og_fold = dw_fold && pp_og_fold_ok(k4, k2);
-    k4.dw = sc.dw; k4.x2 = sc.xa; k4.y = out ? out : sc.xb;
-    k4.pc_w1p = w.pc_w1p; k4.pc_b1 = w.pc_b1; k4.bn_s = w.bn_s; k4.bn_t = w.bn_t; k4.pw2_wp = w.pw2_wp; k4.pw2_b = w.pw2_b;
-    k4.ff_ln_g = w.ff_ln_g[1]; k4.ff_ln_b = w.ff_ln_b[1]; k4.ff_w1p = w.ff_w1p[1]; k4.ff_b1 = w.ff_b1[1];
-    k4.ff_w2p = w.ff_w2p[1]; k4.ff_b2 = w.ff_b2[1]; k4.ln_g = w.ln_g; k4.ln_b = w.ln_b;
-    k4.fc = fc; k4.eps = kLnEps; k4.M = M; k4.slabs = w.tail_slabs; k4.pp_slabs = w.pp_tail; k4.pp_sc[0] = w.pp_tail_sc[0]; k4.pp_sc[1] = w.pp_tail_sc[1];
-    k4.ns_cv_w1 = w.ns_cv_w1; k4.ns_cv_w2 = w.ns_cv_w2; k4.ns_ff_w1 = w.ns_ff2_w1; k4.ns_ff_w2 = w.ns_ff2_w2;
-    // The folded launches (OGF) read x1 from sc.xb, INCLUDING the halo frames of the neighbouring workgroups (the window of
-    // the depthwise conv), so nothing in such a launch may write sc.xb: a workgroup that starts after its neighbour has
-    // stored the block output there would read y as x1 (grids above one workgroup per CU).  x2 is never materialised in
-    // that mode, so sc.xa is free: the block output goes there and the xa/xb swap is skipped.
-    TailFf2Args k4og = k4;
-    if (!out) k4og.y = sc.xa;
-    const bool tail_ff1_case = next && !out && ff1_done && tail_ff1_available() && k4.slabs && next->ff1_slabs;
-    // round 6, small batches (up to MI355ASR_NS1_MAX_M rows): one 16-token tile per workgroup (fused_ns.hip).  The block runs as
-    // [attention + out-projection + GLU] -> [depthwise conv + tail (+ the next block's ff_module_1 + qkv)]: two launches, the first
-    // of which takes the attention along when it can (at most 256 frames, operand bounds known).  Same buffer roles as the folded
-    // pair-pipelined launches below: x2 / u go to sc.xa / sc.u, which are free in that mode; every workgroup reads and writes its
-    // own rows of sc.xa only.
-    // (its own shape rule: 16-frame tiles waste little at any length, so the 64-frame criterion of the folds below does not apply)
-    if (w.pp_tail && w.tail_slabs && tail_pp_selected() && pp_enabled() && ksz == 32 && ns1_rows_ok(M)) {
-      const bool head_fold_case = og_fold && !tail_ff1_case && bo.head && bo.head_pp && bo.head_done && pp_head_fold_ok(M, bo.head->n_valid, bo.head_groups);
-      TailFf2Args kt = tail_ff1_case ? k4 : k4og;
-      kt.dw_u = sc.u; kt.dw_wd = w.dw_w; kt.dw_T = T; kt.dw_pad = dwa.pad_left;
-      if (tail_ff1_case) kt.y = nullptr;
-      const Ff1QkvArgs kn = tail_ff1_case ? ff1_args(*next, nullptr, sc.xa) : Ff1QkvArgs{};
-      if (!head_fold_case && ns1_block_ok(kt, tail_ff1_case ? &kn : nullptr, k2)) {
-        OutGluArgs kg = k2;
-        const bool fuse_attn = ns1_attn_ok(hs, at);
-        if (fuse_attn) {
-          kg.attn = 1; kg.aq = at.q; kg.ak = at.k; kg.av = at.v; kg.a_T = at.Tk; kg.a_H = at.H; kg.a_ldq = at.ldq; kg.a_ldk = at.ldk;
-          kg.a_head_major = at.head_major; kg.a_sq = at.h2_sq; kg.a_sk = at.h2_sk; kg.a_sv = at.h2_sv; kg.a_klen = at.k_len;
-        } else {
-          PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention");
-        }
-        if (tail_ff1_case) {
-          PROF(MI355ASR_K_TAIL_FF1);
-          LAUNCH_TRY(launch_ns1_og_tail(kt, &kn, kg, s), "small-batch block + next ff_module_1");
-          *ff1_done = true;
-          std::swap(sc.xa, sc.xb);
-        } else {
-          PROF(MI355ASR_K_TAIL_FF2);
-          LAUNCH_TRY(launch_ns1_og_tail(kt, nullptr, kg, s), "small-batch block");      // y is in sc.xa (or `out`): no swap
-        }
-        return 0;
-      }
-    }
-    { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
-    if (!og_fold) { PROF(MI355ASR_K_OUT_GLU); LAUNCH_TRY(launch_out_glu(k2, s), "out-projection + GLU"); }
-    if (!dw_fold) { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
-    // out-projection + GLU as its own launch, once, when a folded launcher declines (it declines before launching anything)
-    bool og_pending = og_fold;
-    auto unfold = [&]() -> int {
-      if (!og_pending) return 0;
-      og_pending = false;
-      PROF(MI355ASR_K_OUT_GLU); LAUNCH_TRY(launch_out_glu(k2, s), "out-projection + GLU");
-      return 0;
-    };
-    if (tail_ff1_case) {
-      // the block output feeds only the next block's ff_module_1: keep it in registers, write x1 (into the buffer the
-      // next block knows as sc.xb after the swap below -- this block's x2, which each workgroup has consumed) and qkv
-      TailFf2Args kf = k4;
-      kf.y = nullptr;
-      const Ff1QkvArgs kn = ff1_args(*next, nullptr, sc.xa);
-      PROF(MI355ASR_K_TAIL_FF1);
-      bool launched = og_fold && launch_pp_og_tail_ff1(kf, kn, k2, s) == 0;
-      if (!launched) {
-        if (int rc = unfold()) return rc;
-        launched = launch_tail_ff1(kf, kn, s) == 0;
-      }
-      if (launched) {
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) return fail(MI355ASR_EHIP, "conv tail + ff_module_2 + next ff_module_1: %s", hipGetErrorString(e_));
-        *ff1_done = true;
-        std::swap(sc.xa, sc.xb);
-        return 0;
-      }
-    }
-    {
-      PROF(MI355ASR_K_TAIL_FF2);
-      // round 4: the class head behind the CTC decoder's last block rides in this launch (the block output itself is then
-      // stored only if somebody asked for it)
-      if (bo.head && bo.head_pp && bo.head_done && og_pending && pp_head_fold_ok(M, bo.head->n_valid, bo.head_groups)) {
-        TailFf2Args kh = k4og;
-        if (!out) kh.y = nullptr;
-        kh.head_pp = bo.head_pp; kh.head_sw = bo.head_sw; kh.head_groups = bo.head_groups; kh.head_ldy = bo.head->ldy;
-        kh.head_nvalid = bo.head->n_valid; kh.head_y = bo.head->y; kh.head_argmax = bo.head->argmax_out; kh.head_maxval = bo.head->maxval_out;
-        if (launch_pp_og_tail_ff2(kh, k2, s) == 0) {
-          if (hipGetLastError() != hipSuccess) return fail(MI355ASR_EHIP, "block tail + class head launch failed");
-          *bo.head_done = true;
-          return 0;                                    // nothing was stored: the block's input stays where it was
-        }
-      }
-      if (og_pending && launch_pp_og_tail_ff2(k4og, k2, s) == 0) {
-        if (hipGetLastError() != hipSuccess) return fail(MI355ASR_EHIP, "out-projection + GLU + conv tail + ff_module_2 launch failed");
-        return 0;                                      // y is in sc.xa (or `out`): no swap
-      }
-      if (int rc = unfold()) return rc;
-      LAUNCH_TRY(launch_tail_ff2(k4, s), "conv tail + ff_module_2");
-    }
-    if (!out) std::swap(sc.xa, sc.xb);
-    return 0;
-  }
-  // ff_module_1: xb = xa + fc * FFN(LN(xa))
-  Chain2Args f1{};
-  f1.x = sc.xa; f1.res = sc.xa; f1.y = sc.xb;
-  f1.ln_g = w.ff_ln_g[0]; f1.ln_b = w.ff_ln_b[0];
-  f1.w1p = w.ff_w1p[0]; f1.b1 = w.ff_b1[0]; f1.w2p = w.ff_w2p[0]; f1.b2 = w.ff_b2[0];
-  f1.scale = fc; f1.eps = kLnEps; f1.M = M;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f1, s), "ff_module_1"); }
-  AttnArgs at{};
-  at.ctx = sc.ctx; at.B = B; at.Tq = T; at.H = H; at.D = d;
-  at.win_front = bo.win_front; at.win_back = bo.win_back;
-  if (cross) {
-    // q = (LN(xb + PE) Wq) / sqrt(hs)  [M, d] ; [k | v] = enc [Wk | Wv]  [B*T_enc, 2d]
-    AddPeArgs pa{sc.xb, cross->pe, sc.u, B, T, d};
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_add_pe(pa, s), "positional encoding"); }
-    GemmArgs q{};
-    q.x = sc.u; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.xq_wp; q.bias = w.qkv_b;
-    q.M = M; q.NT = d / 16; q.ldy = d; q.n_valid = d; q.eps = kLnEps;
-    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "cross-attention query projection"); }
-    GemmArgs kv{};
-    kv.x = cross->enc; kv.y = cross->kv; kv.wp = w.xkv_wp; kv.bias = w.qkv_b;   // qkv_b: 3d zeros (no bias)
-    kv.M = B * cross->T_enc; kv.NT = 2 * d / 16; kv.ldy = 2 * d; kv.n_valid = 2 * d; kv.eps = kLnEps;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, kv, s), "cross-attention key/value projection"); }
-    at.q = sc.qkv; at.ldq = d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc;
-  } else {
-    // mhsa: qkv = LN(xb) Wqkv (q pre-scaled)
-    GemmArgs q{};
-    q.x = sc.xb; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.qkv_wp; q.bias = w.qkv_b;
-    q.M = M; q.NT = 3 * d / 16; q.ldy = 3 * d; q.n_valid = 3 * d; q.eps = kLnEps;
-    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "qkv projection"); }
-    at.q = sc.qkv; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
-  }
-  { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
-  // xa = xb + ctx Wo + bo
-  GemmArgs op{};
-  op.x = sc.ctx; op.y = sc.xa; op.res = sc.xb; op.wp = w.out_wp; op.bias = w.out_b;
-  op.M = M; op.NT = d / 16; op.ldy = d; op.n_valid = d; op.eps = kLnEps;
-  { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, op, s), "attention out-projection"); }
-  // conv module: u = GLU(LN(xa) Wpw1 + b)
-  GemmArgs g{};
-  g.x = sc.xa; g.y = sc.u; g.ln_g = w.cv_ln_g; g.ln_b = w.cv_ln_b; g.wp = w.pw1_wp; g.bias = w.pw1_b;
-  g.M = M; g.NT = 2 * d / 16; g.ldy = d; g.n_valid = d; g.eps = kLnEps;
-  { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, g, s), "pw_conv_1 + GLU"); }
-  DwArgs dwa{};
-  dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-  // Keras 'same', stride 1: total k-1, before = (k-1)//2 ; 'causal': all k-1 on the left
-  dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
-  { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
-  // xb = xa + pw2( swish( BN( dw Wpc + bpc ) ) ) + b2
-  Chain2Args cv{};
-  cv.x = sc.dw; cv.res = sc.xa; cv.y = sc.xb;
-  cv.w1p = w.pc_w1p; cv.b1 = w.pc_b1; cv.aff_s = w.bn_s; cv.aff_t = w.bn_t; cv.w2p = w.pw2_wp; cv.b2 = w.pw2_b;
-  cv.scale = 1.0f; cv.eps = kLnEps; cv.M = M;
-  { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, cv, s), "conv module tail"); }
-  // ff_module_2 + block LayerNorm
-  Chain2Args f2{};
-  f2.x = sc.xb; f2.res = sc.xb; f2.y = out ? out : sc.xa;
-  f2.ln_g = w.ff_ln_g[1]; f2.ln_b = w.ff_ln_b[1];
-  f2.w1p = w.ff_w1p[1]; f2.b1 = w.ff_b1[1]; f2.w2p = w.ff_w2p[1]; f2.b2 = w.ff_b2[1];
-  f2.fln_g = w.ln_g; f2.fln_b = w.ln_b;
-  f2.scale = fc; f2.eps = kLnEps; f2.M = M;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f2, s), "ff_module_2 + LayerNorm"); }
-  return 0;
-}
 
 int run_mel(const mi355asr_model* m, const float* wav, int Bp, int Lb, int F, float* logp, float* pmax,
             float* umax, float* mel, hipStream_t s, const int32_t* wav_len = nullptr) {
@@ -1525,7 +1134,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
       LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "ctc project");
     }
   }
-  // round 4: the class head rides in the last block's tail launch where pp_head_kernel would have run (try_head_ld's conditions)
+  // round 4: the class head rides in the last block's tail launch where pp_head_kernel would have run (run_class_head's conditions)
   GemmArgs hdf{};
   hdf.y = logits; hdf.bias = m->fc_b; hdf.M = M; hdf.NT = m->NT_fc; hdf.ldy = m->cfg.num_classes; hdf.n_valid = m->cfg.num_classes; hdf.eps = kLnEps;
   hdf.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
@@ -1544,26 +1153,11 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     if (rc) return rc;
   }
   if (head_done) return ragged_out();
-  if (bf16) {
-    Gemm16Args hd{};
-    hd.x = sc.xa; hd.ldx = d; hd.bias = m->fc_b; hd.y = logits; hd.ldy = m->cfg.num_classes;
-    hd.M = M; hd.K = d; hd.NT = m->NT_fc; hd.n_valid = m->cfg.num_classes; hd.eps = kLnEps;
-    hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
-    // the hidden buffer of the ff modules (M x 4 d floats, planned whenever gemm16_for(m, M)) is free here: per-range winners of a split head
-    hd.part_max = 8;
-    hd.part_v = sc.h4;
-    hd.part_i = reinterpret_cast<int32_t*>(sc.h4 + (size_t)hd.part_max * M);
-    { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm16(m, E16_HEAD, false, hd, m->fc_wp, s), "ctc head"); }
-    return ragged_out();
-  }
-  GemmArgs hd{};
-  hd.x = sc.xa; hd.y = logits; hd.wp = m->fc_wp; hd.bias = m->fc_b;
-  hd.M = M; hd.NT = m->NT_fc; hd.ldy = m->cfg.num_classes; hd.n_valid = m->cfg.num_classes; hd.eps = kLnEps;
-  hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
-  {
-    PROF(MI355ASR_K_CTC_HEAD);
-    if (try_head_ld(m, hd, s) != 0) LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "ctc head");
-  }
+  GemmArgs hd = hdf;
+  hd.x = sc.xa; hd.wp = m->fc_wp;
+  // (the hidden buffer of the ff modules, M x 4 d floats, planned whenever gemm16_for(m, M), is free here: per-range winners of
+  // a layer-at-a-time head split over class ranges)
+  if (int rc = run_class_head(m, hd, HeadLayers::first, nullptr, sc.h4, hd.argmax_out, s)) return rc;
   return ragged_out();                                 // (the class head is row-wise: only the rows past T_b need their values)
 }
 

@@ -128,11 +128,9 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
     hd.x = sc.xa; hd.y = logits; hd.wp = st.fc_wp; hd.bias = st.fc_b;
     hd.M = M; hd.NT = st.NT_fc; hd.ldy = st.num_classes; hd.n_valid = st.num_classes; hd.eps = kLnEps;
     hd.argmax_out = amax;
-    {
-      PROF(MI355ASR_K_CTC_HEAD);
-      // (the q / k / v buffer is dead behind the last block: the per-range arg-max pairs of a head split over class ranges)
-      if (try_head_ld(m, hd, s, sc.qkv) != 0) LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "fully_connected");
-    }
+    // (the q / k / v and context buffers are dead behind the last block: the per-range arg-max pairs of a head split over class
+    // ranges, and the arg-max nobody asked for)
+    if (int rc = run_class_head(m, hd, HeadLayers::never, sc.qkv, nullptr, reinterpret_cast<int32_t*>(sc.ctx), s)) return rc;
   }
   return 0;
 }

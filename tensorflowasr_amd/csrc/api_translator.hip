@@ -152,24 +152,9 @@ int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids, const flo
   hd.M = M; hd.NT = m->t_stack.NT_fc; hd.ldy = m->tcfg.tar_classes; hd.n_valid = m->tcfg.tar_classes; hd.eps = kLnEps;
   hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
   // round 5: from 2048 rows on the class head runs on the two-term stream of pp_head_kernel (or the slab ring), as the CTC decoder's
-  // and the ChunkConformer's heads do (try_head_ld: 144 -> 9160 over 5952 rows 0.44 ms on the fp32 MFMA kernel)
-  {
-    PROF(MI355ASR_K_CTC_HEAD);
-    if (try_head_ld(m, hd, s, (float*)(ws + p.hsplit)) == 0) {
-      if (hipGetLastError() != hipSuccess) return fail(MI355ASR_EHIP, "translator head launch failed");
-      return 0;
-    }
-  }
-  if (gemm16_for(m, M)) {
-    Gemm16Args h16{};
-    h16.x = sc.xa; h16.ldx = d; h16.bias = hd.bias; h16.y = logits; h16.ldy = hd.ldy; h16.M = M; h16.K = d; h16.NT = hd.NT;
-    h16.n_valid = hd.n_valid; h16.eps = kLnEps; h16.argmax_out = hd.argmax_out;
-    h16.part_max = 8; h16.part_v = (float*)(ws + p.hsplit); h16.part_i = reinterpret_cast<int32_t*>(h16.part_v + (size_t)8 * M);
-    { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm16(m, E16_HEAD, false, h16, m->t_stack.fc_wp, s), "translator head"); }
-    return 0;
-  }
-  { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "translator head"); }
-  return 0;
+  // and the ChunkConformer's heads do (144 -> 9160 over 5952 rows: 0.44 ms on the fp32 MFMA kernel)
+  float* hsplit = (float*)(ws + p.hsplit);
+  return run_class_head(m, hd, HeadLayers::after_streams, hsplit, hsplit, hd.argmax_out, s);
 }
 
 // ragged batches: token lengths tok_len [B] (rows of ids) and encoder lengths enc_len [B] (frames of enc), both on the device
@@ -207,20 +192,8 @@ int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, co
   hd.x = sc.xa; hd.y = logits; hd.wp = m->t_stack.fc_wp; hd.bias = m->t_stack.fc_b;
   hd.M = M; hd.NT = m->t_stack.NT_fc; hd.ldy = m->tcfg.tar_classes; hd.n_valid = m->tcfg.tar_classes; hd.eps = kLnEps;
   hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
-  {
-    PROF(MI355ASR_K_CTC_HEAD);
-    if (try_head_ld(m, hd, s, (float*)(ws + p.hsplit)) == 0) {
-      if (hipGetLastError() != hipSuccess) return fail(MI355ASR_EHIP, "translator head launch failed");
-    } else if (gemm16_for(m, M)) {             // few rows: the layer-at-a-time head, as mi355asr_translator_forward takes it
-      Gemm16Args h16{};
-      h16.x = sc.xa; h16.ldx = d; h16.bias = hd.bias; h16.y = logits; h16.ldy = hd.ldy; h16.M = M; h16.K = d; h16.NT = hd.NT;
-      h16.n_valid = hd.n_valid; h16.eps = kLnEps; h16.argmax_out = hd.argmax_out;
-      h16.part_max = 8; h16.part_v = (float*)(ws + p.hsplit); h16.part_i = reinterpret_cast<int32_t*>(h16.part_v + (size_t)8 * M);
-      LAUNCH_TRY(launch_gemm16(m, E16_HEAD, false, h16, m->t_stack.fc_wp, s), "translator head");
-    } else {
-      LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "translator head");
-    }
-  }
+  float* hsplit = (float*)(ws + p.hsplit);
+  if ((rc = run_class_head(m, hd, HeadLayers::after_streams, hsplit, hsplit, hd.argmax_out, s))) return rc;
   const int V = m->tcfg.tar_classes;
   LAUNCH_TRY(launch_ragged_rows(tok_len, B, U, logits, V, V, hd.argmax_out, s), "ragged Translator rows");
   return 0;

@@ -476,28 +476,19 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
 
 }  // namespace
 
-static bool attn_long_on() {
-  // MI355ASR_ATTN_LONG=0: more than 256 keys on the fp32-MFMA kernels (attention_lds_kernel / attention_kernel) as before round 6
-  static const bool on = mi355_env("MI355ASR_ATTN_LONG", 1) != 0;
-  return on;
-}
+// the split kernels take this shape (more than ATTN_SPLIT_SHORT_KEYS keys: attention_split_long_kernel, key blocks with an
+// online softmax); block_path.hip: choose_attention decides whether they run and on how many terms
 bool attention_split_applicable(int hs, const AttnArgs& a) {
-  return hs == HS && a.win_front < 0 && (a.Tk <= TPK || attn_long_on()) && a.Tk > 16 && a.Tq > 16 && a.ldk % 4 == 0 && a.ldq % 4 == 0;
+  static_assert(TPK == ATTN_SPLIT_SHORT_KEYS, "launch.h names the key count of the one-block kernel");
+  return hs == HS && a.win_front < 0 && a.Tk > 16 && a.Tq > 16 && a.ldk % 4 == 0 && a.ldq % 4 == 0;
 }
+// ... and its two-term fp16 form can: the operand bounds are known (not in a timing-only build)
+bool attention_split_two_term_fits(const AttnArgs& a) { return a.h2_sq > 0.f && a.h2_sk > 0.f && a.h2_sv > 0.f && ADG == 0; }
 
-static bool attn_three_env() {
-  // MI355ASR_ATTN_TERMS=3: the three-term bf16 kernel also where the operand bounds are known
-  static const bool three = mi355_env("MI355ASR_ATTN_TERMS", -1) == 3;
-  return three;
-}
-bool attention_split_two_term(int hs, const AttnArgs& a) {
-  return attention_split_applicable(hs, a) && a.h2_sq > 0.f && a.h2_sk > 0.f && a.h2_sv > 0.f && !attn_three_env() && ADG == 0;
-}
-
-int launch_attention_split(int hs, const AttnArgs& a, hipStream_t s) {
-  if (!attention_split_applicable(hs, a)) return -1;
+int launch_attention_split(int hs, const AttnArgs& a, int terms, hipStream_t s) {
+  if (!attention_split_applicable(hs, a) || (terms != 2 && terms != 3) || (terms == 2 && !attention_split_two_term_fits(a))) return -1;
   const int qtiles = (a.Tq + 15) / 16;
-  const bool two = attention_split_two_term(hs, a);
+  const bool two = terms == 2;
   if (a.head_major && (!two || a.ldq != HS || a.ldk != HS)) return -1;       // head-major operands: this kernel's two-term form only
   note_scheme(two ? SCHEME_F16X2 : SCHEME_BF16X3);
   const dim3 grid((qtiles + AW - 1) / AW, a.H, a.B);

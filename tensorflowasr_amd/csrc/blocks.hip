@@ -376,6 +376,7 @@ static void launch_gemm_rows_t(const GemmArgs& a, int ychunks, hipStream_t s) {
 }
 
 int launch_gemm_rows(int D, int epi, bool ln, const GemmArgs& a, hipStream_t s) {
+  if (epi == EPI_HEAD && !a.argmax_out) return -1;     // the head kernel stores the arg-max unconditionally
   // column-chunk width CT per (D, epilogue); the packed weight's NT is padded to a multiple of it on the host
   // (gemm_ct() below is the single source of truth for that padding).
   const int ct = gemm_ct(D, epi);
@@ -637,32 +638,17 @@ static void launch_attention_t(const AttnArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((attention_kernel<HS, 16>), grid, dim3(BLOCK_THREADS), 0, s, a);
 }
 
-// would launch_attention hand this launch to the two-term attention_split_kernel (the one kernel that reads head-major operands)?
-bool attention_takes_head_major(int HS, const AttnArgs& a) {
-  static const bool lds_env = mi355_env("MI355ASR_ATTN_LDS", 1) != 0;
-  static const bool split_env = mi355_env("MI355ASR_ATTN_SPLIT", 1) != 0;
-  return lds_env && split_env && attention_split_two_term(HS, a);
-}
-
-bool attention_applies_lengths(int HS, const AttnArgs& a) {
-  static const bool lds_env = mi355_env("MI355ASR_ATTN_LDS", 1) != 0;
-  static const bool split_env = mi355_env("MI355ASR_ATTN_SPLIT", 1) != 0;
-  return lds_env && split_env && attention_split_applicable(HS, a);
-}
 int launch_attention(int HS, const AttnArgs& a, hipStream_t s) {
-  // short full-attention utterances (offline ConformerCTC): K / V^T staged in LDS (attention_lds.hip)
-  // MI355ASR_ATTN_SPLIT=0: the fp32-MFMA LDS kernel of round 1 instead of the split-bf16 one (attention_split.hip);
-  // MI355ASR_ATTN_LDS=0: neither (online-softmax kernel with K / V from L2)
-  static const bool lds_env = mi355_env("MI355ASR_ATTN_LDS", 1) != 0;
-  static const bool split_env = mi355_env("MI355ASR_ATTN_SPLIT", 1) != 0;
-  if (lds_env && split_env && attention_split_applicable(HS, a))
-    return launch_attention_split(HS, a, s);
-  if (a.k_len) return -1;              // ragged batches: the split kernels are the ones that apply key lengths
-  if (lds_env && split_env && attention_split64_applicable(HS, a))      // round 5: head size 64, operand bounds known, <= 288 keys
-    return launch_attention_split64(HS, a, s);
-  if (a.head_major) return -1;         // head-major q / k / v (round 5) are read by attention_split_kernel only
+  const AttnChoice c = choose_attention(HS, a);       // block_path.hip
+  switch (c.kernel) {
+    case ATTN_SPLIT:
+    case ATTN_SPLIT_LONG: return launch_attention_split(HS, a, c.terms, s);
+    case ATTN_SPLIT64: return launch_attention_split64(HS, a, s);
+    case ATTN_LDS: note_scheme(SCHEME_F32); return launch_attention_lds(HS, a, s);
+    case ATTN_ONLINE: break;
+    default: return -1;
+  }
   note_scheme(SCHEME_F32);
-  if (lds_env && attention_lds_applicable(HS, a)) return launch_attention_lds(HS, a, s);
   if (HS == 36) launch_attention_t<36>(a, s);
   else if (HS == 64) launch_attention_t<64>(a, s);
   else {

@@ -826,14 +826,10 @@ __global__ __launch_bounds__(NW * 64) void ns1_head_kernel(GemmArgs a, const u32
 // ---- small batches: one tile per workgroup ----------------------------------------------------------------------------------------------
 namespace {
 constexpr int NS1_W = 8;       // waves per workgroup (two per SIMD: one wave's fragment loads issue while the other's MFMAs run)
-int ns1_max_rows() {
-  // MI355ASR_NS1_MAX_M=n: the one-tile-per-workgroup kernels up to n rows (0: never).  Default 4096: 256 tiles = one workgroup per CU
-  // (measured at 250 ... 4000 rows: 46 - 50 us per block against 60 - 62; beyond, the workgroups of a launch no longer run at once)
-  static const int n = (int)mi355_env("MI355ASR_NS1_MAX_M", 4096);
-  return n;
-}
 }  // namespace
-bool ns1_rows_ok(int M) { return M > 0 && M <= ns1_max_rows(); }
+// up to MI355ASR_NS1_MAX_M rows (block_path.hip; default 4096: 256 tiles = one workgroup per CU -- measured at 250 ... 4000 rows:
+// 46 - 50 us per block against 60 - 62; beyond, the workgroups of a launch no longer run at once)
+bool ns1_rows_ok(int M) { return M > 0 && M <= block_switches().ns1_max_m; }
 int launch_ns1_ff1_qkv(const Ff1QkvArgs& b, hipStream_t s) {
   if (!ns1_rows_ok(b.M) || !b.ns_w1 || !b.ns_w2 || !b.ns_qkv || b.pre_pp || b.xq_pe) return -1;
   note_scheme(SCHEME_F16X2);
@@ -849,10 +845,8 @@ bool ns1_block_ok(const TailFf2Args& a, const Ff1QkvArgs* b, const OutGluArgs& g
   if (b && (!b->ns_w1 || !b->ns_w2 || !b->ns_qkv || b->pre_pp || b->xq_pe || b->M != a.M)) return false;
   return true;
 }
-bool ns1_attn_ok(int hs, const AttnArgs& at) {
-  // MI355ASR_NS1_ATTN=0: the attention of a small-batch block as its own launch (attention_split_kernel)
-  static const bool on = mi355_env("MI355ASR_NS1_ATTN", 1) != 0;
-  return on && hs == A_HS && at.Tq == at.Tk && at.Tk > 16 && at.Tk <= 256 && at.win_front < 0 && at.H >= 1 && at.H * A_HS == at.D && at.D == D &&
+bool ns1_attn_fits(int hs, const AttnArgs& at) {
+  return hs == A_HS && at.Tq == at.Tk && at.Tk > 16 && at.Tk <= 256 && at.win_front < 0 && at.H >= 1 && at.H * A_HS == at.D && at.D == D &&
          at.h2_sq > 0.f && at.h2_sk > 0.f && at.h2_sv > 0.f && at.ldq % 4 == 0 && at.ldk % 4 == 0 && at.q_off == 0;
 }
 int launch_ns1_og_tail(const TailFf2Args& a, const Ff1QkvArgs* b, const OutGluArgs& g, hipStream_t s) {

@@ -1105,25 +1105,13 @@ __global__ __launch_bounds__(LD_THREADS) void pp_sublinear_kernel(StreamGemmArgs
 
 }  // namespace
 
-// the depthwise conv rides in the tail kernel's prologue when the caller asked for it (dw_u) and the per-utterance tiling wastes
-// little: ceil(T / 64) chunks of 64 frames per utterance (T = 250: 2.4 % idle rows; T = 100 would idle 22 %)
-bool pp_dw_fold_ok(int T, int ksz) {
-  // MI355ASR_PP_DW=0: depthwise conv as its own launch (dwconv_tile_kernel)
-  static const bool on = mi355_env("MI355ASR_PP_DW", 1) != 0;
-  return on && pp_enabled() && ksz == DW_K && T >= 64 && 64 * ((T + 63) / 64) * 10 <= 11 * T;
-}
-bool pp_enabled();
+// The launchers take the kernel the caller chose (block_path.hip) and check only shapes; -1: nothing launched.
+// The depthwise conv can ride in the tail kernel's prologue when the per-utterance tiling wastes little: ceil(T / 64) chunks of
+// 64 frames per utterance (T = 250: 2.4 % idle rows; T = 100 would idle 22 %)
+bool pp_dw_fold_fits(int T, int ksz) { return ksz == DW_K && T >= 64 && 64 * ((T + 63) / 64) * 10 <= 11 * T; }
 static bool pp_dw_fold(const TailFf2Args& a) { return a.dw_u && a.dw_wd && a.dw_T > 0 && a.M % a.dw_T == 0; }
-bool pp_enabled() {
-  // MI355ASR_PP=0: the round-2 chunk-wise ring kernels (fused.hip) instead of the pair-pipelined ones
-  static const bool on = mi355_env("MI355ASR_PP", 1) != 0;
-  return on;
-}
 int launch_pp_head(const GemmArgs& a, const float* pp, float pp_sw, int groups, hipStream_t s) {
-  // MI355ASR_PP_HEAD=0: the three-term head_ld_kernel (fused.hip)
-  static const bool on = mi355_env("MI355ASR_PP_HEAD", 1) != 0;
-  static const bool ring_on = mi355_env("MI355ASR_HEAD_RING", 1) != 0;
-  if (!on || !ring_on || !pp_enabled() || !pp || groups < 1 || a.n_valid > 144 * groups || a.M <= 0) return -1;
+  if (!pp || groups < 1 || a.n_valid > 144 * groups || a.M <= 0) return -1;
   const int tiles = (a.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
   hipLaunchKernelGGL(pp_head_kernel, dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, a, reinterpret_cast<const u32x4_t*>(pp), pp_sw, groups, groups,
@@ -1154,9 +1142,7 @@ int pp_head_ranges(int M, int groups) {
 int launch_pp_head_split(const GemmArgs& a, const float* pp, float pp_sw, int groups, int ranges, float* scratch, hipStream_t s) {
   const bool wants = a.argmax_out != nullptr || a.maxval_out != nullptr;
   if (ranges <= 1 || (wants && !scratch)) return launch_pp_head(a, pp, pp_sw, groups, s);   // (logits only: the ranges need no combine)
-  static const bool on = mi355_env("MI355ASR_PP_HEAD", 1) != 0;
-  static const bool ring_on = mi355_env("MI355ASR_HEAD_RING", 1) != 0;
-  if (!on || !ring_on || !pp_enabled() || !pp || groups < 1 || a.n_valid > 144 * groups || a.M <= 0) return -1;
+  if (!pp || groups < 1 || a.n_valid > 144 * groups || a.M <= 0) return -1;
   const int gper = (groups + ranges - 1) / ranges, nr = (groups + gper - 1) / gper;
   const int tiles = (a.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
@@ -1174,7 +1160,7 @@ int launch_head_combine(const float* part_v, const int32_t* part_i, int ranges, 
 bool pp_sublinear_ok(const StreamGemmArgs& a, const float* pp) {
   // MI355ASR_PP_SUBLINEAR=0: the three-term sublinear_split_ld_kernel (fused.hip)
   static const bool on = mi355_env("MI355ASR_PP_SUBLINEAR", 1) != 0;
-  return on && pp_enabled() && pp && a.NT == KB && a.K % D == 0 && a.K >= D && a.M > 0 && (a.ldy & 3) == 0;
+  return on && block_switches().pp && pp && a.NT == KB && a.K % D == 0 && a.K >= D && a.M > 0 && (a.ldy & 3) == 0;
 }
 int launch_pp_sublinear(const StreamGemmArgs& a, const float* pp, float pp_sw, hipStream_t s) {
   if (!pp_sublinear_ok(a, pp)) return -1;
@@ -1183,16 +1169,14 @@ int launch_pp_sublinear(const StreamGemmArgs& a, const float* pp, float pp_sw, h
   return 0;
 }
 int launch_pp_out_glu(const OutGluArgs& a, hipStream_t s) {
-  // MI355ASR_PP_OUTGLU=0: the three-term out_glu_ld_kernel (fused.hip)
-  static const bool on = mi355_env("MI355ASR_PP_OUTGLU", 1) != 0;
-  if (!on || !pp_enabled() || !a.pp_slabs || a.M <= 0) return -1;
+  if (!a.pp_slabs || a.M <= 0) return -1;
   const int tiles = (a.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
   hipLaunchKernelGGL(pp_out_glu_kernel, dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, a);
   return 0;
 }
 int launch_pp_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, hipStream_t s) {
-  if (!pp_enabled() || !a.pp_slabs || !b.pp_slabs || a.M != b.M || a.M <= 0) return -1;
+  if (!a.pp_slabs || !b.pp_slabs || a.M != b.M || a.M <= 0) return -1;
   const int tiles = (a.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
 #ifdef MI355ASR_DIAG_KERNELS
@@ -1218,7 +1202,7 @@ int launch_pp_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, hipStream_t s)
   return 0;
 }
 int launch_pp_tail_ff2(const TailFf2Args& a, hipStream_t s) {
-  if (!pp_enabled() || !a.pp_slabs || a.M <= 0) return -1;
+  if (!a.pp_slabs || a.M <= 0) return -1;
   const int tiles = (a.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
   if (pp_dw_fold(a)) {
@@ -1231,53 +1215,37 @@ int launch_pp_tail_ff2(const TailFf2Args& a, hipStream_t s) {
 // out-projection + GLU in the prologue of the tail kernels (OGF): the block runs as attention -> this, two launches.
 // g: what pp_out_glu_kernel would have been given (ctx, x1, the LayerNorm parameters, the out_glu stream and its scales;
 // x2 and u are not written).  Needs the depthwise fold (a.dw_wd / dw_T / dw_pad set; a.dw_u is not read).
-bool pp_og_fold_ok(const TailFf2Args& a, const OutGluArgs& g) {
-  // MI355ASR_PP_OGF=0: out-projection + GLU as its own launch (pp_out_glu_kernel)
-  static const bool on = mi355_env("MI355ASR_PP_OGF", 1) != 0;
-  static const bool og_on = mi355_env("MI355ASR_PP_OUTGLU", 1) != 0;
-  return on && og_on && pp_enabled() && a.pp_slabs && g.pp_slabs && g.ctx && g.x1 && a.dw_wd && a.dw_T > 0 && a.M > 0 && a.M % a.dw_T == 0 &&
-         a.M == g.M && (a.dw_pad == 15 || a.dw_pad == 31) && pp_dw_fold_ok(a.dw_T, DW_K);
+bool pp_og_fold_fits(const TailFf2Args& a, const OutGluArgs& g) {
+  return a.pp_slabs && g.pp_slabs && g.ctx && g.x1 && a.dw_wd && a.dw_T > 0 && a.M > 0 && a.M % a.dw_T == 0 && a.M == g.M &&
+         (a.dw_pad == 15 || a.dw_pad == 31) && pp_dw_fold_fits(a.dw_T, DW_K);
 }
 int launch_pp_og_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, const OutGluArgs& g, hipStream_t s) {
-  if (!pp_og_fold_ok(a, g) || !b.pp_slabs || a.M != b.M) return -1;
+  if (!pp_og_fold_fits(a, g) || !b.pp_slabs || a.M != b.M) return -1;
   note_scheme(SCHEME_F16X2);
   hipLaunchKernelGGL((pp_block_kernel<true, true, 0, true, true>), dim3((a.dw_T + 63) / 64, a.M / a.dw_T), dim3(LD_THREADS), 0, s, a, b, g);
   return 0;
 }
-bool pp_head_fold_ok(int M, int n_valid, int groups) {
-  // MI355ASR_PP_HEADF=0: the class head as its own launch (pp_head_kernel); the switches of that kernel apply here too
-  static const bool on = mi355_env("MI355ASR_PP_HEADF", 1) != 0;
-  static const bool head_on = mi355_env("MI355ASR_PP_HEAD", 1) != 0;
-  static const bool ring_on = mi355_env("MI355ASR_HEAD_RING", 1) != 0;
-  return on && head_on && ring_on && pp_enabled() && groups >= 1 && n_valid <= 144 * groups && M > 0;
-}
+// ... with the class head behind the block when a.head_pp is set (round 4: the CTC decoder's last block)
 int launch_pp_og_tail_ff2(const TailFf2Args& a, const OutGluArgs& g, hipStream_t s) {
-  if (!pp_og_fold_ok(a, g)) return -1;
-  note_scheme(SCHEME_F16X2);
+  if (!pp_og_fold_fits(a, g)) return -1;
   if (a.head_pp) {
-    if (!pp_head_fold_ok(a.M, a.head_nvalid, a.head_groups)) return -1;
+    if (a.head_groups < 1 || a.head_nvalid > 144 * a.head_groups) return -1;
+    note_scheme(SCHEME_F16X2);
     hipLaunchKernelGGL((pp_block_kernel<true, false, 0, true, true, false, true>), dim3((a.dw_T + 63) / 64, a.M / a.dw_T), dim3(LD_THREADS), 0, s, a, Ff1QkvArgs{}, g);
     return 0;
   }
+  note_scheme(SCHEME_F16X2);
   hipLaunchKernelGGL((pp_block_kernel<true, false, 0, true, true>), dim3((a.dw_T + 63) / 64, a.M / a.dw_T), dim3(LD_THREADS), 0, s, a, Ff1QkvArgs{}, g);
   return 0;
 }
-bool pp_pre_fold_ok() {
-  // MI355ASR_PP_PRE=0: the subsampling Dense and the CTC decoder's projection as their own launches
-  static const bool on = mi355_env("MI355ASR_PP_PRE", 1) != 0;
-  return on && pp_enabled();
-}
+// ff_module_1 + qkv; with b.pre_pp set, x0 = the layer in front of the block (Ff1QkvArgs::pre_*)
 int launch_pp_ff1_qkv(const Ff1QkvArgs& b, hipStream_t s) {
-  if (!pp_enabled() || !b.pp_slabs || b.M <= 0) return -1;
+  if (!b.pp_slabs || b.M <= 0) return -1;
   if (b.xq_pe && (b.pre_pp || b.qkv_T > 0 || b.xq_U < 1)) return -1;
+  if (b.pre_pp && (!b.pre_x || b.pre_chunks < 1)) return -1;
   const int tiles = (b.M + 15) / 16;
   note_scheme(SCHEME_F16X2);
-  if (b.pre_pp) {
-    if (!pp_pre_fold_ok() || !b.pre_x || b.pre_chunks < 1) return -1;
-    hipLaunchKernelGGL((pp_block_kernel<false, true, 0, false, false, true>), dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, TailFf2Args{}, b, OutGluArgs{});
-    return 0;
-  }
-  if (launch_ns1_ff1_qkv(b, s) == 0) return 0;           // round 6, small batches: one 16-token tile per workgroup (fused_ns.hip)
-  hipLaunchKernelGGL((pp_block_kernel<false, true>), dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, TailFf2Args{}, b, OutGluArgs{});
+  if (b.pre_pp) hipLaunchKernelGGL((pp_block_kernel<false, true, 0, false, false, true>), dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, TailFf2Args{}, b, OutGluArgs{});
+  else hipLaunchKernelGGL((pp_block_kernel<false, true>), dim3((tiles + 3) / 4), dim3(LD_THREADS), 0, s, TailFf2Args{}, b, OutGluArgs{});
   return 0;
 }

@@ -406,42 +406,56 @@ struct TailFf2Args {
   // W1aug [5][36][2][64] / W2 [18][9][2][64]; packed with pp_sc[0] / pp_sc[1]
   const float *ns_cv_w1 = nullptr, *ns_cv_w2 = nullptr, *ns_ff_w1 = nullptr, *ns_ff_w2 = nullptr;
 };
-int launch_ff1_qkv(const Ff1QkvArgs& a, hipStream_t s);
-int launch_out_glu(const OutGluArgs& a, hipStream_t s);
-int launch_tail_ff2(const TailFf2Args& a, hipStream_t s);
-bool tail_ff1_available();
-bool tail_pp_selected();   // launch_tail_ff1 / launch_tail_ff2 will take the pair-pipelined kernels when the block has their streams
-int launch_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, hipStream_t s);   // -1: not available, nothing launched
-// pair-pipelined versions (fused_pp.hip); -1: switched off (MI355ASR_PP=0) or no pp_slabs, nothing launched
-bool pp_enabled();
+// The kernel-choice switches of the Conformer block, attention and class-head paths, each read once (block_path.hip, which
+// also decides every block's kernels).  The launchers below check only shapes; -1: not applicable, nothing launched.
+struct BlockSwitches {
+  bool fused, gemm16, pp, pp_outglu, pp_head, pp_dw, pp_ogf, pp_pre, pp_headf, tail_ff1, head_ring, qkv_head_major, ns1_attn,
+       attn_split, attn_lds, attn_three, attn64_split, attn_long, chain256;
+  long small_m;
+  int ns1_max_m;
+};
+const BlockSwitches& block_switches();
+// the attention kernel launch_attention takes for a launch (ATTN_NONE: none, it returns -1)
+enum AttnKernel { ATTN_NONE, ATTN_SPLIT, ATTN_SPLIT_LONG, ATTN_SPLIT64, ATTN_LDS, ATTN_ONLINE };
+struct AttnChoice {
+  AttnKernel kernel = ATTN_NONE;
+  int terms = 0;   // ATTN_SPLIT / ATTN_SPLIT_LONG: two fp16 or three bf16 terms per operand
+  bool split() const { return kernel == ATTN_SPLIT || kernel == ATTN_SPLIT_LONG; }
+  bool head_major() const { return split() && terms == 2; }   // the one form that reads head-major q / k / v
+  bool applies_lengths() const { return split(); }              // ... and the kernels that read AttnArgs::k_len
+};
+constexpr int ATTN_SPLIT_SHORT_KEYS = 256;                     // keys of attention_split_kernel; more: attention_split_long_kernel
+AttnChoice choose_attention(int HS, const AttnArgs& a);
+// three-term loader-wave kernels (fused.hip)
+int launch_ff1_qkv_ld(const Ff1QkvArgs& a, hipStream_t s);
+int launch_out_glu_ld(const OutGluArgs& a, hipStream_t s);
+int launch_tail_ff1_ld(const TailFf2Args& a, const Ff1QkvArgs& b, hipStream_t s);
+int launch_tail_ff2_ld(const TailFf2Args& a, hipStream_t s);
+// pair-pipelined two-term fp16 kernels (fused_pp.hip)
 int launch_pp_out_glu(const OutGluArgs& a, hipStream_t s);
 // class head of dmodel 144 on the two-term fp16 stream (pp: append_pp_plain of [W ; b] over `groups` column groups, packed with pp_sw)
 int launch_pp_head(const GemmArgs& a, const float* pp, float pp_sw, int groups, hipStream_t s);
 // ... with the column groups split over `ranges` workgroups per row tile (round 6: few rows, many classes); scratch: 2 * ranges * M words
 int pp_head_ranges(int M, int groups);
 int launch_pp_head_split(const GemmArgs& a, const float* pp, float pp_sw, int groups, int ranges, float* scratch, hipStream_t s);
-bool pp_dw_fold_ok(int T, int ksz);   // the tail kernels can take the depthwise conv (kernel size ksz, T frames per utterance) in their prologue
+bool pp_dw_fold_fits(int T, int ksz);   // the tail kernels can take the depthwise conv (kernel size ksz, T frames per utterance) in their prologue
 int launch_pp_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, hipStream_t s);
 int launch_pp_tail_ff2(const TailFf2Args& a, hipStream_t s);
 int launch_pp_ff1_qkv(const Ff1QkvArgs& b, hipStream_t s);
+// round 4: out-projection + residual + LayerNorm + pw_conv_1 + GLU in the prologue of the pair-pipelined tail kernels (the
+// block = attention + ONE launch), with the class head behind the block when a.head_pp is set
+bool pp_og_fold_fits(const TailFf2Args& a, const OutGluArgs& g);
+int launch_pp_og_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, const OutGluArgs& g, hipStream_t s);
+int launch_pp_og_tail_ff2(const TailFf2Args& a, const OutGluArgs& g, hipStream_t s);
 // N-split kernels (fused_ns.hip, round 6): one 16-token tile per workgroup, for small batches (up to MI355ASR_NS1_MAX_M rows): ff_module_1 + qkv; and what the folded tail
 // launches do, as out-projection + GLU (writes g.x2, g.u) followed by depthwise conv + tail [+ next ff_module_1 + qkv when b is set]
 bool ns1_rows_ok(int M);
-bool ns1_block_ok(const TailFf2Args& a, const Ff1QkvArgs* b, const OutGluArgs& g);      // launch_ns1_og_tail will take this block
-bool ns1_attn_ok(int hs, const AttnArgs& at);                                             // ... with its attention in the first launch
+bool ns1_block_ok(const TailFf2Args& a, const Ff1QkvArgs* b, const OutGluArgs& g);      // launch_ns1_og_tail takes this block
+bool ns1_attn_fits(int hs, const AttnArgs& at);                                           // ... and can take its attention in the first launch
 int launch_ns1_ff1_qkv(const Ff1QkvArgs& b, hipStream_t s);
 int launch_ns1_og_tail(const TailFf2Args& a, const Ff1QkvArgs* b, const OutGluArgs& g, hipStream_t s);
-int launch_ns1_head(const GemmArgs& a, const float* ns, float sw, int groups, hipStream_t s);
-int launch_ns1_sublinear(const StreamGemmArgs& a, const float* ns, float sw, hipStream_t s);   // ns: [W chunk ; b] fragments in plain order [5][9 chunks][2][64]   // ns: [W ; b] fragments in plain order [5][9 groups][2][64]
-bool ff1_qkv_pp_selected(bool has_slabs, bool has_pp);   // fused.hip: q, k, v will come from the pair-pipelined producer (head-major layout possible)
-bool ff1_pre_selected();             // ... and launch_ff1_qkv will take that kernel (fused.hip) when the block has its streams
-bool pp_pre_fold_ok();
-bool pp_head_fold_ok(int M, int n_valid, int groups);   // the class head rides in the last block's tail launch (MI355ASR_PP_HEADF=0: own launch)               // the layer in front of a block rides in its ff_module_1 + qkv launch (MI355ASR_PP_PRE=0: own launch)
-// round 4: out-projection + residual + LayerNorm + pw_conv_1 + GLU in the prologue of the pair-pipelined tail kernels (the
-// block = attention + ONE launch); -1: not applicable (switched off, no streams, depthwise fold impossible), nothing launched
-bool pp_og_fold_ok(const TailFf2Args& a, const OutGluArgs& g);
-int launch_pp_og_tail_ff1(const TailFf2Args& a, const Ff1QkvArgs& b, const OutGluArgs& g, hipStream_t s);
-int launch_pp_og_tail_ff2(const TailFf2Args& a, const OutGluArgs& g, hipStream_t s);
+int launch_ns1_head(const GemmArgs& a, const float* ns, float sw, int groups, hipStream_t s);   // ns: [W ; b] fragments in plain order [5][9 groups][2][64]
+int launch_ns1_sublinear(const StreamGemmArgs& a, const float* ns, float sw, hipStream_t s);   // ns: [W chunk ; b] fragments in plain order [5][9 chunks][2][64]
 int launch_sublinear_split(const StreamGemmArgs& a, const float* ws, hipStream_t s);   // -1: shape not supported
 // the same layer on the two-term fp16 stream (fused_pp.hip; pp = append_pp_plain of K / 144 chunks [W_f ; bias or 0], packed with pp_sw)
 int launch_pp_sublinear(const StreamGemmArgs& a, const float* pp, float pp_sw, hipStream_t s);
@@ -455,17 +469,15 @@ int launch_attention(int HS, const AttnArgs& a, hipStream_t s);
 bool attention_head_size_ok(int HS);      // 36 / 64 (tuned kernels) and 12, 16, 24, 32, 48, 72, 128 (online-softmax kernel only)
 bool attention_lds_applicable(int HS, const AttnArgs& a);
 int launch_attention_lds(int HS, const AttnArgs& a, hipStream_t s);
-bool attention_split_applicable(int HS, const AttnArgs& a);
-bool attention_split_two_term(int HS, const AttnArgs& a);
-bool attention_applies_lengths(int HS, const AttnArgs& a);   // blocks.hip: launch_attention would take a kernel that reads a.k_len
-bool attention_takes_head_major(int HS, const AttnArgs& a);   // blocks.hip: launch_attention's own switches included   // the two-term kernel would take this launch (head-major operands allowed)
-int launch_attention_split(int HS, const AttnArgs& a, hipStream_t s);
+bool attention_split_applicable(int HS, const AttnArgs& a);    // attention_split.hip: head size 36, full attention, > 16 keys
+bool attention_split_two_term_fits(const AttnArgs& a);         // ... on two fp16 terms: the operand bounds are known
+int launch_attention_split(int HS, const AttnArgs& a, int terms, hipStream_t s);
 bool attention_split64_applicable(int HS, const AttnArgs& a);   // attention_split64.hip: head size 64, two fp16 terms, <= 288 keys
 int launch_attention_split64(int HS, const AttnArgs& a, hipStream_t s);
 int launch_dwconv(int K, const DwArgs& a, hipStream_t s);
 int launch_stft(const StftArgs& a, hipStream_t s);
 int launch_utt_max(const UttMaxArgs& a, int B, hipStream_t s);
-int launch_head_ld(const GemmArgs& a, const float* slabs, int groups, hipStream_t s);   // dmodel-144 class head on the slab ring; -1: not taken
+int launch_head_ld(const GemmArgs& a, const float* slabs, int groups, hipStream_t s);   // dmodel-144 class head on the three-term slab stream
 int launch_mel(const MelArgs& a, hipStream_t s);
 int launch_mel_band(const MelArgs& a, hipStream_t s);   // freq2mel as the banded matrix it is (triangular filters): HBM-bound
 int launch_db_norm(const MelArgs& a, hipStream_t s);   // mel_layer_type 'Spectrogram': the dB normalisation without the mel matrix

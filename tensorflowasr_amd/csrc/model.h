@@ -303,7 +303,7 @@ struct StackOff {
   float proj_pp_sw = 1.f;
 };
 
-// ---- shared host functions (defined in api.hip) -----------------------------------------------------------
+// ---- shared host functions (defined in api.hip unless noted) -----------------------------------------------------------
 int fail(int code, const char* fmt, ...);
 void same_pad(int n, int k, int s, int* out, int* before);
 void add_block_expected(std::vector<Expected>& ex, const std::string& p, int d, int H, int hs, int k, bool keras_mha = false);
@@ -326,24 +326,33 @@ bool ring_packs_wanted(const mi355asr_model* m);
 void register_rings(mi355asr_model* m, const ArenaBuilder& ab, const float* base);
 // W[144, V] of a class head as the slab stream of head_ld_kernel (fused.hip), registered against its P16 pack
 void put_head_slabs(ArenaBuilder& ab, size_t p16_off, const std::function<float(int, int)>& f, int d, int V, const float* bias);
-// the head on the slab ring when the handle has a stream for hd.wp (fp32 mode, dmodel 144); -1: not taken
-int try_head_ld(const mi355asr_model* m, const GemmArgs& hd, hipStream_t s, float* split_scratch = nullptr);
 FftOff pack_fft(ArenaBuilder& ab, const std::vector<float>& re, const std::vector<float>& im, int n_dft, int nb);
 BlockOff pack_block(mi355asr_model* m, ArenaBuilder& ab, const std::string& p, int d, int H, int hs, int k, bool keras_mha = false);
 BlockDev resolve(const BlockOff& o, const float* base);
 bool use_gemm16(const mi355asr_model* m);
 bool gemm16_for(const mi355asr_model* m, size_t M);
 int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, const float* wp, hipStream_t s);
+// One ConformerBlock (conformer_blocks.py:259-265), block_path.hip.  Input in sc.xa; output to `out`, or (out == nullptr) left in
+// sc.xa -- the fused path ping-pongs xa/xb by swapping the two pointers in `sc` instead of copying.  cross: the Translator's RBlock
+// (conformer_blocks.py:455-463, 496-503), whose attention is a cross-attention with q = LN(x + PE) and k = v = the encoder output.
 // next / ff1_done (dmodel-144 fused path): when `next` is given and the output stays in the scratch buffers, the tail kernel
 // of this block also runs ff_module_1 + qkv of `next` (one launch) and sets *ff1_done, which the caller passes back in as
 // `skip_ff1` for the next block
 int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int B, int T, float* out,
               hipStream_t s, const CrossAttn* cross = nullptr, const BlockDev* next = nullptr, bool* ff1_done = nullptr,
               bool skip_ff1 = false);
-bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);
+bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);   // run_block(w, M rows) can take BlockOpts::pre_*
+// The class head hd (x [M, d] -> logits [M, V], arg-max and / or maximum per row) on the first kernel that takes it: the dmodel-144
+// streams of the handle (fp32 mode), else gemm_rows<EPI_HEAD>.  The layer-at-a-time head (gemm16, when gemm16_for(m, M)) comes
+// first, after the streams, or never.  split: >= 16 M words for a two-term head split over class ranges (null: one range);
+// part: >= 16 M words for a split layer-at-a-time head; amax_scratch: >= M words, the arg-max of the kernels that always store
+// one when hd.argmax_out is null.  (block_path.hip)
+enum class HeadLayers { never, first, after_streams };
+int run_class_head(const mi355asr_model* m, GemmArgs hd, HeadLayers layers, float* split, float* part, int32_t* amax_scratch,
+                   hipStream_t s);
 // ragged batches (api.hip): more than 16 rows per utterance, or EINVAL; the device lengths read back and held to [1, hi]
 int ragged_rows_ok(int T, const char* what);
-int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s);   // run_block(w, M rows) can take BlockOpts::pre_*
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s);
 void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V);   // api_chunk.hip
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip

@@ -2392,11 +2392,11 @@ wav = waves(2, 16000, 11)
 enc = maxdiff(e(wav).cpu().numpy(), co.conformer_encoder(wav.astype(np.float64), w, cfg))
 print("RESULT %.3e %.3e" % (blk, enc))
 '''
-    for extra in ({"MI355ASR_OUTGLU_SPLIT": "0"}, {"MI355ASR_SUBCONV_F32": "1"},
+    for extra in ({"MI355ASR_SUBCONV_F32": "1"},
                   {"MI355ASR_SUBLINEAR_SPLIT": "2"}, {"MI355ASR_SUBLINEAR_SPLIT": "0"},
                   {"MI355ASR_SUBLINEAR_SPLIT": "2", "MI355ASR_PP_SUBLINEAR": "0"}, {"MI355ASR_MEL_BAND": "0"},
-                  {"MI355ASR_FF1QKV_RING": "0"}, {"MI355ASR_HEAD_RING": "0"}, {"MI355ASR_FUSED": "0"},
-                  {"MI355ASR_TAILFF2_RING": "0"}, {"MI355ASR_PP": "0"}, {"MI355ASR_PP": "0", "MI355ASR_TAIL_FF1": "0"},
+                  {"MI355ASR_HEAD_RING": "0"}, {"MI355ASR_FUSED": "0"},
+                  {"MI355ASR_PP": "0"}, {"MI355ASR_PP": "0", "MI355ASR_TAIL_FF1": "0"},
                   {"MI355ASR_TAIL_FF1": "0"}, {"MI355ASR_PP_DW": "0"}, {"MI355ASR_PP_OGF": "0"}, {"MI355ASR_PP_HEAD": "0"},
                   {"MI355ASR_SUBLINEAR_SPLIT": "2", "MI355ASR_PP_PRE": "0"},
                   {"MI355ASR_ATTN_SPLIT": "0"}, {"MI355ASR_ATTN_LDS": "0"}, {"MI355ASR_FFT_SPLIT": "0"}, {"MI355ASR_FFT": "0"},
@@ -2410,6 +2410,96 @@ print("RESULT %.3e %.3e" % (blk, enc))
         assert line, (extra, out.stderr[-2000:])
         blk, enc = (float(v) for v in line[0].split()[1:])
         assert blk < TOL and enc < TOL, (extra, blk, enc)
+
+
+def test_switch_legs_run_the_kernels_they_name_in_a_subprocess(torch_cuda):
+    """The block, attention and class-head switches at 750 rows (3 x 250 frames) and 50 rows (2 x 25), where the
+    one-tile-per-workgroup kernels of fused_ns.hip run by default: the per-category launch counts and operand schemes
+    (mi355asr_profile_read / _schemes) of encoder + CTC decoder show the kernels each switch names."""
+    import subprocess
+    import sys
+    import bench
+    code = r"""
+import sys, json, ctypes
+sys.path.insert(0, "tests")
+from helpers import co, encoder_kwargs, golden_ctc_weights, small_cfg, waves
+from tensorflowasr_amd import _lib
+from tensorflowasr_amd.models import ConformerCTC
+cfg = small_cfg(2)
+w = co.encoder_weights(cfg, seed=3)
+w.update(golden_ctc_weights())
+m = ConformerCTC(1332, **{k: v for k, v in encoder_kwargs(cfg).items() if k != "mel_layer_type"})
+m.load_weights(w, by_name=False)
+lib, nk = _lib.lib(), len(_lib.KERNEL_NAMES)
+res = {}
+for B, L in ((3, 160000), (2, 16000)):
+    _lib.check(lib.mi355asr_profile_enable(m._h.ptr, 1))
+    m.ctc_logits(m.encode(waves(B, L, 11)))
+    ms, cnt, sch = (ctypes.c_double * nk)(), (ctypes.c_int64 * nk)(), (ctypes.c_int32 * nk)()
+    _lib.check(lib.mi355asr_profile_read(m._h.ptr, ms, cnt, nk, 1))
+    _lib.check(lib.mi355asr_profile_schemes(m._h.ptr, sch, nk))
+    res[B * L // 640] = {n: [int(cnt[i]), int(sch[i])] for i, n in enumerate(_lib.KERNEL_NAMES) if cnt[i]}
+print("RESULT " + json.dumps(res))
+"""
+    F32, BF16X3, F16X2 = 0, 1, 2                          # launch.h: OperandScheme
+    block = ("ff1_qkv", "out_glu", "tail_ff2", "tail_ff1", "ctc_head")      # (MI355ASR_PP leaves the attention kernels alone)
+    legs = [
+        (bench.EXACT_ENV, lambda r: all(s != F16X2 for _, s in r.values())),
+        ({"MI355ASR_PP": "0"}, lambda r: all(r[c][1] != F16X2 for c in block if c in r)),
+        ({"MI355ASR_PP_OGF": "0"}, lambda r: r.get("out_glu", [0])[0] > 0),
+        ({"MI355ASR_PP_OUTGLU": "0"}, lambda r: r.get("out_glu", [0, -1])[1] == BF16X3 and r["out_glu"][0] > 0),
+        ({"MI355ASR_PP_DW": "0"}, lambda r: r.get("dwconv", [0])[0] > 0),
+        ({"MI355ASR_NS1_ATTN": "0"}, lambda r: r.get("attention", [0])[0] > 0),
+        ({"MI355ASR_ATTN_SPLIT": "0"}, lambda r: r.get("attention", [0, -1])[1] == F32 and r["attention"][0] > 0),
+        ({"MI355ASR_ATTN_LDS": "0"}, lambda r: r.get("attention", [0, -1])[1] == F32 and r["attention"][0] > 0),
+        ({"MI355ASR_ATTN_TERMS": "3"}, lambda r: r.get("attention", [0, -1])[1] == BF16X3 and r["attention"][0] > 0),
+        ({"MI355ASR_HEAD_RING": "0"}, lambda r: r["ctc_head"][1] == F32),
+        ({"MI355ASR_PP_HEAD": "0"}, lambda r: r["ctc_head"][1] != F16X2),
+        ({}, lambda r: "out_glu" not in r and "dwconv" not in r and "attention" not in r and r["ctc_head"][1] == F16X2),
+    ]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra, ok in legs:
+        env = dict(os.environ, MI355ASR_SMALL_M="0", **extra)
+        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")]
+        assert line, (extra, out.stderr[-2000:])
+        res = json.loads(line[0][len("RESULT "):])
+        for rows in ("750", "50"):
+            assert ok(res[rows]), (extra, rows, res[rows])
+
+
+def test_chunk_predict_without_argmax_on_the_fp32_head_in_a_subprocess(torch_cuda):
+    """ChunkConformer.predict(x) asks for the text logits and no arg-max.  With the one-tile head off (MI355ASR_NS1_MAX_M=0) and
+    fewer than 2048 rows the class head falls back to gemm_rows<EPI_HEAD>, which stores an arg-max: it gets workspace scratch
+    (run_class_head), and the logits equal the default path's."""
+    import subprocess
+    import sys
+    import tempfile
+    code = r"""
+import sys, numpy as np
+sys.path.insert(0, "tests")
+from helpers import chunk_config_dict, co, waves
+from tensorflowasr_amd.models import ChunkConformer
+c5 = dict(co.CHUNK_S, enc_num_blocks=2, picker_num_blocks=1, helper_num_blocks=1, decoder_num_blocks=1)
+w5 = co.chunk_weights(c5, seed=4)
+m = ChunkConformer(chunk_config_dict(c5), c5["picker_num_classes"], c5["decoder_num_classes"])
+m.load_weights(w5, by_name=False)
+out = m.predict(waves(2, 64000, 9))
+out = out[0] if isinstance(out, (tuple, list)) else out
+np.save(sys.argv[1], out.cpu().numpy())
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    with tempfile.TemporaryDirectory() as td:
+        for tag, extra in (("default", {}), ("fp32_head", {"MI355ASR_NS1_MAX_M": "0"})):
+            f = os.path.join(td, tag + ".npy")
+            r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=600, cwd=root)
+            assert r.returncode == 0, (tag, r.stderr[-3000:])
+            res[tag] = np.load(f)
+    a, b = res["default"], res["fp32_head"]
+    assert a.shape == b.shape and a.shape[0] * a.shape[1] < 2048, a.shape
+    assert np.isfinite(b).all() and np.abs(b).max() > 0.1
+    assert maxdiff(a, b) < 2e-3, maxdiff(a, b)
 
 
 def test_fused_block_path_at_short_utterances_in_a_subprocess(torch_cuda):

@@ -1000,9 +1000,6 @@ SWITCHES = {
     "MI355ASR_LEAF_TERMS": "0: fp32 LEAF Gabor convolution | test_leaf_*",
     "MI355ASR_SUBCONV_F32": "1: fp32-MFMA subsampling conv | test_opt_in_kernel_variants",
     "MI355ASR_SUBLINEAR_SPLIT": "0: fp32 subsampling Dense; 2: split kernels for any row count | test_opt_in_kernel_variants",
-    "MI355ASR_FF1QKV_RING": "0: fp32-MFMA ff1_qkv_kernel | test_opt_in_kernel_variants",
-    "MI355ASR_TAILFF2_RING": "0: fp32-MFMA tail_ff2_kernel | test_opt_in_kernel_variants",
-    "MI355ASR_OUTGLU_SPLIT": "0: fp32-MFMA out_glu_kernel | test_opt_in_kernel_variants",
     "MI355ASR_HEAD_RING": "0: fp32-MFMA class head | test_opt_in_kernel_variants",
     "MI355ASR_ATTN_SPLIT": "0: fp32-MFMA attention_lds_kernel | test_opt_in_kernel_variants",
     "MI355ASR_ATTN_LDS": "0: online-softmax attention_kernel (K / V from L2) | test_opt_in_kernel_variants",
