@@ -213,6 +213,9 @@ int mi355asr_recognize(mi355asr_model* m, const float* wav_dev, int32_t B, int32
  * dmodel 144, reduction_factor 4, more than 16 encoder frames in a row of L samples (pad L when every utterance is shorter), and
  * the default kernel switches; anything else returns MI355ASR_EINVAL with a message (mi355asr_last_error), checked before any
  * launch except for kernel switches, which are checked where the block reaches them.
+ * ctc_forward_ragged and translator_forward_ragged also take dmodel 256 with 64-dim heads and a ConvModule kernel size of 32, in fp32 and (the CTC decoder) in the
+ * bf16 GEMM mode (the streaming configuration's global CTC decoder over per-stream histories): every utterance's attention runs
+ * on the kernel its solo call takes.  encoder_forward_ragged and recognize_ragged do not.
  *   encoder_forward_ragged: enc_out_dev f32 [B, T(L), dmodel]; enc_len_dev i32 [B] receives T_b (may be NULL)
  *   ctc_forward_ragged:     enc_dev [B, T, dmodel] with enc_len_dev i32 [B] (1 <= enc_len[b] <= T) frames per utterance
  *   recognize_ragged:       the greedy collapse of utterance b stops at min(T_b, in_len[b]) (in_len_dev may be NULL) */
@@ -223,6 +226,24 @@ int mi355asr_ctc_forward_ragged(mi355asr_model* m, const float* enc_dev, const i
 int mi355asr_recognize_ragged(mi355asr_model* m, const float* wav_dev, const int32_t* wav_len_dev, int32_t B, int32_t L,
                               const int32_t* in_len_dev, int32_t* ids_dev, int32_t* out_len_dev, void* ws_dev, size_t ws_bytes,
                               void* stream);
+
+/* ---- Streaming server: per-stream encoder histories on the device ---------------------------------------------
+ * hist_dev f32 [N, Tcap, d] holds hist_len[s] rows of slot s; the lengths live on the device (hist_len_dev i32 [N]) and in a
+ * host copy the caller keeps (hist_len_host), on which every check is made before anything is launched.  slot_dev / slot_host:
+ * the M distinct slots of the call, on the device and on the host.
+ *   stream_append: chunk_dev f32 [M, Tc, d] goes behind row hist_len[slot[m]] of slot[m]; both copies of the lengths advance
+ *                  by Tc.  MI355ASR_EINVAL when a slot lies outside [0, N), appears twice or would overflow Tcap.
+ *   stream_gather: out_dev f32 [M, Tpad, d] receives the history of slot[m], behind it the first tail_len[m] rows of
+ *                  tail_dev f32 [M, Tc_tail, d] (all three tail arguments NULL: none; tail_len 0: none for that row; the tail
+ *                  is not stored), zeros after that; out_len_dev i32 [M] the row counts.  Tpad >= every count; the ragged CTC
+ *                  call wants Tpad >= 17.  One launch each. */
+int mi355asr_stream_append(const float* chunk_dev, const int32_t* slot_dev, const int32_t* slot_host, int32_t M, int32_t Tc,
+                           int32_t d, float* hist_dev, int32_t* hist_len_dev, int32_t* hist_len_host, int32_t N, int32_t Tcap,
+                           void* stream);
+int mi355asr_stream_gather(const float* hist_dev, const int32_t* hist_len_dev, const int32_t* hist_len_host, int32_t N,
+                           int32_t Tcap, int32_t d, const int32_t* slot_dev, const int32_t* slot_host, int32_t M,
+                           const float* tail_dev, const int32_t* tail_len_dev, const int32_t* tail_len_host, int32_t Tc_tail,
+                           float* out_dev, int32_t* out_len_dev, int32_t Tpad, void* stream);
 
 /* Stage-level entry points (same kernels the calls above run; exposed so that the parity tests can
  * localise a mismatch to one reference layer):

@@ -95,6 +95,8 @@ SIGNATURES = {
     "mi355asr_ctc_forward_ragged": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mi355asr_recognize_ragged": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_translator_forward_ragged": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi355asr_stream_append": (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
+    "mi355asr_stream_gather": (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
     "mi355asr_melspectrogram": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
     "mi355asr_conv_subsampling": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
     "mi355asr_conformer_block": (ctypes.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _SZ, _P]),

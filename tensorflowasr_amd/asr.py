@@ -194,6 +194,59 @@ class ASR:
             txt_row = tr[0].cpu().numpy()
         return self._finish(ctc_row, txt_row)
 
+    # ---- Inference/PythonInference/asr/src/asr.py: the two calls of the streaming session ---------------------------
+    def extract_feature(self, wav):
+        """the streaming encoder on a piece of audio -> enc [1, T, dmodel] on the device.  A piece that is not a whole
+        number of chunks is zero-padded to one, the rule stream_stt uses for its last piece (the reference's ONNX encoder
+        takes any length, its TF function does not)."""
+        wav = np.asarray(wav, np.float32).reshape(-1)
+        chunk = int(self.chunk)
+        n = max(1, -(-len(wav) // chunk))
+        if len(wav) < n * chunk:
+            wav = np.pad(wav, (0, n * chunk - len(wav)))
+        return self.encoder.inference(wav.reshape([1, -1, 1]))
+
+    def _text_of(self, translator_row):
+        out = []
+        for n in translator_row:
+            n = int(n)
+            if n == self.text_featurizer.endid():
+                break
+            if n != 0:
+                out.append(n)
+        return "".join(self.text_featurizer.iextract(out))
+
+    def decode(self, enc_features):
+        """the encoder outputs of a sentence so far -> text: global CTC decoder over all of them, greedy collapse, ten zero
+        tokens appended, Translator, text up to the end id"""
+        import torch
+        if not len(enc_features):
+            return ""
+        enc = enc_features[0] if len(enc_features) == 1 else torch.cat(list(enc_features), 1)
+        _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False)
+        ids, lens = ctc_greedy_decode(frame_ids, None, blank=self.phone_featurizer.num_classes - 1)
+        n = int(lens[0].item())
+        tokens = torch.zeros((1, n + 10), dtype=torch.int32, device=ids.device)
+        tokens[:, :n] = ids[:, :n].clamp(min=0)
+        _, tr = self.translator([tokens, enc], training=False, return_argmax=True, return_logits=False)
+        return self._text_of(tr[0].cpu().numpy())
+
+    def decode_batch(self, enc, enc_lengths, enc_lengths_host=None):
+        """decode() for a ragged batch: enc [M, T, dmodel] (T >= 17) holding enc_lengths[b] frames per row (int32 on the device)
+        -> [text]: one ragged CTCDecoder call, one greedy collapse, one ragged Translator call"""
+        import torch
+        _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False, lengths=enc_lengths)
+        ids, tok = ctc_greedy_decode(frame_ids, enc_lengths, blank=self.phone_featurizer.num_classes - 1)
+        tl = tok.cpu().numpy().astype(np.int32) + 10
+        U = max(17, int(tl.max()))
+        tokens = torch.zeros((enc.shape[0], U), dtype=torch.int32, device=ids.device)
+        w = min(U, ids.shape[1])
+        tokens[:, :w] = ids[:, :w].clamp(min=0)           # the collapse pads with -1: zeros, the ten appended ones among them
+        _, tr = self.translator([tokens, enc], training=False, return_argmax=True, return_logits=False,
+                                token_lengths=torch.from_numpy(tl), enc_lengths=enc_lengths)
+        tr = tr.cpu().numpy()
+        return [self._text_of(tr[b, :tl[b]]) for b in range(enc.shape[0])]
+
     def stt(self, wav_path):
         if self.speech_config["streaming"]:
             return self.stream_stt(wav_path)

@@ -1098,7 +1098,7 @@ int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const P
 }
 
 int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, char* ws, float* logits,
-             int32_t* amax, hipStream_t s, const int32_t* t_len) {
+             int32_t* amax, hipStream_t s, const int32_t* t_len, const int32_t* t_len_host = nullptr) {
   const int d = m->cfg.dmodel;
   // ragged batches: the rows past each utterance's frames get defined values once the head has run
   auto ragged_out = [&]() -> int {
@@ -1145,6 +1145,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     bo.ksz = m->cfg.ctc_kernel_size;
     bo.fc = m->cfg.ctc_fc_factor;
     bo.t_len = t_len;
+    bo.t_len_host = t_len_host;
     if (i == 0 && proj_fold) { bo.pre_x = enc; bo.pre_pp = m->proj_pp; bo.pre_sw = m->proj_pp_sw; bo.pre_chunks = 1; }
     if (i == m->cfg.ctc_num_blocks - 1 && head_it != m->head_of.end() && head_it->second.pp) {
       bo.head = &hdf; bo.head_pp = head_it->second.pp; bo.head_sw = head_it->second.pp_sw; bo.head_groups = head_it->second.groups; bo.head_done = &head_done;
@@ -1936,9 +1937,25 @@ int ragged_rows_ok(int T, const char* what) {
                 "(pad the batch: a row of more than 16 * reduction_factor * hop samples)", what, T);
   return 0;
 }
-int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s) {
+// the ragged CTC decoder / Translator at dmodel 256: 64-dim heads on the layer-at-a-time launches (fp32: the slab-ring packs
+// exist, i.e. MI355ASR_GEMM_RING on and the expected rows not set below the ring kernels' crossover; bf16: always)
+int ragged_layers256_ok(const mi355asr_model* m, int ksz) {
+  if (m->cfg.dmodel != 256 || m->cfg.head_size != 64)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support dmodel other than 144, and 256 with 64-dim heads (dmodel %d, head size %d)",
+                m->cfg.dmodel, m->cfg.head_size);
+  if (ksz != 32)
+    return fail(MI355ASR_EINVAL, "ragged batches at dmodel 256 need a ConvModule kernel size of 32: the depthwise conv kernels that "
+                "apply lengths (kernel size %d)", ksz);
+  if (!use_gemm16(m))
+    return fail(MI355ASR_EINVAL, "ragged batches at dmodel 256 need the layer-at-a-time launches: the slab-ring packs are missing "
+                "(MI355ASR_GEMM_RING=0, or expected rows below the ring kernels' crossover)");
+  return 0;
+}
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s, std::vector<int32_t>* host) {
   if (!len_dev) return fail(MI355ASR_EINVAL, "%s: null device pointer", what);
-  std::vector<int32_t> h((size_t)B);
+  std::vector<int32_t> own;
+  std::vector<int32_t>& h = host ? *host : own;
+  h.assign((size_t)B, 0);
   HIP_TRY(hipMemcpyAsync(h.data(), len_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int b = 0; b < B; ++b)
@@ -1969,15 +1986,17 @@ int mi355asr_ctc_forward_ragged(mi355asr_model* m, const float* enc, const int32
   int rc = check_ready(m);
   if (rc) return rc;
   if (m->cfg.num_classes <= 0) return fail(MI355ASR_ESTATE, "model was created without a CTC head (num_classes=0)");
-  if (m->cfg.gemm_dtype != 0 || m->cfg.dmodel != 144)
-    return fail(MI355ASR_EINVAL, "ragged batches do not support %s", m->cfg.gemm_dtype != 0 ? "the bf16 GEMM mode" : "dmodel other than 144");
+  if (m->cfg.dmodel == 144 && m->cfg.gemm_dtype != 0)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support the bf16 GEMM mode at dmodel 144");
+  if (m->cfg.dmodel != 144 && (rc = ragged_layers256_ok(m, m->cfg.ctc_kernel_size))) return rc;
   if (!enc || !ws || B <= 0 || T <= 0) return fail(MI355ASR_EINVAL, "bad argument");
   if ((rc = ragged_rows_ok(T, "T"))) return rc;
   const Plan p = make_plan(m, B, 16, T);
   if (ws_bytes < p.logp) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.logp);
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s))) return rc;
-  return ctc_impl(m, enc, B, T, p, (char*)ws, logits, amax, s, enc_len);
+  std::vector<int32_t> len_host;
+  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s, &len_host))) return rc;
+  return ctc_impl(m, enc, B, T, p, (char*)ws, logits, amax, s, enc_len, len_host.data());
 }
 
 int mi355asr_recognize_ragged(mi355asr_model* m, const float* wav, const int32_t* wav_len, int32_t B, int32_t L,

@@ -163,17 +163,18 @@ int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, co
                                        void* ws_, size_t ws_bytes, void* stream) {
   if (!m || !m->is_translator) return fail(MI355ASR_EINVAL, "not a Translator handle");
   if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
-  if (m->cfg.dmodel != 144) return fail(MI355ASR_EINVAL, "ragged batches do not support dmodel other than 144 (dmodel %d)", m->cfg.dmodel);
+  int rc = 0;
+  if (m->cfg.dmodel != 144 && (rc = ragged_layers256_ok(m, m->tcfg.kernel_size))) return rc;
   if (!ids || !enc || !ws_) return fail(MI355ASR_EINVAL, "null argument");
   if (B < 1 || U < 1 || T < 1) return fail(MI355ASR_EINVAL, "B, U, T must be positive (got %d, %d, %d)", B, U, T);
   if (U > kMaxTokens) return fail(MI355ASR_EINVAL, "U=%d exceeds the positional-encoding table (%d rows)", U, kMaxTokens);
-  int rc = ragged_rows_ok(U, "U");
-  if (rc || (rc = ragged_rows_ok(T, "T"))) return rc;
+  if ((rc = ragged_rows_ok(U, "U")) || (rc = ragged_rows_ok(T, "T"))) return rc;
   const TransPlan p = make_trans_plan(m, B, U, T);
   if (ws_bytes < p.total) return fail(MI355ASR_EINVAL, "workspace too small: %zu < %zu", ws_bytes, p.total);
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = ragged_check_lengths(tok_len, B, U, "tok_len", s))) return rc;
-  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s))) return rc;
+  std::vector<int32_t> tok_host, enc_host;
+  if ((rc = ragged_check_lengths(tok_len, B, U, "tok_len", s, &tok_host))) return rc;
+  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s, &enc_host))) return rc;
   char* ws = (char*)ws_;
   const int d = m->cfg.dmodel, M = B * U;
   Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
@@ -183,7 +184,9 @@ int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, co
   LAUNCH_TRY(launch_embed(ea, s), "embedding");
   CrossAttn cr{enc, T, (float*)(ws + p.kv), m->t_pe};
   cr.k_len = enc_len;
+  cr.k_len_host = enc_host.data();
   BlockOpts bo = m->t_stack.opts;
+  bo.t_len_host = tok_host.data();
   bo.t_len = tok_len;                   // the ConvModule's depthwise conv reads zeros from token row tok_len[b] on
   for (const auto& blk : m->t_stack.blocks)
     if ((rc = run_block(m, blk, bo, sc, B, U, nullptr, s, &cr))) return rc;

@@ -39,15 +39,19 @@ __global__ __launch_bounds__(ATH, 2) void attention_lds_kernel(AttnArgs a) {
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, g4 = g * 4, c = lane & 15;
   const int qt = blockIdx.x * AW + (threadIdx.x >> 6);
-  const int T = a.Tk, TQ = a.Tq;       // keys / queries per utterance
+  const int TKA = a.Tk, TQA = a.Tq;    // rows per utterance in the buffers
   const int h = blockIdx.y, b = blockIdx.z;
+  int T = TKA, TQ = TQA;               // keys / queries of this utterance
+  if constexpr (HS == 64) {            // ragged batches: the utterance's own lengths (attn64_class; uniform per workgroup)
+    if (a.k_len && (!attn64_mine(a, b, ATTN64_LDS, &TQ, &T) || (int)blockIdx.x * AW * 16 >= TQ)) return;
+  }
   const int ld = a.ldk, D = a.D;
-  const float* __restrict__ kbase = a.k + (size_t)b * T * ld + h * HS;
-  const float* __restrict__ vbase = a.v + (size_t)b * T * ld + h * HS;
+  const float* __restrict__ kbase = a.k + (size_t)b * TKA * ld + h * HS;
+  const float* __restrict__ vbase = a.v + (size_t)b * TKA * ld + h * HS;
 
   // ---- this lane's query fragment (log2 e folded in: softmax uses exp2)
   const int tq = qt * 16 + c;
-  const float* qrow = a.q + ((size_t)b * TQ + min(tq, TQ - 1)) * a.ldq + h * HS;
+  const float* qrow = a.q + ((size_t)b * TQA + min(tq, TQ - 1)) * a.ldq + h * HS;
   constexpr float LOG2E = 1.4426950408889634f;
   f32x4 q4[FB > 0 ? FB : 1];
   float qs[TS > 0 ? TS : 1];
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(ATH, 2) void attention_lds_kernel(AttnArgs a) {
   }
   const float inv = 1.0f / group_sum(psum);
   if (tq < TQ) {
-    float* orow = a.ctx + ((size_t)b * TQ + tq) * D + h * HS;
+    float* orow = a.ctx + ((size_t)b * TQA + tq) * D + h * HS;
 #pragma unroll
     for (int i = 0; i < OT; ++i) {
       if (16 * i + g4 < HS) stg4(orow + 16 * i + g4, o[i] * splat4(inv));
@@ -183,11 +187,13 @@ __global__ __launch_bounds__(ATH, 2) void attention_lds_kernel(AttnArgs a) {
 
 bool attention_lds_applicable(int HS, const AttnArgs& a) {
   // head size 64 (ConformerM / L): K and V^T take 130 KB, one workgroup per CU.
+  if (HS == 64 && a.k_len) return a.win_front < 0 && !a.head_major;     // ragged: each utterance's own counts (attn64_class)
   return (HS == 36 || HS == 64) && a.win_front < 0 && a.Tk <= (HS == 64 ? TP_MAX : 256) && a.Tk > 16 && a.Tq > 16;
 }
 
 int launch_attention_lds(int HS, const AttnArgs& a, hipStream_t s) {
   if (!attention_lds_applicable(HS, a)) return -1;
+  if (a.k_len && !(HS == 64 && (a.own_flags & ATTN64_F_LDS))) return -1;   // ragged: only as launch_attention's LDS class
   const int qtiles = (a.Tq + 15) / 16;
   dim3 grid((qtiles + AW - 1) / AW, a.H, a.B);
   if (HS == 64 && a.Tk > 256) hipLaunchKernelGGL((attention_lds_kernel<64, TP_MAX>), grid, dim3(ATH), 0, s, a);

@@ -72,11 +72,15 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = lane >> 4, g4 = g * 4, c = lane & 15;
-  const int T = a.Tk, TQ = a.Tq;
+  const int TKA = a.Tk, TQA = a.Tq;                                        // rows per utterance in the buffers
   const int h = blockIdx.y, b = blockIdx.z;
+  int T = TKA, TQ = TQA;                                                   // keys / queries of this utterance
+  // ragged batches: the utterance's own lengths; utterances of another class (attn64_class) and query tiles past the
+  // utterance leave before anything is staged (uniform per workgroup).  Key tiles past T are neither staged nor multiplied.
+  if (a.k_len && (!attn64_mine(a, b, ATTN64_SPLIT64, &TQ, &T) || (int)blockIdx.x * MAXQT * 16 >= TQ)) return;
   const int ld = a.ldk, D = a.D;
-  const float* __restrict__ kbase = a.k + (size_t)b * T * ld + h * HS;
-  const float* __restrict__ vbase = a.v + (size_t)b * T * ld + h * HS;
+  const float* __restrict__ kbase = a.k + (size_t)b * TKA * ld + h * HS;
+  const float* __restrict__ vbase = a.v + (size_t)b * TKA * ld + h * HS;
 
   // ---- stage K and V: every global load of the workgroup is requested before the first is used (a load per loop trip costs a
   // memory latency each: ten trips were half of the first version's 35 us), then split and written as fragments.
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
   const f32x4 inv_qk = splat4(1.0f / (sq * sk));                           // powers of two
   for (int qt = blockIdx.x * MAXQT + wv; qt < min(nqt, (int)(blockIdx.x + 1) * MAXQT); qt += AW) {
     const int tq = qt * 16 + c;
-    const float* qrow = a.q + ((size_t)b * TQ + min(tq, TQ - 1)) * a.ldq + h * HS;
+    const float* qrow = a.q + ((size_t)b * TQA + min(tq, TQ - 1)) * a.ldq + h * HS;
     Split2 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
     }
     const float inv = (1.0f / group_sum(psum)) * (1.0f / (SP * sv));      // the second factor is a power of two
     if (tq < TQ) {
-      float* orow = a.ctx + ((size_t)b * TQ + tq) * D + h * HS;
+      float* orow = a.ctx + ((size_t)b * TQA + tq) * D + h * HS;
 #pragma unroll
       for (int i = 0; i < OT; ++i) stg4(orow + 16 * i + g4, o[i] * splat4(inv));
     }
@@ -197,12 +201,14 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
 }  // namespace
 
 bool attention_split64_applicable(int hs, const AttnArgs& a) {
-  return hs == HS && a.win_front < 0 && !a.head_major && a.Tk <= 16 * NKT && a.Tk > 32 && a.Tq > 16 && a.ldk % 4 == 0 && a.ldq % 4 == 0 &&
+  // (with key lengths the key and query counts are those of each utterance: attn64_class)
+  return hs == HS && a.win_front < 0 && !a.head_major && (a.k_len || (a.Tk <= 16 * NKT && a.Tk > 32 && a.Tq > 16)) && a.ldk % 4 == 0 && a.ldq % 4 == 0 &&
          a.h2_sq > 0.f && a.h2_sk > 0.f && a.h2_sv > 0.f;
 }
 
 int launch_attention_split64(int hs, const AttnArgs& a, hipStream_t s) {
   if (!attention_split64_applicable(hs, a)) return -1;
+  if (a.k_len && !(a.own_flags & ATTN64_F_SPLIT64)) return -1;      // ragged: only as launch_attention's split64 class
   note_scheme(SCHEME_F16X2);
   const int qtiles = (a.Tq + 15) / 16;
   hipLaunchKernelGGL(attention_split64_kernel, dim3((qtiles + MAXQT - 1) / MAXQT, a.H, a.B), dim3(ATH), 0, s, a);

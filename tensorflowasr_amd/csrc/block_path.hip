@@ -43,7 +43,11 @@ AttnChoice choose_attention(int HS, const AttnArgs& a) {
     c.kernel = a.Tk > ATTN_SPLIT_SHORT_KEYS ? ATTN_SPLIT_LONG : ATTN_SPLIT;
     return c;
   }
-  if (a.k_len) return c;                              // ragged batches: the split kernels are the ones that apply key lengths
+  if (a.k_len) {                                      // ragged batches: the split kernels apply key lengths, and at head size 64
+    // (token-major rows, full attention) every kernel of the solo call does, each for the utterances it would take alone
+    if (HS == 64 && a.win_front < 0 && !a.head_major && a.ldk % 4 == 0 && a.ldq % 4 == 0) c.kernel = ATTN_RAGGED64;
+    return c;
+  }
   if (split_on && w.attn64_split && attention_split64_applicable(HS, a)) {   // round 5: head size 64, bounds known, <= 288 keys
     c.kernel = ATTN_SPLIT64;
     c.terms = 2;
@@ -53,6 +57,15 @@ AttnChoice choose_attention(int HS, const AttnArgs& a) {
   if (w.attn_lds && attention_lds_applicable(HS, a)) c.kernel = ATTN_LDS;
   else if (attention_head_size_ok(HS)) c.kernel = ATTN_ONLINE;
   return c;
+}
+
+// what choose_attention allows a solo call of head size 64 with these operands (the arguments of attn64_class)
+int attn64_flags(const AttnArgs& a) {
+  const BlockSwitches& w = block_switches();
+  int f = 0;
+  if (w.attn_lds && w.attn_split && w.attn64_split && a.h2_sq > 0.f && a.h2_sk > 0.f && a.h2_sv > 0.f) f |= ATTN64_F_SPLIT64;
+  if (w.attn_lds) f |= ATTN64_F_LDS;
+  return f;
 }
 
 namespace mi355 {
@@ -143,6 +156,9 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
   }
   if (bo.t_len) {
     at.k_len = cross ? cross->k_len : bo.t_len;
+    at.q_len = bo.t_len;                                 // the utterance's own queries: its frames, or its tokens
+    at.q_len_host = bo.t_len_host;
+    at.k_len_host = cross ? cross->k_len_host : bo.t_len_host;
     if (!at.k_len || !choose_attention(hs, at).applies_lengths())
       return fail(MI355ASR_EINVAL, "ragged batches: no length-aware attention kernel for Tq = %d, Tk = %d", at.Tq, at.Tk);
   }
@@ -449,8 +465,11 @@ int run_block(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, S
   if (bo.pre_pp && (cross || skip_ff1 || !block_takes_pre(m, w, (size_t)M)))
     return fail(MI355ASR_ESTATE, "run_block: a layer in front of a block that cannot take it");
   // (ragged batches: the fused kernels, or the layer-at-a-time fp32 launches of at most MI355ASR_SMALL_M rows)
-  if (bo.t_len && (d != 144 || use_gemm16(m) || (!sw.fused && !gemm16_for(m, M))))
-    return fail(MI355ASR_EINVAL, "ragged batches: only the fp32 dmodel-144 block kernels apply lengths (dmodel %d%s%s)", d,
+  // (... and dmodel 256 with 64-dim heads on the layer-at-a-time launches, fp32 or bf16: run_block_layers)
+  const bool layers256 = d == 256 && m->cfg.head_size == 64 && use_gemm16(m);
+  if (bo.t_len && !layers256 && (d != 144 || use_gemm16(m) || (!sw.fused && !gemm16_for(m, M))))
+    return fail(MI355ASR_EINVAL, "ragged batches: only the fp32 dmodel-144 block kernels and the layer-at-a-time launches of "
+                "dmodel 256 with 64-dim heads apply lengths (dmodel %d%s%s)", d,
                 sw.fused ? "" : ", MI355ASR_FUSED=0", use_gemm16(m) ? ", bf16 / layer-at-a-time GEMM mode" : "");
   if (gemm16_for(m, M)) return run_block_layers(m, w, bo, sc, B, T, out, s, cross);
   // round 6: the Translator's RBlock takes the fused kernels too -- its query projection (of LayerNorm(x1 + PE)) rides in the

@@ -430,13 +430,17 @@ __global__ __launch_bounds__(BLOCK_THREADS, ((HS > 36 && KT >= 16) ? 1 : 2)) voi
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, g4 = g * 4, c = lane & 15;
   const int qt = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-  const int T = a.Tk, TQ = a.Tq;       // keys / queries per utterance
-  if (!LDSW && qt * 16 >= TQ) return;
+  const int TKA = a.Tk, TQA = a.Tq;    // rows per utterance in the buffers
   const int h = blockIdx.y, b = blockIdx.z;
+  int T = TKA, TQ = TQA;               // keys / queries of this utterance
+  if constexpr (HS == 64 && !LDSW) {   // ragged batches: the utterance's own lengths (attn64_class; uniform per workgroup)
+    if (a.k_len && !attn64_mine(a, b, KT == 1 ? ATTN64_ONLINE1 : KT == 4 ? ATTN64_ONLINE4 : ATTN64_ONLINE16, &TQ, &T)) return;
+  }
+  if (!LDSW && qt * 16 >= TQ) return;
   const int ld = a.ldk;  // row stride of the k / v buffers
   const int D = a.D;
-  const float* __restrict__ kbase = a.k + (size_t)b * T * ld + h * HS;
-  const float* __restrict__ vbase = a.v + (size_t)b * T * ld + h * HS;
+  const float* __restrict__ kbase = a.k + (size_t)b * TKA * ld + h * HS;
+  const float* __restrict__ vbase = a.v + (size_t)b * TKA * ld + h * HS;
   __shared__ __attribute__((aligned(16))) float kw[LDSW ? ATT_WROWS * HS : 4], vw[LDSW ? ATT_WROWS * HS : 4];
   int wbeg = 0;                        // first key row of the staged window
   if constexpr (LDSW) {
@@ -459,7 +463,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, ((HS > 36 && KT >= 16) ? 1 : 2)) voi
   }
 
   const int tq = qt * 16 + c;
-  const float* qrow = a.q + ((size_t)b * TQ + min(tq, TQ - 1)) * a.ldq + h * HS;
+  const float* qrow = a.q + ((size_t)b * TQA + min(tq, TQ - 1)) * a.ldq + h * HS;
   f32x4 q4[FB > 0 ? FB : 1];
   float qs[TS > 0 ? TS : 1];
 #pragma unroll
@@ -614,7 +618,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, ((HS > 36 && KT >= 16) ? 1 : 2)) voi
   }
   const float inv = 1.0f / group_sum(l_run);
   if (tq < TQ) {
-    float* orow = a.ctx + ((size_t)b * TQ + tq) * D + h * HS;
+    float* orow = a.ctx + ((size_t)b * TQA + tq) * D + h * HS;
 #pragma unroll
     for (int i = 0; i < OT; ++i) {
       if (16 * i + g4 < HS) stg4(orow + 16 * i + g4, o[i] * splat4(inv));
@@ -638,9 +642,32 @@ static void launch_attention_t(const AttnArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((attention_kernel<HS, 16>), grid, dim3(BLOCK_THREADS), 0, s, a);
 }
 
+// ragged batches at head size 64: one launch per kernel class that some utterance of the batch falls into (attn64_class)
+static int launch_attention_ragged64(AttnArgs a, hipStream_t s) {
+  a.own_flags = attn64_flags(a);
+  int need = 0;
+  if (a.k_len_host)
+    for (int b = 0; b < a.B; ++b) {
+      const int tk = min(a.k_len_host[b], a.Tk), tq = min(a.q_len_host ? a.q_len_host[b] : a.k_len_host[b], a.Tq);
+      need |= 1 << attn64_class(tq, tk, a.own_flags);
+    }
+  else need = ~0;
+  auto want = [&](int c) { return (need >> c) & 1; };
+  if ((a.own_flags & ATTN64_F_SPLIT64) && want(ATTN64_SPLIT64) && launch_attention_split64(64, a, s) != 0) return -1;
+  if ((a.own_flags & ATTN64_F_LDS) && want(ATTN64_LDS) && launch_attention_lds(64, a, s) != 0) return -1;
+  note_scheme(SCHEME_F32);
+  const int qtiles = (a.Tq + 15) / 16;
+  const dim3 grid((qtiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, a.H, a.B), blk(BLOCK_THREADS);
+  if (want(ATTN64_ONLINE1)) hipLaunchKernelGGL((attention_kernel<64, 1>), grid, blk, 0, s, a);
+  if (want(ATTN64_ONLINE4)) hipLaunchKernelGGL((attention_kernel<64, 4>), grid, blk, 0, s, a);
+  if (want(ATTN64_ONLINE16)) hipLaunchKernelGGL((attention_kernel<64, 16>), grid, blk, 0, s, a);
+  return 0;
+}
+
 int launch_attention(int HS, const AttnArgs& a, hipStream_t s) {
   const AttnChoice c = choose_attention(HS, a);       // block_path.hip
   switch (c.kernel) {
+    case ATTN_RAGGED64: return launch_attention_ragged64(a, s);
     case ATTN_SPLIT:
     case ATTN_SPLIT_LONG: return launch_attention_split(HS, a, c.terms, s);
     case ATTN_SPLIT64: return launch_attention_split64(HS, a, s);
@@ -808,7 +835,8 @@ static int launch_dwconv_tile(const DwArgs& a, hipStream_t s) {
 }
 
 int launch_dwconv(int K, const DwArgs& a, hipStream_t s) {
-  if (a.t_len && !(K == 32 && a.D == 144)) return -1;   // ragged batches: dwconv_tile_kernel<32, 144> / dwconv_kernel<32, 8> only
+  // ragged batches: dwconv_tile_kernel<32, 144 / 128> / dwconv_kernel<32, 8> only
+  if (a.t_len && !(K == 32 && (a.D == 144 || a.D % 128 == 0))) return -1;
   if (a.T * a.B >= 2048) {                  // LDS-tiled kernel; below: the first-generation kernel (window re-read from L2 per thread)
     if (K == 32 && a.D == 144) return launch_dwconv_tile<32, 144>(a, s);
     if (K == 32 && a.D % 128 == 0) return launch_dwconv_tile<32, 128>(a, s);

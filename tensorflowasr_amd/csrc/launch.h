@@ -75,6 +75,12 @@ struct AttnArgs {
   int win_front, win_back;
   // ragged batches: keys t >= k_len[b] of utterance b are excluded from the softmax (nullptr: all Tk keys); [B] on the device
   const int32_t* k_len = nullptr;
+  // ragged batches, head size 64 (attn64_class below): the queries of utterance b (nullptr: k_len[b], self-attention) and
+  // which of the kernels the solo call could take are enabled (ATTN64_F_*, set by launch_attention)
+  const int32_t* q_len = nullptr;
+  const int32_t *k_len_host = nullptr, *q_len_host = nullptr;   // host copies of k_len / q_len (the entry points read them back):
+                                                                // the launcher skips the kernels no utterance falls to
+  int own_flags = 0;
   // two-term fp16 scheme of attention_split_kernel: powers of two with bound(|q| log2 e) * h2_sq, bound(|k|) * h2_sk,
   // bound(|v|) * h2_sv <= 2^15 (api.hip derives the bounds from the q / k / v weights and the LayerNorm in front of them);
   // 0 = unknown bounds (stage calls on caller-supplied q / k / v): the three-term bf16 kernel
@@ -416,14 +422,36 @@ struct BlockSwitches {
 };
 const BlockSwitches& block_switches();
 // the attention kernel launch_attention takes for a launch (ATTN_NONE: none, it returns -1)
-enum AttnKernel { ATTN_NONE, ATTN_SPLIT, ATTN_SPLIT_LONG, ATTN_SPLIT64, ATTN_LDS, ATTN_ONLINE };
+// ATTN_RAGGED64: head size 64 with AttnArgs::k_len -- every utterance on the kernel its solo call takes (attn64_class)
+enum AttnKernel { ATTN_NONE, ATTN_SPLIT, ATTN_SPLIT_LONG, ATTN_SPLIT64, ATTN_LDS, ATTN_ONLINE, ATTN_RAGGED64 };
 struct AttnChoice {
   AttnKernel kernel = ATTN_NONE;
   int terms = 0;   // ATTN_SPLIT / ATTN_SPLIT_LONG: two fp16 or three bf16 terms per operand
   bool split() const { return kernel == ATTN_SPLIT || kernel == ATTN_SPLIT_LONG; }
   bool head_major() const { return split() && terms == 2; }   // the one form that reads head-major q / k / v
-  bool applies_lengths() const { return split(); }              // ... and the kernels that read AttnArgs::k_len
+  bool applies_lengths() const { return split() || kernel == ATTN_RAGGED64; }   // ... and the kernels that read AttnArgs::k_len
 };
+// Ragged batches at head size 64 (full attention, token-major rows).  A ragged row is defined as the solo call's result, and the
+// solo call's attention kernel depends on its own tq queries and tk keys: attention_split64_kernel for 33 .. 288 keys where the
+// operand bounds are known, attention_lds_kernel for 17 .. 272, else the online-softmax attention_kernel with key blocks of 16 /
+// 64 / 256.  These differ in arithmetic (fp16 terms; one-pass or running softmax), so a ragged launch runs every one of them that
+// some utterance of the batch needs, and a workgroup whose utterance belongs to another class leaves at once (uniform per
+// workgroup).  This is choose_attention() + launch_attention_t<64>() restated per utterance; flags = what the switches and the
+// operand bounds allow (attn64_flags).
+enum { ATTN64_ONLINE1 = 1, ATTN64_ONLINE4 = 2, ATTN64_ONLINE16 = 3, ATTN64_LDS = 4, ATTN64_SPLIT64 = 5 };
+enum { ATTN64_F_SPLIT64 = 1, ATTN64_F_LDS = 2 };
+__host__ __device__ __forceinline__ int attn64_class(int tq, int tk, int flags) {
+  if ((flags & ATTN64_F_SPLIT64) && tk > 32 && tk <= 288 && tq > 16) return ATTN64_SPLIT64;
+  if ((flags & ATTN64_F_LDS) && tk > 16 && tk <= 272 && tq > 16) return ATTN64_LDS;
+  return tk <= 16 ? ATTN64_ONLINE1 : tk <= 96 ? ATTN64_ONLINE4 : ATTN64_ONLINE16;
+}
+// the utterance's own (queries, keys) in a kernel of class `mine`; false: another kernel's utterance
+__device__ __forceinline__ bool attn64_mine(const AttnArgs& a, int b, int mine, int* tq, int* tk) {
+  *tk = min(a.k_len[b], a.Tk);
+  *tq = min(a.q_len ? a.q_len[b] : a.k_len[b], a.Tq);
+  return attn64_class(*tq, *tk, a.own_flags) == mine;
+}
+int attn64_flags(const AttnArgs& a);    // block_path.hip: ATTN64_F_* from the switches and the launch's operand bounds
 constexpr int ATTN_SPLIT_SHORT_KEYS = 256;                     // keys of attention_split_kernel; more: attention_split_long_kernel
 AttnChoice choose_attention(int HS, const AttnArgs& a);
 // three-term loader-wave kernels (fused.hip)

@@ -101,8 +101,10 @@ struct BlockOpts {
   int head_groups = 0;
   bool* head_done = nullptr;
   // ragged batches: utterance b has t_len[b] of the T frames ([B] on the device): its attention sees only those keys and its
-  // depthwise conv reads zeros from frame t_len[b] on.  Only the dmodel-144 fused kernels apply it; run_block refuses the rest.
+  // depthwise conv reads zeros from frame t_len[b] on.  The dmodel-144 fused kernels and the layer-at-a-time
+  // launches of dmodel 256 with 64-dim heads apply it; run_block refuses the rest.
   const int32_t* t_len = nullptr;
+  const int32_t* t_len_host = nullptr;   // ... its host copy, where the entry point has read it back (head size 64: attn64_class)
 };
 
 struct StackDev {
@@ -293,6 +295,7 @@ struct CrossAttn {
   float* kv;          // scratch [B * T_enc, 2d]
   const float* pe;    // [>= T, d]
   const int32_t* k_len = nullptr;   // ragged batches: encoder frames of each utterance ([B] on the device): keys past them are excluded
+  const int32_t* k_len_host = nullptr;   // ... and their host copy
 };
 
 struct StackOff {
@@ -352,7 +355,8 @@ int run_class_head(const mi355asr_model* m, GemmArgs hd, HeadLayers layers, floa
                    hipStream_t s);
 // ragged batches (api.hip): more than 16 rows per utterance, or EINVAL; the device lengths read back and held to [1, hi]
 int ragged_rows_ok(int T, const char* what);
-int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s);
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s, std::vector<int32_t>* host = nullptr);
+int ragged_layers256_ok(const mi355asr_model* m, int ksz);   // dmodel 256, 64-dim heads, ConvModule kernel 32, layer-at-a-time launches
 void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V);   // api_chunk.hip
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip
