@@ -1,0 +1,157 @@
+// CTC prefix beam search behind the C ABI: the one-shot mi355asr_ctc_prefix_beam* entry points (top-n selection on the device, the
+// search on the device or on host threads) and the stateful mi355asr_beam_* decoder handle.  Kernels: beam_device.hip; host search: beam.hip.
+#include "model.h"
+
+extern "C" {
+
+int mi355asr_ctc_prefix_beam_host(const float* probs, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                                  int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                                  int32_t max_len, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp) {
+  if (!probs || !ids || !lens || !scores || !n_hyp) return fail(MI355ASR_EINVAL, "null pointer");
+  if (B <= 0 || T <= 0 || V < 2 || beam_size <= 0 || max_len <= 0 || cutoff_top_n <= 0)
+    return fail(MI355ASR_EINVAL, "bad beam-search argument (B=%d T=%d V=%d beam=%d max_len=%d top_n=%d)", B, T, V,
+                beam_size, max_len, cutoff_top_n);
+  return mi355asr_beam_host_impl(probs, in_len, B, T, V, beam_size, cutoff_prob, cutoff_top_n, num_threads, max_len, ids,
+                                 lens, scores, n_hyp);
+}
+
+int mi355asr_ctc_prefix_beam(const float* x, int32_t is_logits, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                             int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                             int32_t max_len, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp, void* ws,
+                             size_t ws_bytes, void* stream) {
+  if (!x || !ids || !lens || !scores || !n_hyp || !ws) return fail(MI355ASR_EINVAL, "null pointer");
+  if (B <= 0 || T <= 0 || V < 2 || beam_size <= 0 || max_len <= 0 || cutoff_top_n <= 0)
+    return fail(MI355ASR_EINVAL, "bad beam-search argument");
+  if (!(cutoff_prob < 1.0))
+    return fail(MI355ASR_EINVAL, "cutoff_prob >= 1 disables pruning in the reference (every class is visited): use "
+                "mi355asr_ctc_prefix_beam_host for that mode");
+  const int N = std::min(cutoff_top_n, V);
+  if (N > 128) return fail(MI355ASR_EINVAL, "cutoff_top_n=%d: the selection kernel supports up to 128", cutoff_top_n);
+  const size_t frames = (size_t)B * T;
+  const size_t need = frames * N * (sizeof(int32_t) + sizeof(float));
+  if (ws_bytes < need) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* d_idx = (int32_t*)ws;
+  float* d_p = (float*)((char*)ws + frames * N * sizeof(int32_t));
+  if (mi355asr_launch_topn(x, (int)frames, V, N, is_logits, d_idx, d_p, s) != 0)
+    return fail(MI355ASR_EHIP, "top-n kernel launch failed (V=%d needs %zu bytes of LDS)", V, (size_t)V * 4);
+  // MI355ASR_BEAM_DEVICE=0: the prefix search on host threads (beam.hip) instead of the device kernel (beam_device.hip)
+  static const bool dev_env = mi355_env("MI355ASR_BEAM_DEVICE", 1) != 0;
+  const size_t need_dev = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
+  if (dev_env && mi355asr_beam_device_applicable(V, N, beam_size) && ws_bytes >= need_dev) {
+    char* w = (char*)ws + ((need + 255) & ~(size_t)255);
+    BeamDeviceArgs a{};
+    a.top_idx = d_idx; a.top_p = d_p; a.B = B; a.T = T; a.V = V; a.N = N; a.beam = beam_size;
+    a.cutoff_top_n = cutoff_top_n; a.max_len = max_len; a.cutoff_prob = cutoff_prob;
+    int32_t* d_len = nullptr;
+    long long* d_prof = nullptr;
+    (void)mi355asr_beam_device_carve(w, B, T, beam_size, max_len, &a, &d_len, &d_prof);   // the same layout the size query adds up
+    // MI355ASR_BEAM_PROF=1: clock counters of utterance 0's search, printed per call (where a frame's time goes)
+    static const bool prof_env = mi355_env("MI355ASR_BEAM_PROF", 0) != 0;
+    if (prof_env) {
+      a.prof = d_prof;
+      HIP_TRY(hipMemsetAsync(a.prof, 0, 16 * sizeof(long long), s));
+    }
+    // The four results sit next to each other in the workspace (mi355asr_beam_device_carve): ONE copy into a pinned staging buffer of
+    // the calling thread, then host copies -- the caller's arrays are pageable (NumPy), and four hipMemcpyAsync into pageable memory are
+    // four staged, synchronous copies: ~120 us behind a 2.4 ms search (round 6, kernel trace of config 5); the lengths go up through
+    // the same buffer (behind the results' span), so the search is launched without a host-side wait.  The buffer is kept for the
+    // thread's lifetime (never freed: at process exit the runtime may be gone before a destructor would run).
+    const size_t n_ids = (size_t)B * beam_size * max_len * sizeof(int32_t), n_lens = (size_t)B * beam_size * sizeof(int32_t),
+                 n_scores = (size_t)B * beam_size * sizeof(float), n_nh = (size_t)B * sizeof(int32_t);
+    const size_t span = (size_t)((const char*)a.n_hyp - (const char*)a.ids) + n_nh, want = span + n_nh + 64;
+    static thread_local char* stage = nullptr;
+    static thread_local size_t stage_cap = 0;
+    if (want > stage_cap) {
+      if (stage) (void)hipHostFree(stage);
+      stage = nullptr; stage_cap = 0;
+      void* q = nullptr;
+      if (hipHostMalloc(&q, want + want / 4, hipHostMallocDefault) == hipSuccess) { stage = (char*)q; stage_cap = want + want / 4; }
+      else (void)hipGetLastError();
+    }
+    if (in_len) {
+      const void* src = in_len;
+      if (stage) { std::memcpy(stage + span, in_len, n_nh); src = stage + span; }
+      HIP_TRY(hipMemcpyAsync(d_len, src, n_nh, hipMemcpyHostToDevice, s));
+      a.in_len = d_len;
+    }
+    if (mi355asr_launch_beam_device(&a, s) != 0) return fail(MI355ASR_EHIP, "device beam search launch failed");
+    long long prof[16] = {0};
+    if (stage) {
+      HIP_TRY(hipMemcpyAsync(stage, a.ids, span, hipMemcpyDeviceToHost, s));
+    } else {
+      HIP_TRY(hipMemcpyAsync(ids, a.ids, n_ids, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(lens, a.lens, n_lens, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(scores, a.scores, n_scores, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(n_hyp, a.n_hyp, n_nh, hipMemcpyDeviceToHost, s));
+    }
+    if (a.prof) HIP_TRY(hipMemcpyAsync(prof, a.prof, sizeof(prof), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (stage) {
+      std::memcpy(ids, stage, n_ids);
+      std::memcpy(lens, stage + ((const char*)a.lens - (const char*)a.ids), n_lens);
+      std::memcpy(scores, stage + ((const char*)a.scores - (const char*)a.ids), n_scores);
+      std::memcpy(n_hyp, stage + ((const char*)a.n_hyp - (const char*)a.ids), n_nh);
+    }
+    if (a.prof) {
+      const double f = (double)std::max(1ll, prof[8]);
+      fprintf(stderr, "[mi355asr] beam %d, utterance 0: %lld frames (%lld redone by the radix path); clocks per frame: entries %.0f, "
+              "keys+ranks %.0f, keep %.0f, radix path %.0f (keys %.0f, select %.0f, compaction %.0f); inside the entry phase: thread 0 "
+              "%.0f (%.0f up to the parent search), wave 3's candidate list %.0f (%.0f cumulative cut-off)\n", beam_size, prof[8],
+              prof[4], prof[0] / f, prof[1] / f, prof[2] / f, prof[3] / f, prof[5] / f, prof[6] / f, prof[7] / f, prof[9] / f, prof[10] / f,
+              prof[11] / f, prof[12] / f);
+    }
+    return 0;
+  }
+  std::vector<int32_t> h_idx(frames * N);
+  std::vector<float> h_p(frames * N);
+  HIP_TRY(hipMemcpyAsync(h_idx.data(), d_idx, h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h_p.data(), d_p, h_p.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return mi355asr_beam_topn_impl(h_idx.data(), h_p.data(), in_len, B, T, V, N, beam_size, cutoff_prob, cutoff_top_n,
+                                 num_threads, max_len, ids, lens, scores, n_hyp);
+}
+
+int mi355asr_beam_math_eval(int32_t kind, const float* in_dev, void* out_dev, int32_t n, void* stream) {
+  if (!in_dev || !out_dev || n < 0 || kind < 0 || kind > 3) return fail(MI355ASR_EINVAL, "bad argument");
+  if (mi355asr_launch_refmath_eval(kind, in_dev, out_dev, n, (hipStream_t)stream) != 0)
+    return fail(MI355ASR_EHIP, "refmath kernel launch failed");
+  return 0;
+}
+
+int mi355asr_ctc_prefix_beam_workspace_bytes(int32_t B, int32_t T, int32_t cutoff_top_n, int32_t beam_size, int32_t max_len,
+                                             size_t* bytes) {
+  if (!bytes || B <= 0 || T <= 0 || cutoff_top_n <= 0 || beam_size <= 0 || max_len <= 0) return fail(MI355ASR_EINVAL, "bad argument");
+  const size_t need = (size_t)B * T * std::min(cutoff_top_n, 128) * 8;
+  *bytes = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
+  return 0;
+}
+// ---- stateful BeamDecoder ----------------------------------------------------------------------------------
+struct mi355asr_beam { void* st; int V, beam; };
+int mi355asr_beam_create(int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, mi355asr_beam** out) {
+  if (!out) return fail(MI355ASR_EINVAL, "null argument");
+  if (V < 2 || beam_size < 1 || cutoff_top_n < 1 || !(cutoff_prob > 0.0) || cutoff_prob > 1.0)
+    return fail(MI355ASR_EINVAL, "beam decoder: need V >= 2, beam_size >= 1, cutoff_top_n >= 1, 0 < cutoff_prob <= 1");
+  auto* d = new mi355asr_beam{mi355asr_beam_state_new(V, beam_size, cutoff_prob, cutoff_top_n), V, beam_size};
+  *out = d;
+  return 0;
+}
+int mi355asr_beam_decode(mi355asr_beam* d, const float* probs, int32_t T, int32_t max_len, int32_t* ids, int32_t* lens,
+                         float* scores, int32_t* n_hyp) {
+  if (!d || !ids || !lens || !scores || !n_hyp || (T > 0 && !probs)) return fail(MI355ASR_EINVAL, "null argument");
+  if (T < 0 || max_len < 1) return fail(MI355ASR_EINVAL, "T must be >= 0 and max_len >= 1 (got %d, %d)", T, max_len);
+  *n_hyp = mi355asr_beam_state_decode(d->st, probs, T, max_len, ids, lens, scores);
+  return 0;
+}
+int mi355asr_beam_reset(mi355asr_beam* d) {
+  if (!d) return fail(MI355ASR_EINVAL, "null argument");
+  mi355asr_beam_state_reset(d->st);
+  return 0;
+}
+int mi355asr_beam_destroy(mi355asr_beam* d) {
+  if (!d) return 0;
+  mi355asr_beam_state_free(d->st);
+  delete d;
+  return 0;
+}
+}  // extern "C"

@@ -18,18 +18,18 @@ int chunk_geometry(const mi355asr_model* m, int B, int L, ChunkGeom* g) {
   return 0;
 }
 
-struct ChunkPlan {
-  size_t xa, xb, qkv, ctx, u, dw, hid, amax, idx, cnt, logp, pmax, mel, sub, h4, total;
+struct ChunkPlan : ScratchPlan {
+  size_t hid, amax, idx, cnt, logp, pmax, mel, sub, total;
 };
 
 ChunkPlan make_chunk_plan(const mi355asr_model* m, int B, int F, int T) {
   const int d = m->cfg.dmodel;
   const size_t M = (size_t)B * T;
   ChunkPlan p;
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t at = o; o = align256(o + floats * 4); return at; };
-  p.xa = take(M * d); p.xb = take(M * d); p.qkv = take(M * 3 * d); p.ctx = take(M * d);
-  p.u = take(M * d); p.dw = take(M * d); p.hid = take(M * d);
+  Layout lay;
+  auto take = [&](size_t floats) { return lay.take(floats); };
+  lay.scratch(p, M, d);
+  p.hid = take(M * d);
   p.amax = take(M); p.idx = take(M); p.cnt = take(B);
   const int FT = ceil_div(F, 16);
   p.logp = take((size_t)B * F * m->dm.LP);
@@ -37,56 +37,9 @@ ChunkPlan make_chunk_plan(const mi355asr_model* m, int B, int F, int T) {
   p.mel = take((size_t)B * F * m->cfg.n_mels);
   p.sub = take(M * m->dm.F2 * d);
   p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;
-  p.total = o;
+  p.total = lay.o;
   return p;
 }
-
-void add_stack_expected(std::vector<Expected>& ex, const std::string& prefix, const std::string& blk, int nblocks,
-                        int d, int H, int hs, int k, bool project, int num_classes) {
-  if (project) {
-    ex.push_back({prefix + "/project/kernel", {d, d}});
-    ex.push_back({prefix + "/project/bias", {d}});
-  }
-  for (int i = 0; i < nblocks; ++i) add_block_expected(ex, prefix + "/" + blk + std::to_string(i), d, H, hs, k, true);
-  if (num_classes > 0) {
-    ex.push_back({prefix + "/fully_connected/kernel", {d, num_classes}});
-    ex.push_back({prefix + "/fully_connected/bias", {num_classes}});
-  }
-}
-
-
-StackOff pack_stack(mi355asr_model* m, ArenaBuilder& ab, const std::string& prefix, const std::string& blk, int nblocks,
-                    bool project, int V) {
-  const auto& c = m->cfg;
-  const int d = c.dmodel;
-  StackOff so;
-  if (project) {
-    const auto& pj = m->host[prefix + "/project/kernel"].data;
-    so.proj_w = ab.put(pack_p16([&](int k, int n) { return pj[(size_t)k * d + n]; }, d, d, d / 16));
-    so.proj_b = ab.put(m->host[prefix + "/project/bias"].data);
-    if (d == 144) {
-      const auto& pb = m->host[prefix + "/project/bias"].data;
-      std::vector<float> pp;
-      so.proj_pp_sw = append_pp_plain(pp, [&](int k, int n) { return k < d ? pj[(size_t)k * d + n] : pb[n]; }, 1);
-      so.proj_pp = ab.put(pp);
-    }
-  }
-  for (int i = 0; i < nblocks; ++i)
-    so.blocks.push_back(pack_block(m, ab, prefix + "/" + blk + std::to_string(i), d, c.num_heads, c.head_size,
-                                   c.kernel_size, true));
-  if (V > 0) {
-    const auto& fc = m->host[prefix + "/fully_connected/kernel"].data;
-    const int ct = gemm_ct(d, EPI_HEAD);
-    so.NT_fc = ceil_div(ceil_div(V, 16), ct) * ct;
-    so.fc_w = ab.put(pack_p16([&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V, so.NT_fc));
-    if (ring_packs_wanted(m)) put_ring_head(ab, so.fc_w, [&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V);
-    put_head_slabs(ab, so.fc_w, [&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V, m->host[prefix + "/fully_connected/bias"].data.data());
-    so.fc_b = ab.put_padded(m->host[prefix + "/fully_connected/bias"].data.data(), V, (size_t)so.NT_fc * 16);
-  }
-  return so;
-}
-
-
 
 // Dense(d->d) [+ blocks] [+ Dense(d->V) with argmax]; input rows at `in`, blocks run in sc.xa
 // On return the stack's hidden output is in sc.xa (sc is updated: the blocks ping-pong xa/xb).
@@ -124,10 +77,7 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
     if (rc) return rc;
   }
   if (st.fc_wp && (logits || amax)) {
-    GemmArgs hd{};
-    hd.x = sc.xa; hd.y = logits; hd.wp = st.fc_wp; hd.bias = st.fc_b;
-    hd.M = M; hd.NT = st.NT_fc; hd.ldy = st.num_classes; hd.n_valid = st.num_classes; hd.eps = kLnEps;
-    hd.argmax_out = amax;
+    const GemmArgs hd = head_args(st, sc.xa, M, logits, amax);
     // (the q / k / v and context buffers are dead behind the last block: the per-range arg-max pairs of a head split over class
     // ranges, and the arg-max nobody asked for)
     if (int rc = run_class_head(m, hd, HeadLayers::never, sc.qkv, nullptr, reinterpret_cast<int32_t*>(sc.ctx), s)) return rc;
@@ -135,116 +85,62 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
   return 0;
 }
 
+
+// The "valid" Melspectrogram (chunk front): the reference left-pads n_dft - 1 zeros, then a VALID strided conv; log10 only, no
+// max-normalisation (chunk_amplitude_to_decibel, backend_keras.py:25-37).  absmax: B words that receive each utterance's largest
+// |mel| when the banded mel kernel runs; set to null when it did not (the dense kernel does not produce it).
+int run_valid_mel(const mi355asr_model* m, const float* wav, int B, int L, int F, float* logp, float* pmax, float* mel,
+                  unsigned** absmax, hipStream_t s) {
+  const auto& c = m->cfg;
+  const int FT = ceil_div(F, 16);
+  if (m->fft_ok) {
+    FftStftArgs fa{wav, logp, pmax, m->fft_w1p, m->fft_w2p, m->fft_twc, m->fft_tws, m->fft_win,
+                   B, L, F, m->dm.hop, c.n_dft - 1, m->dm.LP, 0};
+    fa.w1s = m->fft_w1s; fa.w2s = m->fft_w2s; fa.w1h = m->fft_w1h; fa.w2h = m->fft_w2h;
+    PROF(MI355ASR_K_STFT);
+    LAUNCH_TRY(launch_fft_stft(fa, s), "stft (valid, fft)");
+  } else {
+    StftArgs st{};
+    st.wav = wav; st.logp = logp; st.pmax = pmax; st.wp = m->dft_wp;
+    st.B = B; st.L = L; st.F = F; st.hop = m->dm.hop; st.pad_left = c.n_dft - 1; st.n_dft = c.n_dft;
+    st.NT = m->dm.NT_dft; st.LP = m->dm.LP; st.nbins = m->dm.nbins; st.FT = FT; st.NCH = m->dm.NCH_dft;
+    st.db10 = 0;
+    PROF(MI355ASR_K_STFT);
+    LAUNCH_TRY(launch_stft(st, s), "stft (valid)");
+  }
+  MelArgs me{};
+  me.logp = logp; me.umax = nullptr; me.mel = mel; me.wp = m->mel_wp;
+  me.B = B; me.F = F; me.LP = m->dm.LP; me.nbins = m->dm.nbins; me.KBm = m->dm.KBm; me.NTm = m->dm.NTm;
+  me.NM = c.n_mels; me.FT = FT; me.floor_db = 0.f;
+  if (absmax && *absmax) { HIP_TRY(hipMemsetAsync(*absmax, 0, sizeof(unsigned) * (size_t)B, s)); me.absmax = *absmax; }
+  { PROF(MI355ASR_K_MEL); LAUNCH_TRY(launch_mel_auto(m, me, s), "mel (valid)"); }
+  if (absmax) *absmax = me.absmax;
+  return 0;
+}
+
 }  // namespace
 
 namespace mi355 {
 
-void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V) {
-  sd.blocks.clear();
-  for (const auto& o : so.blocks) sd.blocks.push_back(resolve(o, base));
-  if (project) { sd.proj_wp = base + so.proj_w; sd.proj_b = base + so.proj_b; }
-  sd.proj_pp = (project && so.proj_pp) ? base + so.proj_pp : nullptr;
-  sd.proj_pp_sw = so.proj_pp_sw;
-  if (V > 0) { sd.fc_wp = base + so.fc_w; sd.fc_b = base + so.fc_b; sd.NT_fc = so.NT_fc; sd.num_classes = V; }
-}
-
 int finalize_chunk(mi355asr_model* m, hipStream_t s) {
-  const auto& c = m->cfg;
   const auto& cc = m->ccfg;
-  const Dims& dm = m->dm;
-  const int d = c.dmodel, nb = dm.nbins;
   ArenaBuilder ab;
   ab.ring_terms = m->cfg.gemm_dtype == 1 ? 1 : 3;
-  const auto& re = m->host["front/mel_layer/real_kernels"].data;
-  const auto& im = m->host["front/mel_layer/imag_kernels"].data;
-  const size_t o_dft = ab.put(pack_p16(
-      [&](int k, int n) { const int bin = n >> 1; return (n & 1) ? im[(size_t)k * nb + bin] : re[(size_t)k * nb + bin]; },
-      c.n_dft, 2 * nb, dm.NT_dft));
-  const FftOff fo = pack_fft(ab, re, im, c.n_dft, nb);
-  const auto& f2m = m->host["front/mel_layer/freq2mel"].data;
-  const size_t o_mel = ab.put(pack_p16([&](int k, int n) { return k < nb ? f2m[(size_t)k * c.n_mels + n] : 0.f; },
-                                       dm.KBm * 16, c.n_mels, dm.NTm));
-  const MelBandOff mbo = pack_mel_band(ab, f2m, nb, c.n_mels);
-  const size_t o_c1w = ab.put(m->host["front/conv_subsampling/conv1/kernel"].data);
-  const size_t o_c1b = ab.put(m->host["front/conv_subsampling/conv1/bias"].data);
-  const auto& c2 = m->host["front/conv_subsampling/conv2/kernel"].data;
-  const size_t o_c2w = ab.put(pack_p16(
-      [&](int kp, int n) {
-        const int kb = kp / 16, r = kp % 16, cb = kb / 9, q = kb % 9;
-        return c2[((size_t)q * d + (16 * cb + r)) * d + n];
-      },
-      9 * d, d, d / 16));
-  const size_t o_c2b = ab.put(m->host["front/conv_subsampling/conv2/bias"].data);
-  const auto& lin = m->host["front/conv_subsampling/linear/kernel"].data;
-  const size_t o_lw = ab.put(pack_p16([&](int k, int n) { return lin[(size_t)k * d + n]; }, dm.F2 * d, d, d / 16));
-  const size_t o_lb = ab.put(m->host["front/conv_subsampling/linear/bias"].data);
   // round 3: the front runs the split-bf16 subsampling kernels of the offline encoder (the explicit front padding and the
-  // VALID geometry are index offsets of the same kernels: subconv.hip reads pt1 / pf1 / pt2 / pf2 / T1 / F1 from its arguments)
-  const bool split_front = d == 144 && c.gemm_dtype == 0;
-  const size_t o_c2s = split_front ? ab.put(pack_conv2_split(c2, d)) : 0;
-  const size_t o_lws = split_front && (dm.F2 * d) % 32 == 0 ? ab.put(pack_linear_split(lin, dm.F2 * d, d)) : 0;
-  // round 4: the two-term fp16 forms -- conv2 as hi + lo of kernel * 2^k (its operand scale comes from the batch's largest |mel|
-  // at run time: the valid frontend's log10 features have no static bound), the Dense as the stream of pp_sublinear_kernel
-  size_t o_c2h = 0, o_lpp = 0;
-  float c2_ws = 0.f, c1_l1 = 0.f, c1_bmax = 0.f, c1_ws = 0.f, lin_pp_sw = 1.f;
-  if (split_front) {
-    const auto& w1 = m->host["front/conv_subsampling/conv1/kernel"].data;
-    const auto& b1 = m->host["front/conv_subsampling/conv1/bias"].data;
-    double wmax = 0.0, l1max = 0.0, bmax = 0.0;
-    for (int ch = 0; ch < d; ++ch) {
-      double sum = 0.0;
-      for (int t = 0; t < 9; ++t) sum += std::fabs((double)w1[(size_t)t * d + ch]);
-      l1max = std::max(l1max, sum);
-      bmax = std::max(bmax, std::fabs((double)b1[ch]));
-    }
-    for (float v : c2) wmax = std::max(wmax, std::fabs((double)v));
-    c2_ws = half_scale_for(wmax);
-    if (c2_ws > 0.f && l1max > 0.0) {
-      o_c2h = ab.put(pack_conv2_half(c2, d, c2_ws));
-      c1_l1 = (float)(l1max * (1.0 + 1e-6));
-      c1_bmax = (float)(bmax * (1.0 + 1e-6));
-      double w1max = 0.0;                          // conv1 on the matrix pipe (subconv.hip, C1M): the mel scale is taken at run time
-      for (float v : w1) w1max = std::max(w1max, std::fabs((double)v));
-      c1_ws = half_scale_for(w1max);
-    }
-    if (o_lws) {
-      const auto& lb = m->host["front/conv_subsampling/linear/bias"].data;
-      std::vector<float> pp;
-      lin_pp_sw = append_pp_plain(pp, [&](int k, int n) {
-        const int f = n / d, col = n - f * d;
-        return k < d ? lin[((size_t)f * d + k) * d + col] : (f == 0 ? lb[col] : 0.f);
-      }, dm.F2);
-      o_lpp = ab.put(pp);
-    }
-  }
-  StackOff e = pack_stack(m, ab, "encoder", "chunk_conformer_block_", cc.enc_num_blocks, false, 0);
-  StackOff pk = pack_stack(m, ab, "picker", "block_", cc.picker_num_blocks, true, cc.picker_num_classes);
-  StackOff hp = pack_stack(m, ab, "helper", "block_", cc.helper_num_blocks, false, 0);
-  StackOff dc = pack_stack(m, ab, "decoder", "block_", cc.decoder_num_blocks, true, cc.decoder_num_classes);
-  if (m->arena) { (void)hipFree(m->arena); m->arena = nullptr; }
-  HIP_TRY(hipMalloc((void**)&m->arena, ab.buf.size() * sizeof(float)));
-  m->arena_floats = ab.buf.size();
-  HIP_TRY(hipMemcpyAsync(m->arena, ab.buf.data(), ab.buf.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  // VALID geometry are index offsets of the same kernels: subconv.hip reads pt1 / pf1 / pt2 / pf2 / T1 / F1 from its arguments);
+  // round 4: and their two-term fp16 forms, conv2's operand scale coming from each utterance's largest |mel| at run time
+  const FrontOff fo = pack_front(m, ab, "front/", kNoMelBound);
+  const StackOff e = pack_stack(m, ab, "encoder/", "chunk_conformer_block_", cc.enc_num_blocks, false, 0, true);
+  const StackOff pk = pack_stack(m, ab, "picker/", "block_", cc.picker_num_blocks, true, cc.picker_num_classes, true);
+  const StackOff hp = pack_stack(m, ab, "helper/", "block_", cc.helper_num_blocks, false, 0, true);
+  const StackOff dc = pack_stack(m, ab, "decoder/", "block_", cc.decoder_num_blocks, true, cc.decoder_num_classes, true);
+  if (int rc = upload_arena(m, ab, s)) return rc;
   const float* base = m->arena;
-  m->ring_of.clear();
-  register_rings(m, ab, base);
-  m->dft_wp = base + o_dft; m->mel_wp = base + o_mel;
-  m->fft_ok = fo.ok;
-  use_mel_band(m, mbo, base);
-  m->fft_w1p = base + fo.w1; m->fft_w2p = base + fo.w2; m->fft_twc = base + fo.twc; m->fft_tws = base + fo.tws;
-  m->fft_w1s = base + fo.w1s; m->fft_w2s = base + fo.w2s; m->fft_w1h = base + fo.w1h; m->fft_w2h = base + fo.w2h;
-  m->fft_win = base + fo.win;
-  m->c1_w = base + o_c1w; m->c1_b = base + o_c1b; m->c2_wp = base + o_c2w; m->c2_b = base + o_c2b;
-  m->lin_wp = base + o_lw; m->lin_b = base + o_lb;
-  m->c2_wsplit = o_c2s ? base + o_c2s : nullptr;
-  m->lin_wsplit = o_lws ? base + o_lws : nullptr;
-  m->c2_whalf = o_c2h ? base + o_c2h : nullptr; m->c2_wscale = c2_ws; m->c1_l1 = c1_l1; m->c1_bmax = c1_bmax; m->c1_wscale = c1_ws;
-  m->lin_pp = o_lpp ? base + o_lpp : nullptr; m->lin_pp_sw = lin_pp_sw;
-  resolve_stack(m->c_enc, e, base, false, 0);
-  resolve_stack(m->c_picker, pk, base, true, cc.picker_num_classes);
-  resolve_stack(m->c_helper, hp, base, false, 0);
-  resolve_stack(m->c_decoder, dc, base, true, cc.decoder_num_classes);
+  resolve_front(m, fo, base);
+  resolve_stack(m->c_enc, e, base);
+  resolve_stack(m->c_picker, pk, base);
+  resolve_stack(m->c_helper, hp, base);
+  resolve_stack(m->c_decoder, dc, base);
   m->finalized = true;
   return 0;
 }
@@ -257,23 +153,23 @@ namespace {
 // 381-388, 447-458, 530-560, 641-672, 750-770).  The caller owns the caches and trims them (valid / window
 // slicing is plain indexing, done in tensorflowasr_amd/models.py as the reference does it in Python).
 // =======================================================================================================
-struct StreamPlan {
-  size_t xa, xb, qkv, ctx, u, dw, amax, logp, pmax, mel, sub, total;
+struct StreamPlan : ScratchPlan {
+  size_t amax, logp, pmax, mel, sub, total;
 };
 // N = longest [cache ; new] row count of any module, F = mel frames of the wav buffer, Fs = rows of [sub cache ; mel]
 StreamPlan make_stream_plan(const mi355asr_model* m, int N, int F, int Fs) {
   const size_t d = m->cfg.dmodel;
   StreamPlan p;
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t at = o; o = align256(o + floats * 4); return at; };
-  p.xa = take(N * d); p.xb = take(N * d); p.qkv = take((size_t)N * 3 * d); p.ctx = take(N * d);
-  p.u = take(N * d); p.dw = take(N * d); p.amax = take(N);
+  Layout lay;
+  auto take = [&](size_t floats) { return lay.take(floats); };
+  lay.scratch(p, N, d);
+  p.amax = take(N);
   const int FT = ceil_div(std::max(F, 1), 16);
   p.logp = take((size_t)std::max(F, 1) * m->dm.LP);
   p.pmax = take((size_t)std::max(FT * m->dm.NCH_dft, F));
   p.mel = take((size_t)std::max(F, 1) * m->cfg.n_mels);
   p.sub = take((size_t)std::max(Fs, 1) * m->dm.F2 * d);
-  p.total = o;
+  p.total = lay.o;
   return p;
 }
 
@@ -403,10 +299,10 @@ int mi355asr_chunk_create(const mi355asr_chunk_config* cfg, mi355asr_model** out
   ex.push_back({"front/conv_subsampling/conv2/bias", {d}});
   ex.push_back({"front/conv_subsampling/linear/kernel", {dm.F2 * d, d}});
   ex.push_back({"front/conv_subsampling/linear/bias", {d}});
-  add_stack_expected(ex, "encoder", "chunk_conformer_block_", c.enc_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, false, 0);
-  add_stack_expected(ex, "picker", "block_", c.picker_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, true, c.picker_num_classes);
-  add_stack_expected(ex, "helper", "block_", c.helper_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, false, 0);
-  add_stack_expected(ex, "decoder", "block_", c.decoder_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, true, c.decoder_num_classes);
+  add_stack_expected(ex, "encoder/", "chunk_conformer_block_", c.enc_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, false, 0, true);
+  add_stack_expected(ex, "picker/", "block_", c.picker_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, true, c.picker_num_classes, true);
+  add_stack_expected(ex, "helper/", "block_", c.helper_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, false, 0, true);
+  add_stack_expected(ex, "decoder/", "block_", c.decoder_num_blocks, d, c.num_heads, c.head_size, c.kernel_size, true, c.decoder_num_classes, true);
   auto opts = [&](int wf, int wb) { BlockOpts o; o.ksz = c.kernel_size; o.fc = c.fc_factor; o.win_front = wf; o.win_back = wb; o.causal = true; return o; };
   m->c_enc.opts = opts(c.enc_win_front, c.enc_win_back);
   m->c_picker.opts = opts(c.picker_win_front, c.picker_win_back);
@@ -450,44 +346,22 @@ int mi355asr_chunk_predict(mi355asr_model* m, const float* wav, int32_t B, int32
   const auto& c = m->cfg;
   const int d = c.dmodel, T = g.T;
   const size_t act = (size_t)B * T * d * 4;
-  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
-             (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
-  sc.h4 = (float*)(ws + p.h4);
+  Scratch sc = make_scratch(p, ws);
   BlockOpts enc_front;
   bool dense_deferred = false;
-  // ---- front: valid Melspectrogram (log10, no max-normalisation) + left-padded VALID ConvSubsampling
+  // ---- front: valid Melspectrogram + left-padded VALID ConvSubsampling
   {
-    const int FT = ceil_div(g.F, 16);
-    StftArgs st{};
-    st.wav = wav; st.logp = (float*)(ws + p.logp); st.pmax = (float*)(ws + p.pmax); st.wp = m->dft_wp;
-    st.B = B; st.L = L; st.F = g.F; st.hop = m->dm.hop; st.pad_left = c.n_dft - 1; st.n_dft = c.n_dft;
-    st.NT = m->dm.NT_dft; st.LP = m->dm.LP; st.nbins = m->dm.nbins; st.FT = FT; st.NCH = m->dm.NCH_dft;
-    st.db10 = 0;                                    // chunk_amplitude_to_decibel: log10 only (backend_keras.py:25-37)
-    if (m->fft_ok) {
-      FftStftArgs fa{wav, st.logp, st.pmax, m->fft_w1p, m->fft_w2p, m->fft_twc, m->fft_tws, m->fft_win,
-                     B, L, g.F, m->dm.hop, c.n_dft - 1, m->dm.LP, 0};
-    fa.w1s = m->fft_w1s; fa.w2s = m->fft_w2s; fa.w1h = m->fft_w1h; fa.w2h = m->fft_w2h;
-      PROF(MI355ASR_K_STFT);
-      LAUNCH_TRY(launch_fft_stft(fa, s), "stft (valid, fft)");
-    } else {
-      PROF(MI355ASR_K_STFT);
-      LAUNCH_TRY(launch_stft(st, s), "stft (valid)");
-    }
-    MelArgs me{};
-    me.logp = st.logp; me.umax = nullptr; me.mel = (float*)(ws + p.mel); me.wp = m->mel_wp;
-    me.B = B; me.F = g.F; me.LP = m->dm.LP; me.nbins = m->dm.nbins; me.KBm = m->dm.KBm; me.NTm = m->dm.NTm;
-    me.NM = c.n_mels; me.FT = FT; me.floor_db = 0.f;
+    float* mel = (float*)(ws + p.mel);
     // round 4: the valid frontend's log10 features have no static bound; the banded mel kernel leaves each utterance's largest
     // |mel| in the first B words of the (by now consumed) per-frame maxima, and the two-term subsampling conv scales by it
     // (round 5: per utterance, not per batch -- a quiet utterance next to a loud one keeps its own 2^-22, and B = 1 == B = N)
     unsigned* melmax = (m->mel_band && m->c2_whalf && m->c1_l1 > 0.f) ? (unsigned*)(ws + p.pmax) : nullptr;
-    if (melmax) { HIP_TRY(hipMemsetAsync(melmax, 0, sizeof(unsigned) * (size_t)B, s)); me.absmax = melmax; }
-    { PROF(MI355ASR_K_MEL); LAUNCH_TRY(launch_mel_auto(m, me, s), "mel (valid)"); }
+    if ((rc = run_valid_mel(m, wav, B, L, g.F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, &melmax, s))) return rc;
     SubConvArgs sa{};
-    sa.mel = me.mel; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+    sa.mel = mel; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
     sa.w2s = m->c2_wsplit;
     static const bool three = mi355_env("MI355ASR_SUBCONV_TERMS", -1) == 3;
-    if (melmax && me.absmax && !three) { sa.w2h = m->c2_whalf; sa.h_wscale = m->c2_wscale; sa.h_melmax = melmax; sa.h_l1 = m->c1_l1; sa.h_bmax = m->c1_bmax; sa.c1_wscale = m->c1_wscale; }
+    if (melmax && !three) { sa.w2h = m->c2_whalf; sa.h_wscale = m->c2_wscale; sa.h_melmax = melmax; sa.h_l1 = m->c1_l1; sa.h_bmax = m->c1_bmax; sa.c1_wscale = m->c1_wscale; }
     sa.B = B; sa.F = g.F; sa.NM = c.n_mels; sa.T1 = g.T1; sa.F1 = m->dm.F1; sa.T2 = T; sa.F2 = m->dm.F2;
     sa.st1 = 2; sa.pt1 = 4; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
     { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (valid)"); }
@@ -626,29 +500,8 @@ int mi355asr_chunk_front_stream(mi355asr_model* m, const float* wav, int32_t Lw,
   char* ws = (char*)ws_;
   hipStream_t s = (hipStream_t)stream;
   // valid Melspectrogram of the whole buffer (each call left-pads n_dft-1 zeros, as the layer does), last nf frames
-  const int FT = ceil_div(F, 16);
-  float* logp = (float*)(ws + p.logp);
   float* mel = (float*)(ws + p.mel);
-  if (m->fft_ok) {
-    FftStftArgs fa{wav, logp, (float*)(ws + p.pmax), m->fft_w1p, m->fft_w2p, m->fft_twc, m->fft_tws, m->fft_win,
-                   1, Lw, F, m->dm.hop, c.n_dft - 1, m->dm.LP, 0};
-    fa.w1s = m->fft_w1s; fa.w2s = m->fft_w2s; fa.w1h = m->fft_w1h; fa.w2h = m->fft_w2h;
-    PROF(MI355ASR_K_STFT);
-    LAUNCH_TRY(launch_fft_stft(fa, s), "stft (valid, fft)");
-  } else {
-    StftArgs st{};
-    st.wav = wav; st.logp = logp; st.pmax = (float*)(ws + p.pmax); st.wp = m->dft_wp;
-    st.B = 1; st.L = Lw; st.F = F; st.hop = m->dm.hop; st.pad_left = c.n_dft - 1; st.n_dft = c.n_dft;
-    st.NT = m->dm.NT_dft; st.LP = m->dm.LP; st.nbins = m->dm.nbins; st.FT = FT; st.NCH = m->dm.NCH_dft;
-    st.db10 = 0;
-    PROF(MI355ASR_K_STFT);
-    LAUNCH_TRY(launch_stft(st, s), "stft (valid)");
-  }
-  MelArgs me{};
-  me.logp = logp; me.umax = nullptr; me.mel = mel; me.wp = m->mel_wp;
-  me.B = 1; me.F = F; me.LP = m->dm.LP; me.nbins = m->dm.nbins; me.KBm = m->dm.KBm; me.NTm = m->dm.NTm;
-  me.NM = c.n_mels; me.FT = FT; me.floor_db = 0.f;
-  { PROF(MI355ASR_K_MEL); LAUNCH_TRY(launch_mel_auto(m, me, s), "mel (valid)"); }
+  if (int rc = run_valid_mel(m, wav, 1, Lw, F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, nullptr, s)) return rc;
   // new_sub = [sub cache ; last nf mel frames]  (ConvSubsampling.stream_call :75)
   const size_t mrow = (size_t)c.n_mels * 4;
   if (S > 0) HIP_TRY(hipMemcpyAsync(new_sub, sub_cache, S * mrow, hipMemcpyDeviceToDevice, s));
@@ -686,8 +539,7 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
   if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
   char* ws = (char*)ws_;
   hipStream_t s = (hipStream_t)stream;
-  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
-             (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
+  Scratch sc = make_scratch(p, ws);
   if (st->proj_wp) {
     GemmArgs pr{};
     pr.x = x; pr.y = sc.xa; pr.wp = st->proj_wp; pr.bias = st->proj_b;
@@ -705,10 +557,7 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
   }
   HIP_TRY(hipMemcpyAsync(hidden, sc.xa, (size_t)T * d * 4, hipMemcpyDeviceToDevice, s));
   if (st->fc_wp && (logits || amax)) {
-    GemmArgs hd{};
-    hd.x = sc.xa; hd.y = logits; hd.wp = st->fc_wp; hd.bias = st->fc_b;
-    hd.M = T; hd.NT = st->NT_fc; hd.ldy = st->num_classes; hd.n_valid = st->num_classes; hd.eps = kLnEps;
-    hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
+    GemmArgs hd = head_args(*st, sc.xa, T, logits, amax ? amax : (int32_t*)(ws + p.amax));
     { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "fully_connected"); }
   }
   return 0;

@@ -1,5 +1,4 @@
-// Translator host side (conformer_blocks.py:439-566) and the stateful beam decoder handle, behind
-// mi355asr_translator_* / mi355asr_beam_* of include/mi355asr.h.
+// Translator host side (conformer_blocks.py:439-566), behind mi355asr_translator_* of include/mi355asr.h.
 #include "model.h"
 
 namespace {
@@ -8,19 +7,19 @@ namespace {
 // =======================================================================================================
 constexpr int kMaxTokens = 2048;   // rows of the positional-encoding table
 
-struct TransPlan {
-  size_t xa, xb, qkv, ctx, u, dw, kv, amax, h4, hsplit, total;
+struct TransPlan : ScratchPlan {
+  size_t kv, amax, hsplit, total;
 };
 TransPlan make_trans_plan(const mi355asr_model* m, int B, int U, int T) {
   const size_t d = m->cfg.dmodel, M = (size_t)B * U;
   TransPlan p;
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t at = o; o = align256(o + floats * 4); return at; };
-  p.xa = take(M * d); p.xb = take(M * d); p.qkv = take(M * 3 * d); p.ctx = take(M * d);
-  p.u = take(M * d); p.dw = take(M * d); p.kv = take((size_t)B * T * 2 * d); p.amax = take(M);
+  Layout lay;
+  auto take = [&](size_t floats) { return lay.take(floats); };
+  lay.scratch(p, M, d);
+  p.kv = take((size_t)B * T * 2 * d); p.amax = take(M);
   p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;
   p.hsplit = take(16 * M);          // per-range (maximum, class) pairs of the class head split over column ranges (up to 8)
-  p.total = o;
+  p.total = lay.o;
   return p;
 }
 
@@ -31,7 +30,7 @@ namespace mi355 {
 int finalize_translator(mi355asr_model* m, hipStream_t s) {
   const auto& c = m->cfg;
   const auto& tc = m->tcfg;
-  const int d = c.dmodel, H = c.num_heads, hs = c.head_size, V = tc.tar_classes;
+  const int d = c.dmodel, hs = c.head_size, V = tc.tar_classes;
   ArenaBuilder ab;
   ab.ring_terms = m->cfg.gemm_dtype == 1 ? 1 : 3;
   const size_t o_emb = ab.put(m->host["inp_embedding/embeddings"].data);
@@ -46,7 +45,7 @@ int finalize_translator(mi355asr_model* m, hipStream_t s) {
   StackOff so;
   for (int i = 0; i < tc.num_blocks; ++i) {
     const std::string p = "decoder_conformer_block_" + std::to_string(i);
-    BlockOff o = pack_block(m, ab, p, d, H, hs, c.kernel_size);
+    BlockOff o = pack_block(m, ab, p, d, hs);
     const auto& qk = m->host[p + "/mhsa_module/mha/query_kernel"].data;   // [H, d, hs]
     const auto& kk = m->host[p + "/mhsa_module/mha/key_kernel"].data;
     const auto& vk = m->host[p + "/mhsa_module/mha/value_kernel"].data;
@@ -61,24 +60,12 @@ int finalize_translator(mi355asr_model* m, hipStream_t s) {
         d, 2 * d, 2 * d / 16));
     so.blocks.push_back(o);
   }
-  const auto& fc = m->host["fully_connected/kernel"].data;
-  const int ct = gemm_ct(d, EPI_HEAD);
-  so.NT_fc = ceil_div(ceil_div(V, 16), ct) * ct;
-  so.fc_w = ab.put(pack_p16([&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V, so.NT_fc));
-  if (ring_packs_wanted(m)) put_ring_head(ab, so.fc_w, [&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V);
-  put_head_slabs(ab, so.fc_w, [&](int k, int n) { return fc[(size_t)k * V + n]; }, d, V, m->host["fully_connected/bias"].data.data());
-  so.fc_b = ab.put_padded(m->host["fully_connected/bias"].data.data(), V, (size_t)so.NT_fc * 16);
-  if (m->arena) { (void)hipFree(m->arena); m->arena = nullptr; }
-  HIP_TRY(hipMalloc((void**)&m->arena, ab.buf.size() * sizeof(float)));
-  m->arena_floats = ab.buf.size();
-  HIP_TRY(hipMemcpyAsync(m->arena, ab.buf.data(), ab.buf.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  pack_head(m, ab, so, m->host["fully_connected/kernel"].data, m->host["fully_connected/bias"].data, V);
+  if (int rc = upload_arena(m, ab, s)) return rc;
   const float* base = m->arena;
-  m->ring_of.clear();
-  register_rings(m, ab, base);
   m->t_emb = base + o_emb;
   m->t_pe = base + o_pe;
-  resolve_stack(m->t_stack, so, base, false, V);
+  resolve_stack(m->t_stack, so, base);
   m->t_stack.opts.ksz = c.kernel_size;
   m->t_stack.opts.fc = c.fc_factor;
   for (auto& kv : m->host) { kv.second.data.clear(); kv.second.data.shrink_to_fit(); }
@@ -125,109 +112,60 @@ int mi355asr_translator_workspace_bytes(const mi355asr_model* m, int32_t B, int3
   return 0;
 }
 
-int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids, const float* enc, int32_t B, int32_t U,
-                                int32_t T, float* logits, int32_t* amax, void* ws_, size_t ws_bytes, void* stream) {
-  if (!m || !m->is_translator) return fail(MI355ASR_EINVAL, "not a Translator handle");
-  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
-  if (!ids || !enc || !ws_) return fail(MI355ASR_EINVAL, "null argument");
-  if (B < 1 || U < 1 || T < 1) return fail(MI355ASR_EINVAL, "B, U, T must be positive (got %d, %d, %d)", B, U, T);
-  if (U > kMaxTokens) return fail(MI355ASR_EINVAL, "U=%d exceeds the positional-encoding table (%d rows)", U, kMaxTokens);
-  const TransPlan p = make_trans_plan(m, B, U, T);
-  if (ws_bytes < p.total) return fail(MI355ASR_EINVAL, "workspace too small: %zu < %zu", ws_bytes, p.total);
-  char* ws = (char*)ws_;
-  hipStream_t s = (hipStream_t)stream;
-  const int d = m->cfg.dmodel, M = B * U;
-  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
-             (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
-  sc.h4 = (float*)(ws + p.h4);
-  EmbedArgs ea{ids, m->t_emb, sc.xa, M, m->tcfg.inp_classes, d};
-  LAUNCH_TRY(launch_embed(ea, s), "embedding");
-  CrossAttn cr{enc, T, (float*)(ws + p.kv), m->t_pe};
-  for (const auto& blk : m->t_stack.blocks) {
-    int rc = run_block(m, blk, m->t_stack.opts, sc, B, U, nullptr, s, &cr);
-    if (rc) return rc;
-  }
-  GemmArgs hd{};
-  hd.x = sc.xa; hd.y = logits; hd.wp = m->t_stack.fc_wp; hd.bias = m->t_stack.fc_b;
-  hd.M = M; hd.NT = m->t_stack.NT_fc; hd.ldy = m->tcfg.tar_classes; hd.n_valid = m->tcfg.tar_classes; hd.eps = kLnEps;
-  hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
-  // round 5: from 2048 rows on the class head runs on the two-term stream of pp_head_kernel (or the slab ring), as the CTC decoder's
-  // and the ChunkConformer's heads do (144 -> 9160 over 5952 rows: 0.44 ms on the fp32 MFMA kernel)
-  float* hsplit = (float*)(ws + p.hsplit);
-  return run_class_head(m, hd, HeadLayers::after_streams, hsplit, hsplit, hd.argmax_out, s);
-}
+}  // extern "C"
 
-// ragged batches: token lengths tok_len [B] (rows of ids) and encoder lengths enc_len [B] (frames of enc), both on the device
-int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, const int32_t* tok_len, const float* enc,
-                                       const int32_t* enc_len, int32_t B, int32_t U, int32_t T, float* logits, int32_t* amax,
-                                       void* ws_, size_t ws_bytes, void* stream) {
+// One body for mi355asr_translator_forward and its ragged form.  ragged: token lengths tok_len [B] (rows of ids) and encoder
+// lengths enc_len [B] (frames of enc), both on the device
+static int translator_forward(mi355asr_model* m, const int32_t* ids, bool ragged, const int32_t* tok_len, const float* enc,
+                              const int32_t* enc_len, int32_t B, int32_t U, int32_t T, float* logits, int32_t* amax,
+                              void* ws_, size_t ws_bytes, hipStream_t s) {
   if (!m || !m->is_translator) return fail(MI355ASR_EINVAL, "not a Translator handle");
   if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
   int rc = 0;
-  if (m->cfg.dmodel != 144 && (rc = ragged_layers256_ok(m, m->tcfg.kernel_size))) return rc;
+  if (ragged && m->cfg.dmodel != 144 && (rc = ragged_layers256_ok(m, m->tcfg.kernel_size))) return rc;
   if (!ids || !enc || !ws_) return fail(MI355ASR_EINVAL, "null argument");
   if (B < 1 || U < 1 || T < 1) return fail(MI355ASR_EINVAL, "B, U, T must be positive (got %d, %d, %d)", B, U, T);
   if (U > kMaxTokens) return fail(MI355ASR_EINVAL, "U=%d exceeds the positional-encoding table (%d rows)", U, kMaxTokens);
-  if ((rc = ragged_rows_ok(U, "U")) || (rc = ragged_rows_ok(T, "T"))) return rc;
+  if (ragged && ((rc = ragged_rows_ok(U, "U")) || (rc = ragged_rows_ok(T, "T")))) return rc;
   const TransPlan p = make_trans_plan(m, B, U, T);
   if (ws_bytes < p.total) return fail(MI355ASR_EINVAL, "workspace too small: %zu < %zu", ws_bytes, p.total);
-  hipStream_t s = (hipStream_t)stream;
   std::vector<int32_t> tok_host, enc_host;
-  if ((rc = ragged_check_lengths(tok_len, B, U, "tok_len", s, &tok_host))) return rc;
-  if ((rc = ragged_check_lengths(enc_len, B, T, "enc_len", s, &enc_host))) return rc;
+  if (ragged && (rc = ragged_check_lengths(tok_len, B, U, "tok_len", s, &tok_host))) return rc;
+  if (ragged && (rc = ragged_check_lengths(enc_len, B, T, "enc_len", s, &enc_host))) return rc;
   char* ws = (char*)ws_;
   const int d = m->cfg.dmodel, M = B * U;
-  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv),
-             (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
-  sc.h4 = (float*)(ws + p.h4);
+  Scratch sc = make_scratch(p, ws);
   EmbedArgs ea{ids, m->t_emb, sc.xa, M, m->tcfg.inp_classes, d};
   LAUNCH_TRY(launch_embed(ea, s), "embedding");
   CrossAttn cr{enc, T, (float*)(ws + p.kv), m->t_pe};
-  cr.k_len = enc_len;
-  cr.k_len_host = enc_host.data();
   BlockOpts bo = m->t_stack.opts;
-  bo.t_len_host = tok_host.data();
-  bo.t_len = tok_len;                   // the ConvModule's depthwise conv reads zeros from token row tok_len[b] on
+  if (ragged) {
+    cr.k_len = enc_len;
+    cr.k_len_host = enc_host.data();
+    bo.t_len_host = tok_host.data();
+    bo.t_len = tok_len;                   // the ConvModule's depthwise conv reads zeros from token row tok_len[b] on
+  }
   for (const auto& blk : m->t_stack.blocks)
     if ((rc = run_block(m, blk, bo, sc, B, U, nullptr, s, &cr))) return rc;
-  // the class head is row-wise: the same kernels as mi355asr_translator_forward, then the rows past tok_len[b] get their values
-  GemmArgs hd{};
-  hd.x = sc.xa; hd.y = logits; hd.wp = m->t_stack.fc_wp; hd.bias = m->t_stack.fc_b;
-  hd.M = M; hd.NT = m->t_stack.NT_fc; hd.ldy = m->tcfg.tar_classes; hd.n_valid = m->tcfg.tar_classes; hd.eps = kLnEps;
-  hd.argmax_out = amax ? amax : (int32_t*)(ws + p.amax);
+  const GemmArgs hd = head_args(m->t_stack, sc.xa, M, logits, amax ? amax : (int32_t*)(ws + p.amax));
+  // round 5: from 2048 rows on the class head runs on the two-term stream of pp_head_kernel (or the slab ring), as the CTC decoder's
+  // and the ChunkConformer's heads do (144 -> 9160 over 5952 rows: 0.44 ms on the fp32 MFMA kernel)
   float* hsplit = (float*)(ws + p.hsplit);
   if ((rc = run_class_head(m, hd, HeadLayers::after_streams, hsplit, hsplit, hd.argmax_out, s))) return rc;
+  // the class head is row-wise: the rows past tok_len[b] get their values afterwards
   const int V = m->tcfg.tar_classes;
-  LAUNCH_TRY(launch_ragged_rows(tok_len, B, U, logits, V, V, hd.argmax_out, s), "ragged Translator rows");
+  if (ragged) LAUNCH_TRY(launch_ragged_rows(tok_len, B, U, logits, V, V, hd.argmax_out, s), "ragged Translator rows");
   return 0;
 }
 
-// ---- stateful BeamDecoder ----------------------------------------------------------------------------------
-struct mi355asr_beam { void* st; int V, beam; };
-int mi355asr_beam_create(int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, mi355asr_beam** out) {
-  if (!out) return fail(MI355ASR_EINVAL, "null argument");
-  if (V < 2 || beam_size < 1 || cutoff_top_n < 1 || !(cutoff_prob > 0.0) || cutoff_prob > 1.0)
-    return fail(MI355ASR_EINVAL, "beam decoder: need V >= 2, beam_size >= 1, cutoff_top_n >= 1, 0 < cutoff_prob <= 1");
-  auto* d = new mi355asr_beam{mi355asr_beam_state_new(V, beam_size, cutoff_prob, cutoff_top_n), V, beam_size};
-  *out = d;
-  return 0;
+extern "C" {
+int mi355asr_translator_forward(mi355asr_model* m, const int32_t* ids, const float* enc, int32_t B, int32_t U,
+                                int32_t T, float* logits, int32_t* amax, void* ws, size_t ws_bytes, void* stream) {
+  return translator_forward(m, ids, false, nullptr, enc, nullptr, B, U, T, logits, amax, ws, ws_bytes, (hipStream_t)stream);
 }
-int mi355asr_beam_decode(mi355asr_beam* d, const float* probs, int32_t T, int32_t max_len, int32_t* ids, int32_t* lens,
-                         float* scores, int32_t* n_hyp) {
-  if (!d || !ids || !lens || !scores || !n_hyp || (T > 0 && !probs)) return fail(MI355ASR_EINVAL, "null argument");
-  if (T < 0 || max_len < 1) return fail(MI355ASR_EINVAL, "T must be >= 0 and max_len >= 1 (got %d, %d)", T, max_len);
-  *n_hyp = mi355asr_beam_state_decode(d->st, probs, T, max_len, ids, lens, scores);
-  return 0;
-}
-int mi355asr_beam_reset(mi355asr_beam* d) {
-  if (!d) return fail(MI355ASR_EINVAL, "null argument");
-  mi355asr_beam_state_reset(d->st);
-  return 0;
-}
-int mi355asr_beam_destroy(mi355asr_beam* d) {
-  if (!d) return 0;
-  mi355asr_beam_state_free(d->st);
-  delete d;
-  return 0;
+int mi355asr_translator_forward_ragged(mi355asr_model* m, const int32_t* ids, const int32_t* tok_len, const float* enc,
+                                       const int32_t* enc_len, int32_t B, int32_t U, int32_t T, float* logits, int32_t* amax,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  return translator_forward(m, ids, true, tok_len, enc, enc_len, B, U, T, logits, amax, ws, ws_bytes, (hipStream_t)stream);
 }
 }  // extern "C"

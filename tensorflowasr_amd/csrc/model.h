@@ -1,4 +1,5 @@
-// Internal host-side model definitions shared by api.hip, api_chunk.hip and api_translator.hip.
+// Internal host-side model definitions shared by the host files: weights.hip, api.hip, api_beam.hip, api_chunk.hip,
+// api_translator.hip, block_path.hip (and the handle kinds of vad.hip / stream_hist.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,6 +108,7 @@ struct BlockOpts {
   const int32_t* t_len_host = nullptr;   // ... its host copy, where the entry point has read it back (head size 64: attn64_class)
 };
 
+// Dense(d -> d) [+ blocks] [+ class head]: the CTC decoder, the four ChunkConformer stacks, the Translator
 struct StackDev {
   std::vector<BlockDev> blocks;
   const float *proj_wp = nullptr, *proj_b = nullptr, *fc_wp = nullptr, *fc_b = nullptr;
@@ -139,9 +141,7 @@ struct mi355asr_model {
   struct HeadStreams { const float* slabs; int groups; const float* pp; float pp_sw; const float* ns; };   // pp: two-term fp16 stream (fused_pp.hip); ns: the same fragments in plain order (fused_ns.hip)
   std::unordered_map<const float*, HeadStreams> head_of;
   const float *dft_wp = nullptr, *mel_wp = nullptr, *c1_w = nullptr, *c1_b = nullptr, *c2_wp = nullptr,
-              *c2_b = nullptr, *lin_wp = nullptr, *lin_b = nullptr, *proj_wp = nullptr, *proj_b = nullptr,
-              *fc_wp = nullptr, *fc_b = nullptr;
-  int NT_fc = 0;
+              *c2_b = nullptr, *lin_wp = nullptr, *lin_b = nullptr;
   // freq2mel as a banded matrix (mel_band_kernel) when every filter's support is narrow, else null (pack_mel_band)
   const int* mel_band = nullptr;
   const float* mel_bw = nullptr;
@@ -159,8 +159,6 @@ struct mi355asr_model {
   const float* lin_pp = nullptr;        // ... and as the two-term fp16 stream of pp_sublinear_kernel (F2 chunks of five ring slots), packed with
   float lin_pp_sw = 1.f;                // ... this power of two
   const float* lin_ns = nullptr;        // ... and the same fragments in plain order (fused_ns.hip: small batches)
-  const float* proj_pp = nullptr;       // the CTC decoder's projection [W ; b] as such a stream (one chunk), packed with
-  float proj_pp_sw = 1.f;               // ... this power of two
   const float* c2_wsplit = nullptr;     // conv2 kernel as split-bf16 fragments (subconv.hip; dmodel 144 / 256 / 512)
   const float* c2_whalf = nullptr;      // ... as two fp16 terms of kernel * c2_wscale (two-term scheme), conv1 values times c2_hscale
   float c2_hscale = 0.f, c2_wscale = 0.f;
@@ -173,7 +171,8 @@ struct mi355asr_model {
   const float *wp_dw = nullptr, *wp_pw = nullptr, *wp_b = nullptr, *wp_fw = nullptr, *wp_fb = nullptr;
   int wp_stride0 = 0;
   std::vector<WavStage> wp_stages;
-  std::vector<BlockDev> enc_blocks, ctc_blocks;
+  std::vector<BlockDev> enc_blocks;
+  StackDev ctc;                         // the CTC decoder: project + decoder blocks + fully_connected (num_classes > 0)
   // ChunkConformer (mi355asr_chunk_create): front + encoder / phone picker / context helper / text decoder stacks
   bool is_chunk = false;
   mi355asr_chunk_config ccfg;
@@ -255,7 +254,6 @@ struct MelBandOff { bool ok = false; size_t band = 0, bw = 0; int BW = 0; };
 // band form of freq2mel [nb, n_mels] for mel_band_kernel; ok = false when a filter spans more than 64 bins (a trained, dense matrix)
 MelBandOff pack_mel_band(ArenaBuilder& ab, const std::vector<float>& f2m, int nb, int n_mels);
 void use_mel_band(mi355asr_model* m, const MelBandOff& o, const float* base);
-int launch_mel_auto(const mi355asr_model* m, MelArgs& me, hipStream_t s);   // banded kernel when available, else the GEMM
 
 struct BlockOff {
   size_t ff_ln_g[2], ff_ln_b[2], ff_w1p[2], ff_b1[2], ff_w2p[2], ff_b2[2];
@@ -274,11 +272,25 @@ struct BlockOff {
   bool split = false;
 };
 
-struct Plan {
-  size_t xa, xb, qkv, ctx, u, dw, enc, amax, logp, pmax, umax, mel, sub, h4, wv, wv_floats, total;
+// byte offsets of the block scratch buffers in a workspace: what every workspace plan holds (h4: planned only where the layer-at-a-time launches run)
+struct ScratchPlan {
+  size_t xa, xb, qkv, ctx, u, dw, h4 = 0;
+};
+struct Plan : ScratchPlan {
+  size_t enc, amax, logp, pmax, umax, mel, sub, wv, wv_floats, total;
 };
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// lays a workspace out: buffers one behind the other, each 256-byte aligned
+struct Layout {
+  size_t o = 0;
+  size_t take(size_t floats) { const size_t at = o; o = align256(o + floats * 4); return at; }
+  // the six block buffers for M rows of d features: what every plan starts with
+  void scratch(ScratchPlan& p, size_t M, size_t d) {
+    p.xa = take(M * d); p.xb = take(M * d); p.qkv = take(M * 3 * d); p.ctx = take(M * d); p.u = take(M * d); p.dw = take(M * d);
+  }
+};
 
 struct Geometry {
   int Bp, Lb, F, T1, T, nblk;
@@ -288,6 +300,11 @@ struct Scratch {
   float *xa, *xb, *qkv, *ctx, *u, *dw;
   float* h4 = nullptr;   // [M, 4d] FFN hidden (bf16 GEMM path only: its layers are separate launches)
 };
+inline Scratch make_scratch(const ScratchPlan& p, char* ws) {
+  Scratch sc{(float*)(ws + p.xa), (float*)(ws + p.xb), (float*)(ws + p.qkv), (float*)(ws + p.ctx), (float*)(ws + p.u), (float*)(ws + p.dw)};
+  sc.h4 = (float*)(ws + p.h4);
+  return sc;
+}
 
 struct CrossAttn {
   const float* enc;   // [B, T_enc, d]
@@ -300,22 +317,34 @@ struct CrossAttn {
 
 struct StackOff {
   std::vector<BlockOff> blocks;
+  bool project = false;
+  int V = 0;               // classes of the head, 0 = none
   size_t proj_w = 0, proj_b = 0, fc_w = 0, fc_b = 0;
   int NT_fc = 0;
   size_t proj_pp = 0;      // dmodel 144: [W ; b] of the projection as a two-term stream (append_pp_plain), 0 = none
   float proj_pp_sw = 1.f;
 };
 
-// ---- shared host functions (defined in api.hip unless noted) -----------------------------------------------------------
-int fail(int code, const char* fmt, ...);
-void same_pad(int n, int k, int s, int* out, int* before);
+struct FrontOff {
+  size_t dft = 0, mel = 0, c1w = 0, c1b = 0, c2w = 0, c2b = 0, lw = 0, lb = 0;
+  size_t c2s = 0, c2h = 0, lws = 0, lpp = 0;   // 0 = not packed: conv2 split-bf16 / two-term fp16, the Dense split-bf16 / two-term stream
+  FftOff fft;
+  MelBandOff band;
+  float c2_hs = 0.f, c2_ws = 0.f, c1_l1 = 0.f, c1_bmax = 0.f, c1_ms = 0.f, c1_ws = 0.f, lin_pp_sw = 1.f;
+};
+constexpr double kNoMelBound = -1.0;
+
+// ---- weights.hip: host tensors -> device arena ---------------------------------------------------------------------------
 void add_block_expected(std::vector<Expected>& ex, const std::string& p, int d, int H, int hs, int k, bool keras_mha = false);
+void add_stack_expected(std::vector<Expected>& ex, const std::string& prefix, const std::string& blk, int nblocks,
+                        int d, int H, int hs, int k, bool project, int num_classes, bool keras_mha);
 std::vector<float> pack_p16(const std::function<float(int, int)>& f, int K, int N, int NTpad);
 std::vector<float> pack_split32(const std::function<float(int, int)>& f, int K, int N);
+std::vector<float> pack_half32(const std::function<float(int, int)>& f, int K, int N, float scale);
 std::vector<float> pack_conv2_split(const std::vector<float>& c2, int d);          // conv2 kernel -> subconv_split_ring_kernel fragments
+std::vector<float> pack_conv2_half(const std::vector<float>& c2, int d, float wscale);   // conv2 kernel * wscale as hi + lo fp16 fragments (two-term scheme)
 std::vector<float> pack_linear_split(const std::vector<float>& lin, int K, int d);  // subsampling Dense -> sublinear_split_kernel slabs
 float half_scale_for(double bound, int max_shift = 100);                            // largest power of two s with bound * s <= 2^15 (0: no usable bound)
-std::vector<float> pack_conv2_half(const std::vector<float>& c2, int d, float wscale);   // conv2 kernel * wscale as hi + lo fp16 fragments (two-term scheme)
 void append_slabs(std::vector<float>& stream, const std::function<float(int, int)>& f, int K, int N, bool group_major);
 // pair-pipelined stream of one chain y += W2 act(W1 x + b1) (fused_pp.hip, tools/gen_pp.py): w1(k, n) with k <= K1 (row K1 = the
 // bias), H hidden features, w2(k, n) [H, 144]; and of a plain layer [145, 144 G] in column groups of nine tiles
@@ -325,17 +354,37 @@ float append_pp_plain(std::vector<float>& stream, const std::function<float(int,
 // W[K, N] as the slab ring of gemm_ring.hip, registered in ab.ring_pairs against the P16 pack at p16_off
 void put_ring(ArenaBuilder& ab, size_t p16_off, const std::function<float(int, int)>& f, int K, int N, bool glu);
 void put_ring_head(ArenaBuilder& ab, size_t p16_off, const std::function<float(int, int)>& f, int K, int V);
+long ring_min_rows();          // rows from which launch_gemm16 hands a dense layer to the ring kernels
 bool ring_packs_wanted(const mi355asr_model* m);
 void register_rings(mi355asr_model* m, const ArenaBuilder& ab, const float* base);
 // W[144, V] of a class head as the slab stream of head_ld_kernel (fused.hip), registered against its P16 pack
 void put_head_slabs(ArenaBuilder& ab, size_t p16_off, const std::function<float(int, int)>& f, int d, int V, const float* bias);
 FftOff pack_fft(ArenaBuilder& ab, const std::vector<float>& re, const std::vector<float>& im, int n_dft, int nb);
-BlockOff pack_block(mi355asr_model* m, ArenaBuilder& ab, const std::string& p, int d, int H, int hs, int k, bool keras_mha = false);
+BlockOff pack_block(mi355asr_model* m, ArenaBuilder& ab, const std::string& p, int d, int hs, bool keras_mha = false);
 BlockDev resolve(const BlockOff& o, const float* base);
+void pack_head(mi355asr_model* m, ArenaBuilder& ab, StackOff& so, const std::vector<float>& fc, const std::vector<float>& bias, int V);
+StackOff pack_stack(mi355asr_model* m, ArenaBuilder& ab, const std::string& prefix, const std::string& blk, int nblocks,
+                    bool project, int V, bool keras_mha);
+void resolve_stack(StackDev& sd, const StackOff& so, const float* base);
+double db_mel_bound(const mi355asr_model* m, const std::string& prefix);
+FrontOff pack_front(mi355asr_model* m, ArenaBuilder& ab, const std::string& prefix, double mel_bound, std::vector<float>* lin_plain = nullptr);
+void resolve_front(mi355asr_model* m, const FrontOff& o, const float* base);
+int upload_arena(mi355asr_model* m, const ArenaBuilder& ab, hipStream_t s);
+
+// ---- api.hip: errors, geometry helpers, the ragged-batch checks ------------------------------------------------------------
+int fail(int code, const char* fmt, ...);
+void same_pad(int n, int k, int s, int* out, int* before);
+int launch_mel_auto(const mi355asr_model* m, MelArgs& me, hipStream_t s);   // banded kernel when available, else the GEMM
+int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, const float* wp, hipStream_t s);
+// ragged batches: more than 16 rows per utterance, or EINVAL; the device lengths read back and held to [1, hi]
+int ragged_rows_ok(int T, const char* what);
+int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s, std::vector<int32_t>* host = nullptr);
+int ragged_layers256_ok(const mi355asr_model* m, int ksz);   // dmodel 256, 64-dim heads, ConvModule kernel 32, layer-at-a-time launches
+
+// ---- block_path.hip: which kernels run a block and a class head ------------------------------------------------------------
 bool use_gemm16(const mi355asr_model* m);
 bool gemm16_for(const mi355asr_model* m, size_t M);
-int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, const float* wp, hipStream_t s);
-// One ConformerBlock (conformer_blocks.py:259-265), block_path.hip.  Input in sc.xa; output to `out`, or (out == nullptr) left in
+// One ConformerBlock (conformer_blocks.py:259-265).  Input in sc.xa; output to `out`, or (out == nullptr) left in
 // sc.xa -- the fused path ping-pongs xa/xb by swapping the two pointers in `sc` instead of copying.  cross: the Translator's RBlock
 // (conformer_blocks.py:455-463, 496-503), whose attention is a cross-attention with q = LN(x + PE) and k = v = the encoder output.
 // next / ff1_done (dmodel-144 fused path): when `next` is given and the output stays in the scratch buffers, the tail kernel
@@ -349,15 +398,20 @@ bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M);   //
 // streams of the handle (fp32 mode), else gemm_rows<EPI_HEAD>.  The layer-at-a-time head (gemm16, when gemm16_for(m, M)) comes
 // first, after the streams, or never.  split: >= 16 M words for a two-term head split over class ranges (null: one range);
 // part: >= 16 M words for a split layer-at-a-time head; amax_scratch: >= M words, the arg-max of the kernels that always store
-// one when hd.argmax_out is null.  (block_path.hip)
+// one when hd.argmax_out is null.
 enum class HeadLayers { never, first, after_streams };
 int run_class_head(const mi355asr_model* m, GemmArgs hd, HeadLayers layers, float* split, float* part, int32_t* amax_scratch,
                    hipStream_t s);
-// ragged batches (api.hip): more than 16 rows per utterance, or EINVAL; the device lengths read back and held to [1, hi]
-int ragged_rows_ok(int T, const char* what);
-int ragged_check_lengths(const int32_t* len_dev, int B, int hi, const char* what, hipStream_t s, std::vector<int32_t>* host = nullptr);
-int ragged_layers256_ok(const mi355asr_model* m, int ksz);   // dmodel 256, 64-dim heads, ConvModule kernel 32, layer-at-a-time launches
-void resolve_stack(StackDev& sd, const StackOff& so, const float* base, bool project, int V);   // api_chunk.hip
+// the class head of a stack over M rows of x: the arguments every head kernel takes
+inline GemmArgs head_args(const StackDev& st, const float* x, int M, float* logits, int32_t* argmax) {
+  GemmArgs hd{};
+  hd.x = x; hd.y = logits; hd.wp = st.fc_wp; hd.bias = st.fc_b;
+  hd.M = M; hd.NT = st.NT_fc; hd.ldy = st.num_classes; hd.n_valid = st.num_classes; hd.eps = kLnEps;
+  hd.argmax_out = argmax;
+  return hd;
+}
+
+// ---- the other handle kinds' weight packing ----------------------------------------------------------------------------------
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip
 int finalize_vad(mi355asr_model* m, hipStream_t s);          // vad.hip

@@ -915,7 +915,7 @@ def test_device_beam_search_arithmetic_is_the_host_c_librarys(tmp_path):
 
 
 def test_host_fp16_rounding_of_the_two_term_weight_packs_equals_numpy():
-    """api.hip's f16_rne / f16_to_float (the hi and lo terms of the two-term fp16 weight packs are rounded on the host):
+    """weights.hip's f16_rne / f16_to_float (the hi and lo terms of the two-term fp16 weight packs are rounded on the host):
     normal and subnormal values, overflow, exact ties between neighbouring halves -- bit-equal to NumPy's float16."""
     import ctypes
     from tensorflowasr_amd import _lib
