@@ -351,6 +351,39 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
                                 float* hidden_dev, float* logits_dev, int32_t* argmax_dev, float* new_mha_dev,
                                 float* new_cnn_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- ChunkConformer streaming: many streams per call, state on the device --------------------------------------
+ * One call advances every stream that has a packet by that packet; stream b's results are those of the single-stream
+ * calls above (picker_stream_predict -> feature_pick -> decoder_stream_predict) on its own audio, whatever else shares
+ * the call.  A stream lives in a SLOT (0 .. n_streams - 1) of an opaque state buffer the caller allocates on the device;
+ * between calls everything a stream needs stays there (wav and sub caches, per block the projected keys / values and
+ * the GLU rows of the last win_front / kernel_size frames, the decoder rows that wait for right context).
+ * A packet is wav_buf_length = 16 * hop samples; a stream's LAST packet may be shorter (n_samples_host), its first may
+ * not.  Supported: what chunk_conformerS.yml ships -- chunk_num 16, win_back 0 for encoder / picker / helper, win_back
+ * <= 16 for the text decoder, fp32; anything else is MI355ASR_EINVAL before anything is launched, as are a slot out of
+ * range or named twice and a packet length outside 1 .. wav_buf_length.  The step makes no host synchronisation: its
+ * integer results are device arrays the caller reads back with one copy.
+ * Outputs (device, NULL = not wanted), n = streams of the call, TPd = decoder win_back + 4: */
+typedef struct {
+  int32_t* phone_argmax;    /* i32 [n, 4]        per-frame argmax of the phone picker                               */
+  int32_t* n_picked;        /* i32 [n]           frames of the call the picker did not call blank                   */
+  int32_t* text_argmax;     /* i32 [n, TPd]      per-frame argmax of the text decoder: valid rows, then unvalid     */
+  int32_t* n_valid;         /* i32 [n]           text rows that are final (0 when nothing was picked)               */
+  int32_t* n_unvalid;       /* i32 [n]           text rows that will be run again with more right context           */
+  float*   phone_logits;    /* f32 [n, 4, picker_num_classes]                                                       */
+  float*   text_logits;     /* f32 [n, TPd, decoder_num_classes]  rows past n_valid + n_unvalid are padding         */
+  float*   picker_hidden;   /* f32 [n, 4, d]                                                                        */
+} mi355asr_chunk_streams_outputs;
+/* bytes of the state buffer for n_streams slots and of the workspace of a step over up to n_streams streams */
+int mi355asr_chunk_streams_bytes(const mi355asr_model* m, int32_t n_streams, size_t* state_bytes, size_t* ws_bytes);
+/* the n slots of slots_host (NULL: all n_streams) become fresh streams; a new state buffer is reset as a whole first */
+int mi355asr_chunk_streams_reset(mi355asr_model* m, void* state_dev, int32_t n_streams, const int32_t* slots_host,
+                                 int32_t n, void* stream);
+/* packets_dev f32 [n, wav_buf_length] (row i: the packet of slot slots_host[i], the rest of a short one is ignored);
+ * n_samples_host i32 [n] or NULL (every packet full) */
+int mi355asr_chunk_streams_step(mi355asr_model* m, void* state_dev, int32_t n_streams, const int32_t* slots_host,
+                                int32_t n, const float* packets_dev, const int32_t* n_samples_host,
+                                const mi355asr_chunk_streams_outputs* outs, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* ---- Translator: phoneme ids + encoder output -> text logits -------------------------------
  * replaces: Translator(inp_classes, tar_classes, dmodel, num_blocks, head_size, num_heads, kernel_size, dropout,
  * fc_factor) (test_asr.py:76-84; conformer_blocks.py:505-548): Embedding(inp_classes -> d) -> num_blocks x RBlock

@@ -50,6 +50,12 @@ class ChunkOutputs(ctypes.Structure):
                                                "helper_out", "text_logits", "text_argmax")]
 
 
+class ChunkStreamsOutputs(ctypes.Structure):
+    """mirror of `mi355asr_chunk_streams_outputs`."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("phone_argmax", "n_picked", "text_argmax", "n_valid", "n_unvalid",
+                                               "phone_logits", "text_logits", "picker_hidden")]
+
+
 class Mi355AsrError(RuntimeError):
     pass
 
@@ -108,6 +114,9 @@ SIGNATURES = {
     "mi355asr_chunk_stream_workspace_bytes": (ctypes.c_int, [_P, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_chunk_front_stream": (ctypes.c_int, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mi355asr_chunk_stack_stream": (ctypes.c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mi355asr_chunk_streams_bytes": (ctypes.c_int, [_P, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "mi355asr_chunk_streams_reset": (ctypes.c_int, [_P, _P, _I, _P, _I, _P]),
+    "mi355asr_chunk_streams_step": (ctypes.c_int, [_P, _P, _I, _P, _I, _P, _P, ctypes.POINTER(ChunkStreamsOutputs), _P, _SZ, _P]),
     "mi355asr_translator_create": (ctypes.c_int, [ctypes.POINTER(TranslatorConfig), ctypes.POINTER(_P)]),
     "mi355asr_translator_workspace_bytes": (ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_translator_forward": (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),

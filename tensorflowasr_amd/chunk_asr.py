@@ -166,3 +166,145 @@ class ChunkAMTester(ChunkASR):
             if self.all_steps and self.steps >= self.all_steps:
                 break
         return self.results()
+
+
+class _Greedy:
+    """greedy CTC text of a growing frame sequence, kept as integers on the host: merge repeated frames, drop the blank
+    (tf.keras.backend.ctc_decode), then drop id 0 as `_ctc_text` does."""
+
+    def __init__(self, blank):
+        self.blank, self.prev, self.ids = blank, None, []
+
+    def feed(self, frames):
+        for f in frames:
+            f = int(f)
+            if f != self.prev and f != self.blank:
+                self.ids.append(f)
+            self.prev = f
+        return self
+
+    def fork(self):
+        g = _Greedy(self.blank)
+        g.prev, g.ids = self.prev, list(self.ids)
+        return g
+
+    def text(self):
+        return [n for n in self.ids if n != 0]
+
+
+class _Stream:
+    def __init__(self, phone_blank, text_blank):
+        self.buf = np.zeros(0, np.float32)
+        self.packets = 0
+        self.phones = _Greedy(phone_blank)      # over the picked (non-blank) phone frames of every packet so far
+        self.n_phone_frames = 0
+        self.valid = _Greedy(text_blank)        # over the final text frames
+        self.n_valid = 0
+        self.unvalid = []                       # the text frames that still wait for right context (of the last decoder run)
+
+
+class ChunkStreamingServer:
+    """Many live ChunkConformer streams on one GPU: `ChunkASR.stream_call`'s loop for every caller at once.
+
+        srv = ChunkStreamingServer(chunk_asr, 64)
+        slot = srv.open()
+        for t, phones, text in srv.send({slot: samples})[slot]: ...      # any number of samples per call
+        tail = srv.close(slot)                                            # the rest as the short last packet
+
+    `send` cuts what arrives into packets of `wav_buf_length` samples and runs ONE `stream_step` per tick over all streams
+    that have a full packet; the tuples are those `stream_call` appends, one per packet completed.  The per-frame argmax
+    comes from the head kernels; each stream's greedy text is continued on the host from its frame ids instead of being
+    decoded again from all logits.  `stepper` (default: the recogniser's model) is anything with `open_streams`,
+    `reset_streams` and `stream_step` of `ChunkConformer`."""
+
+    def __init__(self, chunk_asr, n_streams, stepper=None):
+        from .models import StreamGuard
+        self.asr = chunk_asr
+        self.stepper = stepper if stepper is not None else chunk_asr.runner
+        self.n_streams = int(n_streams)
+        self.wav_buf_length = int(chunk_asr.wav_buf_length)
+        self.state = self.stepper.open_streams(self.n_streams)
+        self.guard = StreamGuard(self.n_streams, self.wav_buf_length)
+        self.streams = {}
+        self.free = list(range(self.n_streams - 1, -1, -1))
+        self.win_back = int(getattr(self.state, "win_back", 0))
+
+    def open(self):
+        if not self.free:
+            raise RuntimeError("all %d stream slots are in use" % self.n_streams)
+        slot = self.free.pop()
+        self.stepper.reset_streams(self.state, [slot])
+        self.guard.reset([slot])
+        self.streams[slot] = _Stream(self.asr.phone_featurizer.num_classes - 1, self.asr.text_featurizer.num_classes - 1)
+        return slot
+
+    def _stream(self, slot):
+        if slot not in self.streams:
+            raise KeyError("slot %r is not open" % (slot,))
+        return self.streams[slot]
+
+    def tick(self, packets):
+        """{slot: one packet} -> {slot: tuple or None}: one `stream_step` over these streams."""
+        slots = sorted(packets)
+        rows = [np.asarray(packets[s], np.float32).reshape(-1) for s in slots]
+        for s in slots:
+            self._stream(s)
+        lens = [len(r) for r in rows]
+        self.guard.check(slots, lens)
+        res = self.stepper.stream_step(self.state, slots, rows)
+        self.guard.commit(slots, lens)
+        out = {}
+        sr = self.asr.speech_featurizer.sample_rate
+        for s in slots:
+            st, r = self.streams[s], res[s]
+            st.packets += 1
+            if r["n_picked"] > 0:                                   # the decoder ran (stream_call: feature_outputs.shape[1] != 0)
+                blank = st.phones.blank
+                picked = [f for f in r["phone_ids"] if int(f) != blank]
+                st.phones.feed(picked)
+                st.n_phone_frames += len(picked)
+                nv = r["n_valid"]
+                st.valid.feed(r["text_ids"][:nv])
+                st.n_valid += nv
+                # (win_back 0: the reference returns zeros_like(valid logits) as the unvalid part -- nv frames of class 0)
+                st.unvalid = list(r["text_ids"][nv:]) if self.win_back else [0] * nv
+            out[s] = None
+            if st.n_valid + len(st.unvalid) == 0 or st.n_phone_frames == 0:
+                continue
+            text = self.asr.text_featurizer.iextract(st.valid.fork().feed(st.unvalid).text())
+            phone = self.asr.phone_featurizer.iextract(st.phones.text())
+            out[s] = (st.packets * self.wav_buf_length / sr, " ".join(phone), "".join(text))
+        return out
+
+    def send(self, audio):
+        """{slot: float samples of any length} -> {slot: [(seconds_heard, phones, text), ...]}"""
+        out = {}
+        for s, x in audio.items():
+            st = self._stream(s)
+            st.buf = np.concatenate([st.buf, np.asarray(x, np.float32).reshape(-1)])
+            out[s] = []
+        W = self.wav_buf_length
+        while True:
+            ready = {s: st.buf[:W] for s, st in self.streams.items() if len(st.buf) >= W}
+            if not ready:
+                break
+            for s in ready:
+                self.streams[s].buf = self.streams[s].buf[W:]
+            for s, t in self.tick(ready).items():
+                if t is not None:
+                    out.setdefault(s, []).append(t)
+        return out
+
+    def close(self, slot):
+        """the buffered tail as the stream's short last packet -> its tuples; the slot is free afterwards."""
+        st = self._stream(slot)
+        try:
+            out = []
+            if len(st.buf):
+                t = self.tick({slot: st.buf})[slot]
+                if t is not None:
+                    out.append(t)
+            return out
+        finally:
+            del self.streams[slot]
+            self.free.append(slot)

@@ -89,20 +89,22 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
 // The "valid" Melspectrogram (chunk front): the reference left-pads n_dft - 1 zeros, then a VALID strided conv; log10 only, no
 // max-normalisation (chunk_amplitude_to_decibel, backend_keras.py:25-37).  absmax: B words that receive each utterance's largest
 // |mel| when the banded mel kernel runs; set to null when it did not (the dense kernel does not produce it).
+// pad_left: zeros in front of the first frame (default: the layer's n_dft - 1; the batched streams frame a window they cut themselves)
 int run_valid_mel(const mi355asr_model* m, const float* wav, int B, int L, int F, float* logp, float* pmax, float* mel,
-                  unsigned** absmax, hipStream_t s) {
+                  unsigned** absmax, hipStream_t s, int pad_left = -1) {
   const auto& c = m->cfg;
+  if (pad_left < 0) pad_left = c.n_dft - 1;
   const int FT = ceil_div(F, 16);
   if (m->fft_ok) {
     FftStftArgs fa{wav, logp, pmax, m->fft_w1p, m->fft_w2p, m->fft_twc, m->fft_tws, m->fft_win,
-                   B, L, F, m->dm.hop, c.n_dft - 1, m->dm.LP, 0};
+                   B, L, F, m->dm.hop, pad_left, m->dm.LP, 0};
     fa.w1s = m->fft_w1s; fa.w2s = m->fft_w2s; fa.w1h = m->fft_w1h; fa.w2h = m->fft_w2h;
     PROF(MI355ASR_K_STFT);
     LAUNCH_TRY(launch_fft_stft(fa, s), "stft (valid, fft)");
   } else {
     StftArgs st{};
     st.wav = wav; st.logp = logp; st.pmax = pmax; st.wp = m->dft_wp;
-    st.B = B; st.L = L; st.F = F; st.hop = m->dm.hop; st.pad_left = c.n_dft - 1; st.n_dft = c.n_dft;
+    st.B = B; st.L = L; st.F = F; st.hop = m->dm.hop; st.pad_left = pad_left; st.n_dft = c.n_dft;
     st.NT = m->dm.NT_dft; st.LP = m->dm.LP; st.nbins = m->dm.nbins; st.FT = FT; st.NCH = m->dm.NCH_dft;
     st.db10 = 0;
     PROF(MI355ASR_K_STFT);
@@ -562,4 +564,310 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
   }
   return 0;
 }
+}  // extern "C"
+
+// =======================================================================================================
+// Batched ChunkConformer streaming: many streams per call, all state on the device (chunk_stream.hip has the
+// kernels and the row layout).  Stream b of a tick is picker_stream_predict -> feature_pick ->
+// decoder_stream_predict of the single-stream path above on that stream's own caches.
+// =======================================================================================================
+namespace {
+
+constexpr int kCsChunkNum = 16;   // mel frames per packet (ChunkConformerFront.chunk_num of chunk_conformerS.yml)
+
+// one slot of the state buffer, in 4-byte words: [wav cache | sub cache | counters | waiting decoder rows | per block: K ring, V ring, GLU ring]
+struct CsLayout {
+  int Wb, S, TP, TPd, wbd, nblk;
+  size_t wav, sub, hdr, carry, zero_words, slot_words;
+  std::vector<size_t> blk;        // K ring of block j (V ring: + wf d, GLU ring: + 2 wf d); blocks in the order encoder, picker, helper, decoder
+  size_t meta(int j) const { return hdr + 4 + 4 * (size_t)j; }
+};
+
+// refuses what the batched step does not cover (everything chunk_conformerS.yml ships is covered)
+int cs_config_ok(const mi355asr_model* m) {
+  if (!m || !m->is_chunk) return fail(MI355ASR_EINVAL, "not a ChunkConformer handle");
+  const auto& c = m->ccfg;
+  if (c.enc_win_back != 0 || c.picker_win_back != 0 || c.helper_win_back != 0)
+    return fail(MI355ASR_EINVAL, "batched streams: encoder / picker / helper win_back must be 0 (got %d, %d, %d)", c.enc_win_back,
+                c.picker_win_back, c.helper_win_back);
+  if (c.decoder_win_back > 16) return fail(MI355ASR_EINVAL, "batched streams: decoder win_back=%d, at most 16", c.decoder_win_back);
+  if (m->cfg.gemm_dtype != 0) return fail(MI355ASR_EINVAL, "batched streams: fp32 (gemm_dtype float32) only");
+  const int TP = kCsChunkNum / m->cfg.reduction_factor;
+  const int wfs[4] = {c.enc_win_front, c.picker_win_front, c.helper_win_front, c.decoder_win_front};
+  for (int i = 0; i < 4; ++i) {
+    const int rows = i == 3 ? c.decoder_win_back + TP : TP;
+    if (wfs[i] < rows || wfs[i] + rows > 64)
+      return fail(MI355ASR_EINVAL, "batched streams: win_front=%d of stack %d: need %d <= win_front <= %d", wfs[i], i, rows, 64 - rows);
+  }
+  if (c.kernel_size < c.decoder_win_back + TP) return fail(MI355ASR_EINVAL, "batched streams: kernel_size=%d too small", c.kernel_size);
+  return 0;
+}
+
+CsLayout cs_layout(const mi355asr_model* m) {
+  const auto& c = m->ccfg;
+  const size_t d = m->cfg.dmodel;
+  CsLayout L;
+  L.Wb = kCsChunkNum * m->dm.hop;
+  L.TP = kCsChunkNum / m->cfg.reduction_factor;
+  L.S = L.TP;                                   // init_picker_caches: chunk_num / reduction_factor zero mel rows
+  L.wbd = c.decoder_win_back;
+  L.TPd = L.wbd + L.TP;
+  const int nb[4] = {c.enc_num_blocks, c.picker_num_blocks, c.helper_num_blocks, c.decoder_num_blocks};
+  const int wf[4] = {c.enc_win_front, c.picker_win_front, c.helper_win_front, c.decoder_win_front};
+  L.nblk = nb[0] + nb[1] + nb[2] + nb[3];
+  auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  size_t o = 0;
+  L.wav = o; o = up(o + L.Wb);
+  L.sub = o; o = up(o + (size_t)L.S * m->cfg.n_mels);
+  L.hdr = o; o = up(o + 4 + 4 * (size_t)L.nblk);
+  L.zero_words = o;
+  L.carry = o; o = up(o + (size_t)std::max(L.wbd, 1) * d);
+  for (int st = 0; st < 4; ++st)
+    for (int j = 0; j < nb[st]; ++j) {
+      L.blk.push_back(o);
+      o = up(o + (2 * (size_t)wf[st] + c.kernel_size) * d);
+    }
+  L.slot_words = o;
+  return L;
+}
+
+struct CsPlan : ScratchPlan {
+  size_t tab, window, logp, pmax, mel, nsub, sub, hid, amax_p, amax_t, total;
+};
+CsPlan cs_plan(const mi355asr_model* m, const CsLayout& L, int n) {
+  const size_t d = m->cfg.dmodel;
+  CsPlan p;
+  Layout lay;
+  lay.scratch(p, (size_t)n * L.TPd, d);
+  p.tab = lay.take((size_t)n * 5);               // slots, packet lengths, helper rows, decoder rows, valid decoder rows
+  const int F = kCsChunkNum, FT = ceil_div(F, 16);
+  p.window = lay.take((size_t)n * ((F - 1) * m->dm.hop + m->cfg.n_dft));
+  p.logp = lay.take((size_t)n * F * m->dm.LP);
+  p.pmax = lay.take((size_t)n * std::max(FT * m->dm.NCH_dft, F));
+  p.mel = lay.take((size_t)n * F * m->cfg.n_mels);
+  p.nsub = lay.take((size_t)n * (L.S + F) * m->cfg.n_mels);
+  p.sub = lay.take((size_t)n * L.TP * m->dm.F2 * d);
+  p.hid = lay.take((size_t)n * L.TP * d);
+  p.amax_p = lay.take((size_t)n * L.TP);
+  p.amax_t = lay.take((size_t)n * L.TPd);
+  p.total = lay.o;
+  return p;
+}
+
+size_t cs_state_bytes(const CsLayout& L, int n_streams) { return ((size_t)n_streams * L.slot_words + (size_t)n_streams) * 4; }
+
+// One stack over the n TP padded rows in sc.xa (result there too): the row-wise layers on every row, attention and depthwise conv
+// per stream on its T[i] real rows against its caches.  blk0 = index of the stack's first block in the state layout.
+int cs_run_stack(const mi355asr_model* m, const StackDev& st, const CsLayout& L, int blk0, float* state, const int32_t* slots,
+                 int n, int TP, const int32_t* T, const int32_t* A, Scratch& sc, hipStream_t s) {
+  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size;
+  const int M = n * TP;
+  const BlockOpts& bo = st.opts;
+  for (size_t i = 0; i < st.blocks.size(); ++i) {
+    const BlockDev& w = st.blocks[i];
+    const size_t koff = L.blk[blk0 + i], ring = (size_t)bo.win_front * d;
+    Chain2Args f1{};
+    f1.x = sc.xa; f1.res = sc.xa; f1.y = sc.xb;
+    f1.ln_g = w.ff_ln_g[0]; f1.ln_b = w.ff_ln_b[0];
+    f1.w1p = w.ff_w1p[0]; f1.b1 = w.ff_b1[0]; f1.w2p = w.ff_w2p[0]; f1.b2 = w.ff_b2[0];
+    f1.scale = bo.fc; f1.eps = kLnEps; f1.M = M;
+    { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f1, s), "ff_module_1"); }
+    GemmArgs q{};
+    q.x = sc.xb; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.qkv_wp; q.bias = w.qkv_b;
+    q.M = M; q.NT = 3 * d / 16; q.ldy = 3 * d; q.n_valid = 3 * d; q.eps = kLnEps;
+    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
+    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "qkv projection"); }
+    CsAttnArgs at{};
+    at.qkv = sc.qkv; at.ctx = sc.ctx; at.state = state; at.slot_words = L.slot_words; at.meta_off = L.meta(blk0 + (int)i);
+    at.k_off = koff; at.v_off = koff + ring; at.slots = slots; at.T = T; at.A = A;
+    at.n = n; at.TP = TP; at.H = H; at.wf = bo.win_front; at.wb = bo.win_back;
+    { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_cs_attn(hs, at, s), "stream attention"); }
+    GemmArgs op{};
+    op.x = sc.ctx; op.y = sc.xa; op.res = sc.xb; op.wp = w.out_wp; op.bias = w.out_b;
+    op.M = M; op.NT = d / 16; op.ldy = d; op.n_valid = d; op.eps = kLnEps;
+    { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, op, s), "attention out-projection"); }
+    GemmArgs g{};
+    g.x = sc.xa; g.y = sc.u; g.ln_g = w.cv_ln_g; g.ln_b = w.cv_ln_b; g.wp = w.pw1_wp; g.bias = w.pw1_b;
+    g.M = M; g.NT = 2 * d / 16; g.ldy = d; g.n_valid = d; g.eps = kLnEps;
+    { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, g, s), "pw_conv_1 + GLU"); }
+    CsDwArgs dwa{};
+    dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.state = state; dwa.slot_words = L.slot_words;
+    dwa.meta_off = at.meta_off; dwa.g_off = koff + 2 * ring; dwa.slots = slots; dwa.T = T; dwa.A = A;
+    dwa.n = n; dwa.TP = TP; dwa.D = d; dwa.K = bo.ksz; dwa.wf = bo.win_front;
+    { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_cs_dwconv(dwa, s), "stream depthwise conv"); }
+    Chain2Args cv{};
+    cv.x = sc.dw; cv.res = sc.xa; cv.y = sc.xb;
+    cv.w1p = w.pc_w1p; cv.b1 = w.pc_b1; cv.aff_s = w.bn_s; cv.aff_t = w.bn_t; cv.w2p = w.pw2_wp; cv.b2 = w.pw2_b;
+    cv.scale = 1.0f; cv.eps = kLnEps; cv.M = M;
+    { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, cv, s), "conv module tail"); }
+    Chain2Args f2{};
+    f2.x = sc.xb; f2.res = sc.xb; f2.y = sc.xa;
+    f2.ln_g = w.ff_ln_g[1]; f2.ln_b = w.ff_ln_b[1];
+    f2.w1p = w.ff_w1p[1]; f2.b1 = w.ff_b1[1]; f2.w2p = w.ff_w2p[1]; f2.b2 = w.ff_b2[1];
+    f2.fln_g = w.ln_g; f2.fln_b = w.ln_b;
+    f2.scale = bo.fc; f2.eps = kLnEps; f2.M = M;
+    { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f2, s), "ff_module_2 + LayerNorm"); }
+  }
+  return 0;
+}
+
+// Dense(d -> d) of a stack with a projection: x -> sc.xa
+int cs_project(const mi355asr_model* m, const StackDev& st, const float* x, int M, Scratch& sc, hipStream_t s) {
+  const int d = m->cfg.dmodel;
+  GemmArgs pr{};
+  pr.x = x; pr.y = sc.xa; pr.wp = st.proj_wp; pr.bias = st.proj_b;
+  pr.M = M; pr.NT = d / 16; pr.ldy = d; pr.n_valid = d; pr.eps = kLnEps;
+  PROF(MI355ASR_K_CTC_PROJECT);
+  LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "project");
+  return 0;
+}
+
+int cs_common_checks(const mi355asr_model* m, int n_streams) {
+  if (int rc = cs_config_ok(m)) return rc;
+  if (n_streams < 1) return fail(MI355ASR_EINVAL, "n_streams=%d: need at least one slot", n_streams);
+  return 0;
+}
+
+// slots_host [n]: in range, each at most once
+int cs_check_slots(const int32_t* slots, int n, int n_streams) {
+  std::vector<char> seen((size_t)n_streams, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= n_streams) return fail(MI355ASR_EINVAL, "slot %d (entry %d) out of range 0 .. %d", slots[i], i, n_streams - 1);
+    if (seen[slots[i]]) return fail(MI355ASR_EINVAL, "slot %d is named twice", slots[i]);
+    seen[slots[i]] = 1;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355asr_chunk_streams_bytes(const mi355asr_model* m, int32_t n_streams, size_t* state_bytes, size_t* ws_bytes) {
+  if (int rc = cs_common_checks(m, n_streams)) return rc;
+  const CsLayout L = cs_layout(m);
+  if (state_bytes) *state_bytes = cs_state_bytes(L, n_streams);
+  if (ws_bytes) *ws_bytes = cs_plan(m, L, n_streams).total;      // a tick of n streams needs the plan of n: any n <= n_streams fits
+  return 0;
+}
+
+int mi355asr_chunk_streams_reset(mi355asr_model* m, void* state_dev, int32_t n_streams, const int32_t* slots_host, int32_t n,
+                                 void* stream) {
+  if (int rc = cs_common_checks(m, n_streams)) return rc;
+  if (!state_dev) return fail(MI355ASR_EINVAL, "null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const CsLayout L = cs_layout(m);
+  CsResetArgs ra{};
+  ra.state = (float*)state_dev; ra.slot_words = L.slot_words; ra.zero_words = (int)L.zero_words;
+  if (!slots_host) {
+    ra.n = n_streams;
+  } else {
+    if (n < 1) return fail(MI355ASR_EINVAL, "n=%d: need at least one slot", n);
+    if (int rc = cs_check_slots(slots_host, n, n_streams)) return rc;
+    // the slot table travels in the tail of the state buffer (n_streams words behind the slots)
+    int32_t* tab = (int32_t*)state_dev + (size_t)n_streams * L.slot_words;
+    m->cs_tab.assign(slots_host, slots_host + n);
+    HIP_TRY(hipMemcpyAsync(tab, m->cs_tab.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    ra.slots = tab; ra.n = n;
+  }
+  LAUNCH_TRY(launch_cs_reset(ra, s), "stream reset");
+  return 0;
+}
+
+int mi355asr_chunk_streams_step(mi355asr_model* m, void* state_dev, int32_t n_streams, const int32_t* slots_host, int32_t n,
+                                const float* packets_dev, const int32_t* n_samples_host,
+                                const mi355asr_chunk_streams_outputs* outs, void* ws_, size_t ws_bytes, void* stream) {
+  if (int rc = cs_common_checks(m, n_streams)) return rc;
+  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
+  if (!state_dev || !slots_host || !packets_dev || !outs || !ws_) return fail(MI355ASR_EINVAL, "null argument");
+  if (n < 1 || n > n_streams) return fail(MI355ASR_EINVAL, "n=%d: need 1 .. n_streams (%d)", n, n_streams);
+  if (int rc = cs_check_slots(slots_host, n, n_streams)) return rc;
+  const CsLayout L = cs_layout(m);
+  if (n_samples_host)
+    for (int i = 0; i < n; ++i)
+      if (n_samples_host[i] < 1 || n_samples_host[i] > L.Wb)
+        return fail(MI355ASR_EINVAL, "n_samples[%d]=%d: need 1 .. %d", i, n_samples_host[i], L.Wb);
+  const CsPlan p = cs_plan(m, L, n);
+  if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
+  char* ws = (char*)ws_;
+  hipStream_t s = (hipStream_t)stream;
+  const auto& c = m->cfg;
+  const int d = c.dmodel, TP = L.TP, TPd = L.TPd;
+  float* state = (float*)state_dev;
+  Scratch sc = make_scratch(p, ws);
+  // ---- the tick's tables: slots and packet lengths up, the per-stream row counts are made on the device
+  int32_t* tab = (int32_t*)(ws + p.tab);
+  int32_t *slots = tab, *nsamp = tab + n, *Th = tab + 2 * n, *Td = tab + 3 * n, *Vd = tab + 4 * n;
+  m->cs_tab.assign(slots_host, slots_host + n);
+  if (n_samples_host) m->cs_tab.insert(m->cs_tab.end(), n_samples_host, n_samples_host + n);
+  HIP_TRY(hipMemcpyAsync(tab, m->cs_tab.data(), m->cs_tab.size() * 4, hipMemcpyHostToDevice, s));
+  // ---- front: window of [wav cache ; packet], valid mel, [sub cache ; mel], two VALID convs, Dense
+  const int F = kCsChunkNum;
+  CsFrontArgs fa{};
+  fa.state = state; fa.slot_words = L.slot_words; fa.wav_off = L.wav; fa.slots = slots; fa.packets = packets_dev;
+  fa.n_samples = n_samples_host ? nsamp : nullptr; fa.window = (float*)(ws + p.window);
+  fa.n = n; fa.Wb = L.Wb; fa.Lwin = (F - 1) * m->dm.hop + c.n_dft; fa.hop = m->dm.hop;
+  LAUNCH_TRY(launch_cs_front_window(fa, s), "stream front window");
+  float* mel = (float*)(ws + p.mel);
+  // the window's frames begin at multiples of hop: the valid framing with nothing padded in front
+  if (int rc = run_valid_mel(m, fa.window, n, fa.Lwin, F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, nullptr, s, 0)) return rc;
+  CsSubArgs su{};
+  su.state = state; su.slot_words = L.slot_words; su.sub_off = L.sub; su.slots = slots; su.mel = mel;
+  su.new_sub = (float*)(ws + p.nsub); su.n = n; su.S = L.S; su.F = F; su.NM = c.n_mels;
+  LAUNCH_TRY(launch_cs_sub(su, s), "stream sub cache");
+  const int rows = L.S + F, T1 = (rows - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1;
+  if (T2 != TP) return fail(MI355ASR_EINVAL, "batched streams: the front yields %d rows per packet, expected %d", T2, TP);
+  SubConvArgs sa{};
+  sa.mel = su.new_sub; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+  sa.B = n; sa.F = rows; sa.NM = c.n_mels; sa.T1 = T1; sa.F1 = m->dm.F1; sa.T2 = T2; sa.F2 = m->dm.F2;
+  sa.st1 = 2; sa.pt1 = 0; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
+  { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (streams)"); }
+  StreamGemmArgs lg{};
+  lg.x = sa.out; lg.y = sc.xa; lg.wp = m->lin_wp; lg.bias = m->lin_b;
+  lg.M = n * TP; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+  { PROF(MI355ASR_K_SUBLINEAR); LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear"); }
+  // ---- encoder, phone picker (win_back 0: every row is valid, nothing waits)
+  const auto& cc = m->ccfg;
+  int blk = 0;
+  if (int rc = cs_run_stack(m, m->c_enc, L, blk, state, slots, n, TP, nullptr, nullptr, sc, s)) return rc;
+  blk += cc.enc_num_blocks;
+  if (int rc = cs_project(m, m->c_picker, sc.xa, n * TP, sc, s)) return rc;
+  if (int rc = cs_run_stack(m, m->c_picker, L, blk, state, slots, n, TP, nullptr, nullptr, sc, s)) return rc;
+  blk += cc.picker_num_blocks;
+  int32_t* amax_p = outs->phone_argmax ? outs->phone_argmax : (int32_t*)(ws + p.amax_p);
+  {
+    GemmArgs hd = head_args(m->c_picker, sc.xa, n * TP, outs->phone_logits, amax_p);
+    PROF(MI355ASR_K_CTC_HEAD);
+    LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "phone fully_connected");
+  }
+  float* hid = (float*)(ws + p.hid);
+  HIP_TRY(hipMemcpyAsync(hid, sc.xa, (size_t)n * TP * d * 4, hipMemcpyDeviceToDevice, s));
+  if (outs->picker_hidden) HIP_TRY(hipMemcpyAsync(outs->picker_hidden, sc.xa, (size_t)n * TP * d * 4, hipMemcpyDeviceToDevice, s));
+  // ---- feature_pick: the rows the picker did not call blank, and with them the row counts of the second half
+  CsPickArgs pa{};
+  pa.amax = amax_p; pa.hidden = hid; pa.picked = sc.xa; pa.state = state; pa.slot_words = L.slot_words; pa.hdr_off = L.hdr;
+  pa.slots = slots; pa.Th = Th; pa.Td = Td; pa.Vd = Vd;
+  pa.n_picked = outs->n_picked; pa.n_valid = outs->n_valid; pa.n_unvalid = outs->n_unvalid;
+  pa.n = n; pa.TP = TP; pa.D = d; pa.blank = cc.picker_num_classes - 1; pa.wb = L.wbd;
+  LAUNCH_TRY(launch_cs_pick(pa, s), "stream feature_pick");
+  // ---- context helper on the picked rows
+  if (int rc = cs_run_stack(m, m->c_helper, L, blk, state, slots, n, TP, Th, nullptr, sc, s)) return rc;
+  blk += cc.helper_num_blocks;
+  // ---- text decoder on [waiting rows ; helper output]; its last win_back rows wait for the next tick
+  float* dec_in = sc.xb;                        // (free between two stacks)
+  CsCarryArgs ca{};
+  ca.helped = sc.xa; ca.dec_in = dec_in; ca.state = state; ca.slot_words = L.slot_words; ca.hdr_off = L.hdr; ca.carry_off = L.carry;
+  ca.slots = slots; ca.Td = Td; ca.Vd = Vd; ca.n = n; ca.TP = TP; ca.TPd = TPd; ca.D = d;
+  LAUNCH_TRY(launch_cs_carry(ca, s), "stream decoder input");
+  if (int rc = cs_project(m, m->c_decoder, dec_in, n * TPd, sc, s)) return rc;
+  if (int rc = cs_run_stack(m, m->c_decoder, L, blk, state, slots, n, TPd, Td, Vd, sc, s)) return rc;
+  int32_t* amax_t = outs->text_argmax ? outs->text_argmax : (int32_t*)(ws + p.amax_t);
+  {
+    GemmArgs hd = head_args(m->c_decoder, sc.xa, n * TPd, outs->text_logits, amax_t);
+    PROF(MI355ASR_K_CTC_HEAD);
+    LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "text fully_connected");
+  }
+  return 0;
+}
+
 }  // extern "C"

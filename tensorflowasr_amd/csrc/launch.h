@@ -488,6 +488,68 @@ int launch_sublinear_split(const StreamGemmArgs& a, const float* ws, hipStream_t
 // the same layer on the two-term fp16 stream (fused_pp.hip; pp = append_pp_plain of K / 144 chunks [W_f ; bias or 0], packed with pp_sw)
 int launch_pp_sublinear(const StreamGemmArgs& a, const float* pp, float pp_sw, hipStream_t s);
 bool pp_sublinear_ok(const StreamGemmArgs& a, const float* pp);   // ... would take it
+// chunk_stream.hip: batched ChunkConformer streaming.  state = the caller's state buffer, slot_words floats per slot, *_off = word
+// offsets inside a slot; slots [n] = the slot of each stream of the tick; stream i owns rows i TP .. i TP + TP - 1 of the
+// activation buffers; T [n] = its real rows (null: TP), A [n] = how many of them join the cache (null: T).  All on the device.
+struct CsFrontArgs {
+  float* state; size_t slot_words, wav_off;
+  const int32_t* slots;
+  const float* packets;        // [n, Wb]
+  const int32_t* n_samples;    // [n] samples of each packet, 1 .. Wb (null: Wb)
+  float* window;               // [n, Lwin]: the samples under the last chunk_num valid-mode frames of [cache ; packet]
+  int n, Wb, Lwin, hop;
+};
+struct CsSubArgs {
+  float* state; size_t slot_words, sub_off;
+  const int32_t* slots;
+  const float* mel;            // [n, F, NM]
+  float* new_sub;              // [n, S + F, NM] = [sub cache ; mel]
+  int n, S, F, NM;
+};
+struct CsAttnArgs {
+  const float* qkv;            // [n TP, 3 D], q scaled by 1 / sqrt(head size)
+  float* ctx;                  // [n TP, D], rows >= T[i] zero
+  float* state; size_t slot_words, meta_off, k_off, v_off;   // meta: int (rows seen, K / V ring position, GLU ring position, -)
+  const int32_t *slots, *T, *A;
+  int n, TP, H, wf, wb;
+};
+struct CsDwArgs {
+  const float* u;              // [n TP, D] GLU output of the new rows
+  float* y;                    // [n TP, D], rows >= T[i] zero
+  const float* wd;             // [K, D]
+  float* state; size_t slot_words, meta_off, g_off;
+  const int32_t *slots, *T, *A;
+  int n, TP, D, K, wf;
+};
+struct CsPickArgs {
+  const int32_t* amax;         // [n TP] phone arg-max
+  const float* hidden;         // [n TP, D]
+  float* picked;               // [n TP, D]: the rows whose arg-max is not the blank, compacted, zero padded
+  const float* state; size_t slot_words, hdr_off;            // hdr: int (decoder rows waiting for right context, ...)
+  const int32_t* slots;
+  int32_t *Th, *Td, *Vd;       // [n] rows of the helper / of the text decoder / its valid rows
+  int32_t *n_picked, *n_valid, *n_unvalid;   // [n] caller's outputs (null: not wanted)
+  int n, TP, D, blank, wb;
+};
+struct CsCarryArgs {
+  const float* helped;         // [n TP, D]
+  float* dec_in;               // [n TPd, D] = [waiting rows ; helper output], zero padded
+  float* state; size_t slot_words, hdr_off, carry_off;
+  const int32_t *slots, *Td, *Vd;
+  int n, TP, TPd, D;
+};
+struct CsResetArgs {
+  float* state; size_t slot_words;
+  const int32_t* slots;        // [n] (null: slots 0 .. n - 1)
+  int n, zero_words;
+};
+int launch_cs_front_window(const CsFrontArgs& a, hipStream_t s);
+int launch_cs_sub(const CsSubArgs& a, hipStream_t s);
+int launch_cs_attn(int HS, const CsAttnArgs& a, hipStream_t s);
+int launch_cs_dwconv(const CsDwArgs& a, hipStream_t s);
+int launch_cs_pick(const CsPickArgs& a, hipStream_t s);
+int launch_cs_carry(const CsCarryArgs& a, hipStream_t s);
+int launch_cs_reset(const CsResetArgs& a, hipStream_t s);
 int launch_pick(const PickArgs& a, hipStream_t s);
 int launch_row_argmax(const float* x, int32_t* out, int M, int V, hipStream_t s);
 int launch_gather(const GatherArgs& a, hipStream_t s);

@@ -186,6 +186,7 @@ struct mi355asr_model {
   bool vad_enhance = false;   // mi355asr_vad_enhancer_create: the arena also holds audio_voice_mask
   mi355asr_vad_config vcfg;
   StackDev c_enc, c_picker, c_helper, c_decoder;
+  std::vector<int32_t> cs_tab;   // batched chunk streams: the host side of a tick's slot table while its copy is in flight
   // optional per-kernel timing with HIP events on the launch stream (mi355asr_profile_*)
   mutable bool prof = false;
   mutable std::vector<hipEvent_t> ev_free;

@@ -956,6 +956,51 @@ def _chunk_block_shapes(p, d, H, hs, k):
     return s
 
 
+class StreamGuard:
+    """Host bookkeeping of the batched ChunkConformer streams: which slots have begun and which have had their short last
+    packet.  The rules of a tick (mi355asr.h): every slot once, a packet of 1 .. wav_buf_length samples, a stream's FIRST
+    packet full (fewer than chunk_num mel frames: the single-stream path runs those), nothing after a short packet but a reset."""
+
+    def __init__(self, n_streams, wav_buf_length):
+        self.n_streams, self.wav_buf_length = int(n_streams), int(wav_buf_length)
+        self.packets = [0] * self.n_streams
+        self.ended = [False] * self.n_streams
+
+    def reset(self, slots):
+        for s in slots:
+            self.packets[s], self.ended[s] = 0, False
+
+    def check(self, slots, lengths):
+        if len(slots) < 1:
+            raise ValueError("a tick needs at least one stream")
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot is named twice in one tick: %s" % (sorted(slots),))
+        for s, k in zip(slots, lengths):
+            if not 0 <= s < self.n_streams:
+                raise ValueError("slot %d out of range 0 .. %d" % (s, self.n_streams - 1))
+            if not 1 <= k <= self.wav_buf_length:
+                raise ValueError("slot %d: a packet holds 1 .. %d samples, got %d" % (s, self.wav_buf_length, k))
+            if self.ended[s]:
+                raise ValueError("slot %d has had its short last packet: reset it before it takes another" % s)
+            if self.packets[s] == 0 and k != self.wav_buf_length:
+                raise ValueError("slot %d: the first packet of a stream must be full (%d samples, got %d); shorter "
+                                 "utterances go through the single-stream calls" % (s, self.wav_buf_length, k))
+
+    def commit(self, slots, lengths):
+        for s, k in zip(slots, lengths):
+            self.packets[s] += 1
+            self.ended[s] = k != self.wav_buf_length
+
+
+class ChunkStreams:
+    """State of `ChunkConformer.open_streams`: the device buffers of all slots (opaque) and the host's StreamGuard."""
+
+    def __init__(self, n_streams, wav_buf_length, win_back):
+        self.n_streams, self.wav_buf_length, self.win_back = n_streams, wav_buf_length, win_back
+        self.guard = StreamGuard(n_streams, wav_buf_length)
+        self.buf = self.ws = None
+
+
 class ChunkConformer(_ModelBase):
     """asr/models/chunk_conformer_blocks.py:775-822, offline `predict`: front -> ChunkConformerEncoder -> phone
     picker -> feature_pick -> ContextHelper -> text decoder.  `config` is the reference's model YAML as a dict
@@ -1069,7 +1114,8 @@ class ChunkConformer(_ModelBase):
         """(front_wav_cache, front_sub_cache, encoder_mha_cache, encoder_cnn_cache, picker_mha_cache,
         picker_cnn_cache, dec_inp) as ChunkConformer.init_picker_caches (:799-808)."""
         if B != 1:
-            raise NotImplementedError("the streaming entry points are single-stream, as the reference's (dec_inp is [1, 0, d])")
+            raise NotImplementedError("the cache tuples are the single-stream contract, as the reference's (dec_inp is [1, 0, d]); "
+                                      "many streams: open_streams(n) / stream_step")
         dev, d = self._h.device, self.dmodel
         _, _, sub_length, _ = self._stream_cfg()
         z = lambda n: torch.zeros((n, 1, 0, d), dtype=torch.float32, device=dev)
@@ -1080,7 +1126,8 @@ class ChunkConformer(_ModelBase):
     def init_decoder_caches(self, B=1):
         """(helper_mha_cache, helper_cnn_cache, decoder_mha_cache, decoder_cnn_cache, dec_inp) (:810-814)."""
         if B != 1:
-            raise NotImplementedError("the streaming entry points are single-stream, as the reference's")
+            raise NotImplementedError("the cache tuples are the single-stream contract, as the reference's; many streams: "
+                                      "open_streams(n) / stream_step")
         dev, d = self._h.device, self.dmodel
         z = lambda n: torch.zeros((n, 1, 0, d), dtype=torch.float32, device=dev)
         return (z(self.blocks["helper"]), z(self.blocks["helper"]), z(self.blocks["decoder"]), z(self.blocks["decoder"]),
@@ -1183,6 +1230,91 @@ class ChunkConformer(_ModelBase):
         valid_ctc, _, dec_mha, dec_cnn, unvalid_ctc = self._stack_stream_call("decoder", 3, dec_inp, dec_mha, dec_cnn, True)
         dec_inp = dec_inp[:, valid_ctc.shape[1]:]
         return valid_ctc, unvalid_ctc, (helper_mha, helper_cnn, dec_mha, dec_cnn, dec_inp)
+
+    # ---- many streams per call, state on the device (mi355asr_chunk_streams_*) ---------------
+    def open_streams(self, n_streams):
+        """-> ChunkStreams: `n_streams` slots of device state, every slot a fresh stream."""
+        h = self._h
+        if not h.built:
+            self._build()
+        chunk_num, hop, _, win = self._stream_cfg()
+        if chunk_num != 16:
+            raise NotImplementedError("batched streams: chunk_num %d, the kernels are laid out for 16" % chunk_num)
+        sb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(h.lib.mi355asr_chunk_streams_bytes(h.ptr, int(n_streams), ctypes.byref(sb), ctypes.byref(wb)))
+        st = ChunkStreams(int(n_streams), chunk_num * hop, win["decoder"][1])
+        st.buf = torch.empty(sb.value, dtype=torch.uint8, device=h.device)
+        st.ws = torch.empty(wb.value, dtype=torch.uint8, device=h.device)
+        self.reset_streams(st, None)
+        return st
+
+    def reset_streams(self, state, slots=None):
+        """the given slots (None: all) become fresh streams."""
+        h = self._h
+        tab = None if slots is None else np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        with torch.cuda.device(h.device):
+            _lib.check(h.lib.mi355asr_chunk_streams_reset(h.ptr, _p(state.buf), state.n_streams,
+                                                          tab.ctypes.data_as(ctypes.c_void_p) if tab is not None else None,
+                                                          0 if tab is None else len(tab), h._stream()))
+        state.guard.reset(range(state.n_streams) if tab is None else tab.tolist())
+
+    def stream_step(self, state, slots, packets, n_samples=None, want_logits=False):
+        """One tick: slot slots[i] takes packets[i] (wav_buf_length samples; a stream's last packet may be shorter: pass a
+        list of arrays, or a padded [n, wav_buf_length] array with n_samples).  -> {slot: dict(phone_ids i32 [4], n_picked,
+        text_ids i32 [n_valid + n_unvalid], n_valid, n_unvalid)}; with want_logits also phone_logits [4, Vp], text_logits
+        [n_valid + n_unvalid, Vt] and picker_hidden [4, d] (torch, on the device)."""
+        h = self._h
+        dev = h.device
+        slots = [int(v) for v in slots]
+        n, Wb = len(slots), state.wav_buf_length
+        if n_samples is None and not (torch.is_tensor(packets) or (isinstance(packets, np.ndarray) and packets.ndim == 2)):
+            rows = [np.asarray(r, np.float32).reshape(-1) for r in packets]
+            n_samples = [len(r) for r in rows]
+            if any(k > Wb for k in n_samples):
+                raise ValueError("a packet holds at most %d samples" % Wb)
+            pk = np.zeros((len(rows), Wb), np.float32)
+            for i, r in enumerate(rows):
+                pk[i, :len(r)] = r
+            packets = pk
+        pk = h.to_device(packets).reshape(-1, Wb)
+        if pk.shape[0] != n:
+            raise ValueError("%d slots, %d packets" % (n, pk.shape[0]))
+        lens = [Wb] * n if n_samples is None else [int(v) for v in n_samples]
+        state.guard.check(slots, lens)
+        short = any(k != Wb for k in lens)
+        TP, TPd = 4, state.win_back + 4
+        ints = torch.empty(n * (TP + TPd + 3), dtype=torch.int32, device=dev)     # every integer result: one copy back
+        o = 0
+        parts = {}
+        for name, k in (("phone_argmax", n * TP), ("n_picked", n), ("text_argmax", n * TPd), ("n_valid", n), ("n_unvalid", n)):
+            parts[name] = ints[o:o + k]
+            o += k
+        bufs = {}
+        if want_logits:
+            bufs["phone_logits"] = torch.empty((n, TP, self.phone_num_classes), dtype=torch.float32, device=dev)
+            bufs["text_logits"] = torch.empty((n, TPd, self.txt_num_classes), dtype=torch.float32, device=dev)
+            bufs["picker_hidden"] = torch.empty((n, TP, self.dmodel), dtype=torch.float32, device=dev)
+        outs = _lib.ChunkStreamsOutputs(**{k: v.data_ptr() for k, v in list(parts.items()) + list(bufs.items())})
+        tab = np.asarray(slots, np.int32)
+        ns = np.asarray(lens, np.int32)
+        with torch.cuda.device(dev):
+            _lib.check(h.lib.mi355asr_chunk_streams_step(h.ptr, _p(state.buf), state.n_streams, tab.ctypes.data_as(ctypes.c_void_p), n,
+                                                         _p(pk), ns.ctypes.data_as(ctypes.c_void_p) if short else None,
+                                                         ctypes.byref(outs), _p(state.ws), state.ws.numel(), h._stream()))
+        state.guard.commit(slots, lens)
+        r = ints.cpu().numpy()
+        pa, npk = r[:n * TP].reshape(n, TP), r[n * TP:n * TP + n]
+        ta = r[n * TP + n:n * TP + n + n * TPd].reshape(n, TPd)
+        nv, nu = r[-2 * n:-n], r[-n:]
+        out = {}
+        for i, slot in enumerate(slots):
+            k = int(nv[i] + nu[i])
+            out[slot] = {"phone_ids": pa[i].copy(), "n_picked": int(npk[i]), "text_ids": ta[i, :k].copy(),
+                         "n_valid": int(nv[i]), "n_unvalid": int(nu[i])}
+            if want_logits:
+                out[slot].update(phone_logits=bufs["phone_logits"][i], text_logits=bufs["text_logits"][i, :k],
+                                 picker_hidden=bufs["picker_hidden"][i])
+        return out
 
     def feature_pick(self, encoder_hidden_states, ctc_outs, max_T=None):
         """ChunkConformer.feature_pick (:913-999): keep the frames whose argmax is not the blank, compacted per
