@@ -143,6 +143,38 @@ int mi355asr_ctc_forward(mi355asr_model* m, const float* enc_dev, int32_t B, int
 int mi355asr_ctc_greedy(const int32_t* frame_argmax_dev, const int32_t* in_len_dev, int32_t B, int32_t T,
                         int32_t blank, int32_t* ids_dev, int32_t* out_len_dev, void* stream);
 
+/* replaces: tf.keras.backend.ctc_batch_cost(y_true, y_pred, input_length, label_length) of CTCTrainer._train_step /
+ * _eval_step (asr/trainer/ctc_runners.py:91,133) and ChunkConformer.train_step / test_step
+ * (chunk_conformer_blocks.py:1058-1075, 1142-1159): tf.compat.v1.nn.ctc_loss on log(y_pred + 1e-7), which applies a
+ * softmax to its inputs, so a frame's class distribution is q = (p + 1e-7) / sum_k (p_k + 1e-7); repeats merged;
+ * loss_b = -log sum_paths prod_t q[b, t, pi_t] over the frames t < in_len[b] and the labels labels[b, :label_len[b]].
+ * Model-independent.  x_dev f32 [B, T, V]: probabilities (is_logits = 0, ctc_batch_cost's own argument; loss only, a
+ * non-NULL grad_dev is rejected) or logits (p = softmax(x); grad_dev, if given, receives d loss_b / d x through the
+ * whole chain softmax -> + 1e-7 -> log -> log-softmax -> CTC, rows t >= in_len[b] are 0).  in_len_dev i32 [B] may be
+ * NULL (= T); labels_dev i32 [B, U]; label_len_dev i32 [B] (0 is legal: the all-blank path); `blank` is an argument (the
+ * reference's is V - 1).  loss_dev f32 [B].
+ * Not the reference's behaviour, on purpose: a target that no path of in_len[b] frames can emit (in_len < label_len +
+ * adjacent repeats; also a label outside [0, V) or equal to the blank) makes TensorFlow raise; here loss = +inf and
+ * the utterance's gradient rows are 0, with no NaN anywhere.
+ * Returns -1 with a message, launching nothing, for V < 2, blank outside [0, V), U above the built limit (511), a
+ * workspace smaller than mi355asr_ctc_loss_workspace_bytes says, and NULL outputs.  No allocation, no host
+ * synchronisation; the result of a row is bit-identical from run to run and whatever else is in the batch. */
+int mi355asr_ctc_loss_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t U, int32_t want_grad, size_t* bytes);
+int mi355asr_ctc_loss(const float* x_dev, int32_t is_logits, const int32_t* in_len_dev, const int32_t* labels_dev,
+                      const int32_t* label_len_dev, int32_t B, int32_t T, int32_t V, int32_t U, int32_t blank,
+                      float* loss_dev, float* grad_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* Forced alignment: the max-plus (Viterbi) pass over the lattice that mi355asr_ctc_loss sums over -- the token times
+ * ASR.offline_stt (test_asr.py:186-200) does not return.  Arguments as for mi355asr_ctc_loss.
+ * path_dev i32 [B, T]: the class of every frame on the best path (-1 at t >= in_len[b]); spans_dev i32 [B, U, 2]: first
+ * and last frame of each label (-1 for unused entries); score_dev f32 [B]: log of the best path's probability under q.
+ * An infeasible target: score -inf, path and spans -1. */
+int mi355asr_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t U, size_t* bytes);
+int mi355asr_ctc_align(const float* x_dev, int32_t is_logits, const int32_t* in_len_dev, const int32_t* labels_dev,
+                       const int32_t* label_len_dev, int32_t B, int32_t T, int32_t V, int32_t U, int32_t blank,
+                       int32_t* path_dev, int32_t* spans_dev, float* score_dev, void* ws_dev, size_t ws_bytes,
+                       void* stream);
+
 /* replaces: ctc_beam_search_decoder_batch(probs_split, vocabulary, beam_size, num_processes, cutoff_prob,
  * cutoff_top_n, ext_scorer = nullptr) of externals/ctc_decoders (ctc_beam_search_decoder.cpp:18-187, 426-459;
  * SWIG entry decoders.i) -- the scorer-less CTC prefix beam search.  Blank = class V-1, vocabulary = classes

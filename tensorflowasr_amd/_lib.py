@@ -88,6 +88,10 @@ SIGNATURES = {
     "mi355asr_encoder_forward": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
     "mi355asr_ctc_forward": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mi355asr_ctc_greedy": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "mi355asr_ctc_loss_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_ctc_loss": (ctypes.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi355asr_ctc_align_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_ctc_align": (ctypes.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_ctc_prefix_beam_host": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
     "mi355asr_ctc_prefix_beam": (ctypes.c_int, [_P, _I, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P,
                                                 _P, _SZ, _P]),

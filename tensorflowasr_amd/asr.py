@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from .featurizers import SpeechFeaturizer, TextFeaturizer
-from .models import ConformerEncoder, CTCDecoder, StreamingConformerEncoder, Translator, ctc_greedy_decode
+from .models import ConformerEncoder, CTCDecoder, StreamingConformerEncoder, Translator, ctc_forced_align, ctc_greedy_decode
 
 
 class ASR:
@@ -128,6 +128,28 @@ class ASR:
         ctc_row, txt_row = ctc_decode[0].cpu().numpy(), translator_out[0].cpu().numpy()
         self.timings["offline_stt"] = time.time() - t0
         return self._finish(ctc_row, txt_row)
+
+    def align(self, wav_or_path, phones):
+        """When each phone was spoken: encoder -> CTC logits -> forced alignment (models.ctc_forced_align) of `phones` (a
+        space-separated string, or a list of tokens or of ids) to the utterance.  -> [(phone, start_s, end_s), ...]: start_s =
+        first frame x the frame period, end_s = (last frame + 1) x the frame period, the period being reduction_factor x
+        stride_ms (40 ms for the shipped configurations).  Raises ValueError when the utterance has too few frames for them.
+        The score of the alignment and its frames are kept in self.last_alignment (score, spans [U, 2])."""
+        data = self.speech_featurizer.load_wav(wav_or_path) if isinstance(wav_or_path, (str, os.PathLike)) else wav_or_path
+        tokens = phones.split() if isinstance(phones, str) else list(phones)
+        ids = [int(t) if isinstance(t, (int, np.integer)) else self.phone_featurizer.token_to_index[t] for t in tokens]
+        enc_outputs = self.encoder(np.asarray(data, np.float32).reshape([1, -1, 1]), training=False)
+        logits = self.ctc_model(enc_outputs, training=False)
+        # the blank is the LAST class, as tf.keras.backend.ctc_decode and ctc_batch_cost have it (see _phone_ids)
+        _, spans, score = ctc_forced_align(logits, np.asarray([ids], np.int32).reshape(1, len(ids)),
+                                           blank=self.phone_featurizer.num_classes - 1)
+        spans, score = spans[0].cpu().numpy(), float(score[0].item())
+        if not np.isfinite(score):
+            raise ValueError("%d phones cannot be aligned to %d frames" % (len(ids), logits.shape[1]))
+        self.last_alignment = (score, spans)
+        period = self.model_config["reduction_factor"] * self.speech_config["stride_ms"] / 1000.0
+        return [(self.phone_featurizer.index_to_token[i], float(a) * period, float(b + 1) * period)
+                for i, (a, b) in zip(ids, spans)]
 
     def offline_stt_batch(self, items, max_batch_samples=None):
         """offline_stt_wave for every item of a list -- paths or 1-D waveforms -- in ragged batches: one encoder, CTC and

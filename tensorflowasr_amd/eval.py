@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .asr import ASR
-from .models import ctc_greedy_decode
+from .models import ctc_greedy_decode, ctc_loss
 
 
 # ---- utils/xer.py ---------------------------------------------------------------------------------------------
@@ -195,11 +195,16 @@ class EvalList:
 # ---- asr/tester/am_tester.py ----------------------------------------------------------------------------------
 class AMTester(ASR):
     """`AMTester(config)`: same models / checkpoints as `ASR`, evaluated over batches
-    `(features [B,L,1], input_length [B], phone_labels [B,P], phone_label_length [B], text_labels [B,Q])`."""
+    `(features [B,L,1], input_length [B], phone_labels [B,P], phone_label_length [B], text_labels [B,Q])`.
+    with_ctc_loss=True adds the `ctc_loss` metric of CTCTrainer._eval_step (asr/trainer/ctc_runners.py:125-150): the mean of
+    tf.keras.backend.ctc_batch_cost(phone_labels, softmax(logits), input_length, phone_label_length) over the utterances."""
 
-    def __init__(self, config, device="cuda:0", load_checkpoint=True):
+    def __init__(self, config, device="cuda:0", load_checkpoint=True, with_ctc_loss=False):
         self.config = config
+        self.with_ctc_loss = bool(with_ctc_loss)
         self.eval_metrics = {k: _Mean() for k in ("phone_ser", "phone_cer", "txt_ser", "txt_cer")}
+        if self.with_ctc_loss:
+            self.eval_metrics["ctc_loss"] = _Mean()
         self.ctc_nums = [0, 0, 0, 0]          # n, s, i, d
         self.translator_nums = [0, 0, 0, 0]
         self.steps, self.all_steps = 0, 0
@@ -222,9 +227,13 @@ class AMTester(ASR):
 
     def _eval_step(self, batch):
         """am_tester.py:34-89."""
-        features, input_length, phone_labels, _, tar_label = batch
+        features, input_length, phone_labels, phone_label_length, tar_label = batch
         enc_output = self.encoder(features, training=False)
-        _, frame_ids = self.ctc_model(enc_output, training=False, return_argmax=True, return_logits=False)
+        logits, frame_ids = self.ctc_model(enc_output, training=False, return_argmax=True, return_logits=self.with_ctc_loss)
+        if self.with_ctc_loss:
+            # ctc_batch_cost on softmax(logits): the logits entry of the loss takes the softmax inside its row kernel
+            for v in ctc_loss(logits, phone_labels, input_length, phone_label_length).cpu().numpy():
+                self.eval_metrics["ctc_loss"].update_state(v)
         # tf.keras.backend.ctc_decode treats the LAST class as the blank whatever `blank_at_zero` says (am_tester.py:38-40)
         ids, lens = ctc_greedy_decode(frame_ids, input_length, blank=self.phone_featurizer.num_classes - 1)
         ctc_decode = ids[:, :max(int(lens.max().item()), 1)].clamp_(min=0).contiguous()

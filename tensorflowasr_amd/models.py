@@ -854,6 +854,91 @@ def ctc_prefix_beam_decode(x, input_length=None, beam_width=10, cutoff_prob=0.99
     return ids, lens, scores, n_hyp
 
 
+def _ctc_lattice_inputs(x, labels, input_length, label_length, blank, device):
+    """the common argument handling of ctc_loss / ctc_forced_align: x f32 [B,T,V] and labels i32 [B,U] on the device, lengths
+    i32 [B] there (input_length may stay None = T).  Labels that arrive on the host are checked here (inside [0, V), not the
+    blank); labels already on the device are not read back -- the kernels answer such a row like an infeasible one."""
+    xt = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    dev = torch.device(device) if device is not None else (xt.device if xt.is_cuda else torch.device("cuda:0"))
+    if xt.dim() != 3:
+        raise ValueError("x: [B, T, V], got %s" % (tuple(xt.shape),))
+    B, T, V = (int(v) for v in xt.shape)
+    blank = V - 1 if blank is None else int(blank)
+    lt = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+    if lt.dim() != 2 or lt.shape[0] != B:
+        raise ValueError("labels: [B, U] with B=%d, got %s" % (B, tuple(lt.shape)))
+    U = int(lt.shape[1])
+
+    def lengths(v, default):
+        if v is None:
+            return None if default is None else torch.full((B,), default, dtype=torch.int32, device=dev)
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+        t = t.reshape(-1)                                  # the reference passes [B, 1]
+        if t.numel() != B:
+            raise ValueError("lengths: %d values for a batch of %d" % (t.numel(), B))
+        return t.to(device=dev, dtype=torch.int32).contiguous()
+
+    ll_on_device = torch.is_tensor(label_length) and label_length.is_cuda
+    if not lt.is_cuda and not ll_on_device and U > 0 and V >= 2 and 0 <= blank < V:
+        n = np.full((B,), U) if label_length is None else np.asarray(label_length).reshape(-1)
+        lh = lt.numpy()
+        used = np.arange(U)[None, :] < np.clip(n, 0, U)[:, None]
+        if (((lh < 0) | (lh >= V) | (lh == blank)) & used).any():
+            raise _lib.Mi355AsrError("ctc: a label is outside [0, %d) or equals the blank (%d)" % (V, blank))
+    xt = xt.to(device=dev, dtype=torch.float32).contiguous()
+    lt = lt.to(device=dev, dtype=torch.int32).contiguous()
+    return xt, lt, lengths(input_length, None), lengths(label_length, U), B, T, V, U, blank, dev
+
+
+def ctc_loss(logits, labels, input_length=None, label_length=None, blank=None, return_grad=False, device=None, is_logits=True):
+    """The CTC loss of tf.keras.backend.ctc_batch_cost (ctc_runners.py:91,133) from logits: p = softmax(logits), the frame's
+    class distribution q = (p + 1e-7) / sum(p + 1e-7), loss_b = -log sum over the alignments of labels[b, :label_length[b]]
+    in the frames t < input_length[b] (`mi355asr_ctc_loss`).  blank defaults to V - 1.
+    -> loss f32 [B]; with return_grad=True (loss, d loss_b / d logits f32 [B, T, V]), rows t >= input_length[b] exactly 0.
+    A target that cannot be aligned (input_length < label_length + adjacent repeats) gives +inf and a zero gradient, where
+    TensorFlow raises."""
+    lib = _lib.lib()
+    xt, lt, il, ll, B, T, V, U, blank, dev = _ctc_lattice_inputs(logits, labels, input_length, label_length, blank, device)
+    if return_grad and not is_logits:
+        raise ValueError("the gradient is with respect to logits")
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.mi355asr_ctc_loss_workspace_bytes(B, T, V, U, int(bool(return_grad)), ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, T, V), dtype=torch.float32, device=dev) if return_grad else None
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mi355asr_ctc_loss(_p(xt), int(bool(is_logits)), _p(il), _p(lt) if U else None, _p(ll), B, T, V, U, blank,
+                                         _p(loss), _p(grad), _p(ws), nbytes.value, st))
+    return (loss, grad) if return_grad else loss
+
+
+def ctc_batch_cost(y_true, y_pred, input_length, label_length, device=None):
+    """tf.keras.backend.ctc_batch_cost(y_true [B,U], y_pred [B,T,V] probabilities, input_length [B,1], label_length [B,1])
+    -> f32 [B,1], the blank being the last class (ctc_runners.py:91,133; chunk_conformer_blocks.py:1058-1075)."""
+    return ctc_loss(y_pred, y_true, input_length, label_length, device=device, is_logits=False).reshape(-1, 1)
+
+
+def ctc_forced_align(x, labels, input_length=None, label_length=None, blank=None, is_logits=True, device=None):
+    """The most probable alignment of labels[b, :label_length[b]] to the frames t < input_length[b] under the class
+    distribution of ctc_loss (`mi355asr_ctc_align`): -> (path i32 [B,T]: class per frame, -1 past the utterance;
+    spans i32 [B,U,2]: first and last frame of every label, -1 where unused; score f32 [B]: log-probability of that path;
+    -inf, with path and spans -1, when the labels cannot be aligned)."""
+    lib = _lib.lib()
+    xt, lt, il, ll, B, T, V, U, blank, dev = _ctc_lattice_inputs(x, labels, input_length, label_length, blank, device)
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.mi355asr_ctc_align_workspace_bytes(B, T, V, U, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, U, 2), dtype=torch.int32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mi355asr_ctc_align(_p(xt), int(bool(is_logits)), _p(il), _p(lt) if U else None, _p(ll), B, T, V, U, blank,
+                                          _p(path), _p(spans) if U else None, _p(score), _p(ws), nbytes.value, st))
+    return path, spans, score
+
+
 class ChunkBeamPipeline:
     """ChunkConformer `predict` of batch n + 1 overlapped with the prefix beam search of batch n (round 3).
 
