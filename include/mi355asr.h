@@ -177,7 +177,7 @@ int mi355asr_ctc_align(const float* x_dev, int32_t is_logits, const int32_t* in_
 
 /* replaces: ctc_beam_search_decoder_batch(probs_split, vocabulary, beam_size, num_processes, cutoff_prob,
  * cutoff_top_n, ext_scorer = nullptr) of externals/ctc_decoders (ctc_beam_search_decoder.cpp:18-187, 426-459;
- * SWIG entry decoders.i) -- the scorer-less CTC prefix beam search.  Blank = class V-1, vocabulary = classes
+ * SWIG entry decoders.i) -- the CTC prefix beam search without a scorer (with one: mi355asr_ctc_prefix_beam_lm* below).  Blank = class V-1, vocabulary = classes
  * 0..V-2 (as the reference assigns blank_id = vocabulary.size()).  Token ids are returned instead of the
  * concatenated vocabulary strings.  Outputs are HOST buffers: ids i32 [B, beam, max_len] (-1 padded, hypotheses
  * best first), lens i32 [B, beam], scores f32 [B, beam] (log prob), n_hyp i32 [B] (number of valid hypotheses).
@@ -227,6 +227,49 @@ int mi355asr_beam_decode(mi355asr_beam* d, const float* probs_host, int32_t T, i
                          int32_t* lens_host, float* scores_host, int32_t* n_hyp_host);
 int mi355asr_beam_reset(mi355asr_beam* d);
 int mi355asr_beam_destroy(mi355asr_beam* d);
+
+/* The external scorer of the prefix beam search: a back-off n-gram language model in CHARACTER-BASED mode.
+ * replaces: Scorer(alpha, beta, lm_path, vocab_list) of externals/ctc_decoders (scorer.h, scorer.cpp; KenLM behind
+ * get_log_cond_prob, scorer.cpp:74-93) as ctc_beam_search_decoder.cpp:64-73, 84-86, 111-128 use it.  The word-based mode
+ * (a dictionary FST over OpenFST) is not built.  The ARPA file is read by the caller (tensorflowasr_amd/ngram.py); the
+ * library takes the model as LM-word ids: 0 = out of vocabulary, 1 .. counts[0] = the unigrams.
+ *   mi355asr_lm_create: order 1 .. 6; counts i64 [order]; words i32 = for m = 1 .. order, counts[m-1] n-grams of m ids each
+ *     (w_1 .. w_m, w_m the predicted word); logp / backoff f32, one per n-gram in the same sequence (log10, as KenLM keeps
+ *     them; the back-off of the highest order is ignored); class_word i32 [n_classes]: acoustic class -> LM word, 0 for a
+ *     class the model does not know (and for "<unk>"); bos_word: the id of "<s>" (0: none); space_class: the " " class or
+ *     -2 -- make_ngram stops at a space and leaves empty words behind it (scorer.cpp:164-194), so a space among the last
+ *     `order` tokens scores OOV_SCORE, which is what mapping it to word 0 does.  The n-grams are packed once into one
+ *     open-addressed table keyed by 64 bits of the ids (csrc/lm_table.h; a repeated key is MI355ASR_EINVAL), shared by the
+ *     host and the device search, uploaded to a device on first use and read-only afterwards.
+ *   mi355asr_lm_score: for verification (as mi355asr_beam_math_eval): out[i] = get_log_cond_prob of the i-th of n n-grams
+ *     (i32 [n, order], w_1 .. w_order, "<s>"-padded by the caller, 0 = OOV) as the float KenLM returns: OOV_SCORE = -1000 when
+ *     any word is OOV, else logp of the longest stored suffix + the back-offs of the contexts backed off from, shortest
+ *     first, added in float.  HOST pointers; on_device != 0 evaluates them in a kernel with the device search's own routine.
+ *   mi355asr_ctc_prefix_beam_lm_host / _lm / mi355asr_beam_create_lm: the three searches above with (lm, alpha, beta):
+ *     float score = (float)(cond * alpha); log_p += score; log_p += beta (float += double) for every new or re-reached
+ *     prefix, log10 values used as they are; the per-frame min_cutoff / full_beam pruning of the scorer path; the returned
+ *     scores include the LM terms.  lm NULL is the scorer-less search.  lm must have n_classes = V - 1.  The device search
+ *     serves beam_size <= 128, cutoff_top_n <= 40, order <= 6 (ws_dev of mi355asr_ctc_prefix_beam_lm_workspace_bytes);
+ *     anything else, or MI355ASR_BEAM_DEVICE=0, runs the host search on the device's top-n lists. */
+typedef struct mi355asr_lm mi355asr_lm;
+int mi355asr_lm_create(int32_t order, const int64_t* counts, const int32_t* words, const float* logp, const float* backoff,
+                       const int32_t* class_word, int32_t n_classes, int32_t bos_word, int32_t space_class, mi355asr_lm** out);
+int mi355asr_lm_destroy(mi355asr_lm* lm);
+int mi355asr_lm_score(const mi355asr_lm* lm, const int32_t* ngrams_host, int32_t n, float* out_host, int32_t on_device,
+                      void* stream);
+int mi355asr_ctc_prefix_beam_lm_host(const float* probs_host, const int32_t* in_len_host, int32_t B, int32_t T, int32_t V,
+                                     int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                                     int32_t max_len, const mi355asr_lm* lm, double alpha, double beta, int32_t* ids_host,
+                                     int32_t* lens_host, float* scores_host, int32_t* n_hyp_host);
+int mi355asr_ctc_prefix_beam_lm(const float* x_dev, int32_t is_logits, const int32_t* in_len_host, int32_t B, int32_t T,
+                                int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                                int32_t max_len, const mi355asr_lm* lm, double alpha, double beta, int32_t* ids_host,
+                                int32_t* lens_host, float* scores_host, int32_t* n_hyp_host, void* ws_dev, size_t ws_bytes,
+                                void* stream);
+int mi355asr_ctc_prefix_beam_lm_workspace_bytes(int32_t B, int32_t T, int32_t cutoff_top_n, int32_t beam_size, int32_t max_len,
+                                                size_t* bytes);
+int mi355asr_beam_create_lm(int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, const mi355asr_lm* lm,
+                            double alpha, double beta, mi355asr_beam** out);
 
 /* encoder + CTCDecoder + greedy in one call: wav [B,L] -> ids i32 [B,T_total] (-1 padded), out_len i32 [B].
  * This is the timed region of bench.py (offline_stt steps 3-5, test_asr.py:191-198). */

@@ -100,6 +100,15 @@ SIGNATURES = {
     "mi355asr_beam_decode": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mi355asr_beam_reset": (ctypes.c_int, [_P]),
     "mi355asr_beam_destroy": (ctypes.c_int, [_P]),
+    "mi355asr_lm_create": (ctypes.c_int, [_I, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(_P)]),
+    "mi355asr_lm_destroy": (ctypes.c_int, [_P]),
+    "mi355asr_lm_score": (ctypes.c_int, [_P, _P, _I, _P, _I, _P]),
+    "mi355asr_ctc_prefix_beam_lm_host": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, ctypes.c_double,
+                                                        ctypes.c_double, _P, _P, _P, _P]),
+    "mi355asr_ctc_prefix_beam_lm": (ctypes.c_int, [_P, _I, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, ctypes.c_double,
+                                                   ctypes.c_double, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mi355asr_ctc_prefix_beam_lm_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi355asr_beam_create_lm": (ctypes.c_int, [_I, _I, ctypes.c_double, _I, _P, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_P)]),
     "mi355asr_recognize": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_encoder_forward_ragged": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mi355asr_ctc_forward_ragged": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),

@@ -63,10 +63,23 @@ class ChunkASR:
         return data / np.abs(data.max())               # test_chunk_asr.py:49 (sic: abs of the max, not max of the abs)
 
     def offline_stt(self, wav_path):
-        """runner.predict on the whole utterance + greedy CTC decode (test_chunk_asr.py:56, 124-137) -> text"""
+        """runner.predict on the whole utterance + greedy CTC decode (test_chunk_asr.py:56, 124-137) -> text; with
+        `beam_width` > 1 in the text vocabulary's config, the prefix beam search (and its `lm_config` scorer) instead"""
         data = self.load_wav(wav_path)
         logits, _ = self.runner.predict(data.reshape([1, -1, 1]))
+        beam = int(self.text_featurizer.decoder_config.get("beam_width", 1) or 1)
+        if beam > 1:
+            return "".join(self.text_featurizer.iextract(self._beam_text(logits, beam)))
         return "".join(self.text_featurizer.iextract(_ctc_text(logits, self.text_featurizer.num_classes - 1)))
+
+    def _beam_text(self, logits, beam):
+        """beam_width > 1: the best hypothesis of the prefix beam search on the text logits, with the vocabulary's scorer
+        (lm_config) if it has one -> id list without zeros, as _ctc_text returns"""
+        from .models import ctc_prefix_beam_decode
+        if logits.shape[1] == 0:
+            return []
+        ids, lens, _, _ = ctc_prefix_beam_decode(logits, None, beam, is_logits=True, ext_scorer=self.text_featurizer.scorer)
+        return [int(n) for n in ids[0, 0, :int(lens[0, 0])] if n != 0]
 
     def stream_call(self, wav_path, verbose=False):
         """test_chunk_asr.py:47-139 -> {"streaming": [(seconds_heard, phones, text), ...], "offline": text}"""

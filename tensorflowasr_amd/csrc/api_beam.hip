@@ -2,7 +2,56 @@
 // search on the device or on host threads) and the stateful mi355asr_beam_* decoder handle.  Kernels: beam_device.hip; host search: beam.hip.
 #include "model.h"
 
+namespace {
+// the scorer of a call: lm null = the scorer-less search; otherwise its class map has to cover the V - 1 non-blank classes
+int check_scorer(const mi355asr_lm* lm, int V, double alpha, double beta) {
+  if (!lm) return 0;
+  int n = 0;
+  (void)mi355asr_lm_class_word(lm, &n);
+  if (n != V - 1) return fail(MI355ASR_EINVAL, "the language model was created for %d classes, the search has %d + blank", n, V - 1);
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(MI355ASR_EINVAL, "alpha and beta must be finite");
+  return 0;
+}
+int prefix_beam_impl(const float* x, int32_t is_logits, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                     int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                     int32_t max_len, const BeamLm* sc, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp, void* ws,
+                     size_t ws_bytes, void* stream);
+}  // namespace
+
 extern "C" {
+
+int mi355asr_ctc_prefix_beam_lm_host(const float* probs, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                                     int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                                     int32_t max_len, const mi355asr_lm* lm, double alpha, double beta, int32_t* ids,
+                                     int32_t* lens, float* scores, int32_t* n_hyp) {
+  if (!probs || !ids || !lens || !scores || !n_hyp) return fail(MI355ASR_EINVAL, "null pointer");
+  if (B <= 0 || T <= 0 || V < 2 || beam_size <= 0 || max_len <= 0 || cutoff_top_n <= 0)
+    return fail(MI355ASR_EINVAL, "bad beam-search argument (B=%d T=%d V=%d beam=%d max_len=%d top_n=%d)", B, T, V,
+                beam_size, max_len, cutoff_top_n);
+  if (int rc = check_scorer(lm, V, alpha, beta)) return rc;
+  const BeamLm sc{lm, alpha, beta};
+  return mi355asr_beam_host_lm_impl(probs, in_len, B, T, V, beam_size, cutoff_prob, cutoff_top_n, num_threads, max_len, &sc, ids,
+                                    lens, scores, n_hyp);
+}
+
+int mi355asr_ctc_prefix_beam_lm(const float* x, int32_t is_logits, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                                int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                                int32_t max_len, const mi355asr_lm* lm, double alpha, double beta, int32_t* ids, int32_t* lens,
+                                float* scores, int32_t* n_hyp, void* ws, size_t ws_bytes, void* stream) {
+  if (V >= 2)
+    if (int rc = check_scorer(lm, V, alpha, beta)) return rc;
+  const BeamLm sc{lm, alpha, beta};
+  return prefix_beam_impl(x, is_logits, in_len, B, T, V, beam_size, cutoff_prob, cutoff_top_n, num_threads, max_len, &sc, ids, lens,
+                          scores, n_hyp, ws, ws_bytes, stream);
+}
+
+int mi355asr_ctc_prefix_beam_lm_workspace_bytes(int32_t B, int32_t T, int32_t cutoff_top_n, int32_t beam_size, int32_t max_len,
+                                                size_t* bytes) {
+  if (!bytes || B <= 0 || T <= 0 || cutoff_top_n <= 0 || beam_size <= 0 || max_len <= 0) return fail(MI355ASR_EINVAL, "bad argument");
+  const size_t need = (size_t)B * T * (std::min(cutoff_top_n, 128) * 12 + 4);     // classes, probabilities, LM words; the blank's probability
+  *bytes = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
+  return 0;
+}
 
 int mi355asr_ctc_prefix_beam_host(const float* probs, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
                                   int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
@@ -19,6 +68,17 @@ int mi355asr_ctc_prefix_beam(const float* x, int32_t is_logits, const int32_t* i
                              int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
                              int32_t max_len, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp, void* ws,
                              size_t ws_bytes, void* stream) {
+  return prefix_beam_impl(x, is_logits, in_len, B, T, V, beam_size, cutoff_prob, cutoff_top_n, num_threads, max_len, nullptr, ids,
+                          lens, scores, n_hyp, ws, ws_bytes, stream);
+}
+}  // extern "C"
+
+namespace {
+int prefix_beam_impl(const float* x, int32_t is_logits, const int32_t* in_len, int32_t B, int32_t T, int32_t V,
+                     int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
+                     int32_t max_len, const BeamLm* sc, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp, void* ws,
+                     size_t ws_bytes, void* stream) {
+  const mi355asr_lm* lm = sc ? sc->lm : nullptr;
   if (!x || !ids || !lens || !scores || !n_hyp || !ws) return fail(MI355ASR_EINVAL, "null pointer");
   if (B <= 0 || T <= 0 || V < 2 || beam_size <= 0 || max_len <= 0 || cutoff_top_n <= 0)
     return fail(MI355ASR_EINVAL, "bad beam-search argument");
@@ -28,17 +88,22 @@ int mi355asr_ctc_prefix_beam(const float* x, int32_t is_logits, const int32_t* i
   const int N = std::min(cutoff_top_n, V);
   if (N > 128) return fail(MI355ASR_EINVAL, "cutoff_top_n=%d: the selection kernel supports up to 128", cutoff_top_n);
   const size_t frames = (size_t)B * T;
-  const size_t need = frames * N * (sizeof(int32_t) + sizeof(float));
+  // with a scorer: the LM words of the lists and the blank's probability per frame behind the two lists
+  const size_t need = frames * N * (sizeof(int32_t) + sizeof(float)) + (lm ? frames * N * sizeof(int32_t) + frames * sizeof(float) : 0);
   if (ws_bytes < need) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   int32_t* d_idx = (int32_t*)ws;
   float* d_p = (float*)((char*)ws + frames * N * sizeof(int32_t));
-  if (mi355asr_launch_topn(x, (int)frames, V, N, is_logits, d_idx, d_p, s) != 0)
+  int32_t* d_w = lm ? (int32_t*)(d_p + frames * N) : nullptr;
+  float* d_blank = lm ? (float*)(d_w + frames * N) : nullptr;
+  if (mi355asr_launch_topn(x, (int)frames, V, N, is_logits, d_idx, d_p, d_blank, s) != 0)
     return fail(MI355ASR_EHIP, "top-n kernel launch failed (V=%d needs %zu bytes of LDS)", V, (size_t)V * 4);
   // MI355ASR_BEAM_DEVICE=0: the prefix search on host threads (beam.hip) instead of the device kernel (beam_device.hip)
   static const bool dev_env = mi355_env("MI355ASR_BEAM_DEVICE", 1) != 0;
   const size_t need_dev = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
-  if (dev_env && mi355asr_beam_device_applicable(V, N, beam_size) && ws_bytes >= need_dev) {
+  const bool fits = lm ? mi355asr_beam_device_lm_applicable(V, N, beam_size, mi355asr_lm_host_view(lm)->order)
+                       : mi355asr_beam_device_applicable(V, N, beam_size);
+  if (dev_env && fits && ws_bytes >= need_dev) {
     char* w = (char*)ws + ((need + 255) & ~(size_t)255);
     BeamDeviceArgs a{};
     a.top_idx = d_idx; a.top_p = d_p; a.B = B; a.T = T; a.V = V; a.N = N; a.beam = beam_size;
@@ -75,7 +140,14 @@ int mi355asr_ctc_prefix_beam(const float* x, int32_t is_logits, const int32_t* i
       HIP_TRY(hipMemcpyAsync(d_len, src, n_nh, hipMemcpyHostToDevice, s));
       a.in_len = d_len;
     }
-    if (mi355asr_launch_beam_device(&a, s) != 0) return fail(MI355ASR_EHIP, "device beam search launch failed");
+    if (lm) {
+      BeamLmDeviceArgs l{};
+      const int32_t* d_map = nullptr;
+      if (mi355asr_lm_device_view(lm, &l.view, &d_map) != 0) return fail(MI355ASR_EHIP, "language model upload failed");
+      if (mi355asr_launch_lm_map(d_idx, frames * N, d_map, V - 1, d_w, s) != 0) return fail(MI355ASR_EHIP, "LM word kernel launch failed");
+      l.top_w = d_w; l.blank_p = d_blank; l.alpha = sc->alpha; l.beta = sc->beta;
+      if (mi355asr_launch_beam_device_lm(&a, &l, s) != 0) return fail(MI355ASR_EHIP, "device beam search (scorer) launch failed");
+    } else if (mi355asr_launch_beam_device(&a, s) != 0) return fail(MI355ASR_EHIP, "device beam search launch failed");
     long long prof[16] = {0};
     if (stage) {
       HIP_TRY(hipMemcpyAsync(stage, a.ids, span, hipMemcpyDeviceToHost, s));
@@ -107,10 +179,15 @@ int mi355asr_ctc_prefix_beam(const float* x, int32_t is_logits, const int32_t* i
   std::vector<float> h_p(frames * N);
   HIP_TRY(hipMemcpyAsync(h_idx.data(), d_idx, h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(h_p.data(), d_p, h_p.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  std::vector<float> h_blank(lm ? frames : 0);
+  if (lm) HIP_TRY(hipMemcpyAsync(h_blank.data(), d_blank, frames * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  return mi355asr_beam_topn_impl(h_idx.data(), h_p.data(), in_len, B, T, V, N, beam_size, cutoff_prob, cutoff_top_n,
-                                 num_threads, max_len, ids, lens, scores, n_hyp);
+  return mi355asr_beam_topn_lm_impl(h_idx.data(), h_p.data(), lm ? h_blank.data() : nullptr, in_len, B, T, V, N, beam_size, cutoff_prob,
+                                    cutoff_top_n, num_threads, max_len, sc, ids, lens, scores, n_hyp);
 }
+}  // namespace
+
+extern "C" {
 
 int mi355asr_beam_math_eval(int32_t kind, const float* in_dev, void* out_dev, int32_t n, void* stream) {
   if (!in_dev || !out_dev || n < 0 || kind < 0 || kind > 3) return fail(MI355ASR_EINVAL, "bad argument");
@@ -133,6 +210,17 @@ int mi355asr_beam_create(int32_t V, int32_t beam_size, double cutoff_prob, int32
   if (V < 2 || beam_size < 1 || cutoff_top_n < 1 || !(cutoff_prob > 0.0) || cutoff_prob > 1.0)
     return fail(MI355ASR_EINVAL, "beam decoder: need V >= 2, beam_size >= 1, cutoff_top_n >= 1, 0 < cutoff_prob <= 1");
   auto* d = new mi355asr_beam{mi355asr_beam_state_new(V, beam_size, cutoff_prob, cutoff_top_n), V, beam_size};
+  *out = d;
+  return 0;
+}
+int mi355asr_beam_create_lm(int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, const mi355asr_lm* lm,
+                            double alpha, double beta, mi355asr_beam** out) {
+  if (!out) return fail(MI355ASR_EINVAL, "null argument");
+  if (V < 2 || beam_size < 1 || cutoff_top_n < 1 || !(cutoff_prob > 0.0) || cutoff_prob > 1.0)
+    return fail(MI355ASR_EINVAL, "beam decoder: need V >= 2, beam_size >= 1, cutoff_top_n >= 1, 0 < cutoff_prob <= 1");
+  if (int rc = check_scorer(lm, V, alpha, beta)) return rc;
+  const BeamLm sc{lm, alpha, beta};
+  auto* d = new mi355asr_beam{mi355asr_beam_state_new_lm(V, beam_size, cutoff_prob, cutoff_top_n, &sc), V, beam_size};
   *out = d;
   return 0;
 }

@@ -3,6 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lm_table.h"
+
+struct mi355asr_lm;
+// the scorer of a search (replaces: Scorer* ext_scorer with its alpha / beta); lm null = the scorer-less search
+struct BeamLm {
+  const mi355asr_lm* lm;
+  double alpha, beta;
+};
+
 extern "C" {
 int mi355asr_beam_host_impl(const float* probs, const int32_t* in_len, int B, int T, int V, int beam_size,
                             double cutoff_prob, int cutoff_top_n, int num_threads, int max_len, int32_t* ids,
@@ -37,6 +46,32 @@ int mi355asr_launch_beam_device(const BeamDeviceArgs* a, hipStream_t s);
 // kind 0 expf(in[i]) -> float, 1 logf -> float, 2 log((double)in[i] + FLT_MIN) -> double, 3 log_sum_exp(in[i], in[n + i]) -> float,
 // evaluated by the device search's own routines (refmath.h)
 int mi355asr_launch_refmath_eval(int kind, const float* in, void* out, int n, hipStream_t s);
+// blank_p_dev (may be null): the probability of class V - 1 per frame, what the scorer's min_cutoff needs
 int mi355asr_launch_topn(const float* x_dev, int frames, int V, int N, int is_logits, int32_t* idx_dev, float* p_dev,
-                         hipStream_t s);
+                         float* blank_p_dev, hipStream_t s);
+
+// ---- the searches with an n-gram scorer (lm.hip: the table; beam.hip / beam_device.hip: the searches) ----
+const LmView* mi355asr_lm_host_view(const mi355asr_lm* lm);
+const int32_t* mi355asr_lm_class_word(const mi355asr_lm* lm, int* n_classes);       // class -> LM word (0: OOV), host
+// the table and the class map on the current device (uploaded on first use, kept until mi355asr_lm_destroy); 0 on success
+int mi355asr_lm_device_view(const mi355asr_lm* lm, LmView* view, const int32_t** class_word_dev);
+int mi355asr_beam_host_lm_impl(const float* probs, const int32_t* in_len, int B, int T, int V, int beam_size,
+                               double cutoff_prob, int cutoff_top_n, int num_threads, int max_len, const BeamLm* sc,
+                               int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp);
+int mi355asr_beam_topn_lm_impl(const int32_t* top_idx, const float* top_p, const float* blank_p, const int32_t* in_len,
+                               int B, int T, int V, int N, int beam_size, double cutoff_prob, int cutoff_top_n,
+                               int num_threads, int max_len, const BeamLm* sc, int32_t* ids, int32_t* lens, float* scores,
+                               int32_t* n_hyp);
+void* mi355asr_beam_state_new_lm(int V, int beam_size, double cutoff_prob, int cutoff_top_n, const BeamLm* sc);
+// what the device search with a scorer reads besides BeamDeviceArgs (device pointers)
+struct BeamLmDeviceArgs {
+  LmView view;
+  const int32_t* top_w;     // [B, T, N] LM word of top_idx (mi355asr_launch_lm_map)
+  const float* blank_p;     // [B, T] probability of the blank
+  double alpha, beta;
+};
+bool mi355asr_beam_device_lm_applicable(int V, int N, int beam, int order);
+int mi355asr_launch_lm_map(const int32_t* top_idx, size_t n, const int32_t* class_word_dev, int n_classes, int32_t* top_w,
+                           hipStream_t s);
+int mi355asr_launch_beam_device_lm(const BeamDeviceArgs* a, const BeamLmDeviceArgs* l, hipStream_t s);
 }

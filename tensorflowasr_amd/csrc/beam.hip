@@ -1,4 +1,4 @@
-// CTC prefix beam search (scorer-less), the decode step of BASELINE config 5.
+// CTC prefix beam search (scorer-less, or with the character-based n-gram scorer of lm_table.h), the decode step of BASELINE config 5.
 //
 // Reference: externals/ctc_decoders.zip -- ctc_beam_search_decoder.cpp:18-187 (search), decoder_utils.cpp:7-38
 // (get_pruned_log_probs), decoder_utils.h:41-49 (log_sum_exp), decoder_utils.cpp:137-147 (prefix_compare),
@@ -46,6 +46,7 @@ inline float log_sum_exp(float x, float y) {   // decoder_utils.h:41-49, T = flo
 struct Node {
   int ch, parent, first_child, next_sibling;
   float b_prev, nb_prev, b_cur, nb_cur, score;
+  float lm;       // scorer: (float)(get_log_cond_prob(make_ngram(node)) * alpha) -- depends on the node only, set when it is made
   int stamp;      // frame at which the node was last put on the candidate list
   int slot;       // this frame's tie-break word (Search::better)
   bool exists;
@@ -63,11 +64,11 @@ class Trie {
     Node& n = nodes[id];
     n.ch = ch; n.parent = parent; n.first_child = -1; n.next_sibling = -1;
     n.b_prev = n.nb_prev = n.b_cur = n.nb_cur = n.score = kNegInf;
-    n.stamp = -1; n.slot = 0; n.exists = true;
+    n.stamp = -1; n.slot = 0; n.exists = true; n.lm = 0.f;
     return id;
   }
   // PathTrie::get_path_trie (path_trie.cpp:37-91, dictionary-less branch)
-  int child(int p, int c) {
+  int child(int p, int c, bool* fresh = nullptr) {
     for (int k = nodes[p].first_child; k >= 0; k = nodes[k].next_sibling) {
       if (nodes[k].ch == c) {
         Node& n = nodes[k];
@@ -79,6 +80,7 @@ class Trie {
       }
     }
     const int id = make(c, p);
+    if (fresh) *fresh = true;
     nodes[id].next_sibling = nodes[p].first_child;
     nodes[p].first_child = id;
     return id;
@@ -140,6 +142,27 @@ struct Search {
   std::vector<int> prefixes, touched;
   int beam;
   int blank;
+  // the scorer (ctc_beam_search_decoder.cpp:64-73, 84-86, 111-128; character-based mode): null = the scorer-less search
+  const LmView* lm = nullptr;
+  const int32_t* class_word = nullptr;
+  double alpha = 0.0, beta = 0.0;
+
+  void set_scorer(const BeamLm* sc) {
+    if (!sc || !sc->lm) return;
+    lm = mi355asr_lm_host_view(sc->lm);
+    class_word = mi355asr_lm_class_word(sc->lm, nullptr);
+    alpha = sc->alpha;
+    beta = sc->beta;
+  }
+  // Scorer::make_ngram (scorer.cpp:164-194, character mode) of node id + get_log_cond_prob, times alpha, as the float the
+  // reference assigns it to (ctc_beam_search_decoder.cpp:122-125)
+  float lm_term(int id) const {
+    int32_t r[kLmMaxOrder] = {0, 0, 0, 0, 0, 0};
+    int n = 0;
+    for (int k = id; n < lm->order && trie.nodes[k].ch != -1; k = trie.nodes[k].parent) r[n++] = class_word[trie.nodes[k].ch];
+    for (; n < lm->order; ++n) r[n] = lm->bos;
+    return (float)((double)lm_cond(*lm, r) * alpha);
+  }
 
   void reset(int beam_size, int blank_id) {
     beam = beam_size;
@@ -166,9 +189,15 @@ struct Search {
     return a.slot < b.slot;
   }
 
-  void step(int t, const std::vector<Cand>& cands) {
+  // p_blank: the frame's blank probability (only read with a scorer)
+  void step(int t, const std::vector<Cand>& cands, float p_blank = 0.f) {
     touched.clear();
     const int nbm = (int)prefixes.size(), nc = (int)cands.size();
+    // the scorer's pruning (:64-73): the beam is in rank order, so its last entry is the worst one; the reference's `break`
+    // over the sorted beam (:84-86) skips exactly the pairs that fail the test, whatever the order among equal scores
+    const bool full_beam = lm && nbm == beam;
+    float min_cutoff = kNegInf;
+    if (lm) min_cutoff = (float)((double)trie.nodes[prefixes[nbm - 1]].score + std::log((double)p_blank) - std::max(0.0, beta));
     for (int i = 0; i < nbm; ++i) {
       trie.nodes[prefixes[i]].stamp = t;
       trie.nodes[prefixes[i]].slot = i;
@@ -178,6 +207,7 @@ struct Search {
       const float lp = cands[k].lp;
       for (int i = 0; i < nbm; ++i) {
         const int pi = prefixes[i];
+        if (full_beam && lp + trie.nodes[pi].score < min_cutoff) continue;
         if (c == blank) {
           Node& p = trie.nodes[pi];
           p.b_cur = log_sum_exp(p.b_cur, lp + p.score);
@@ -187,12 +217,18 @@ struct Search {
           Node& p = trie.nodes[pi];
           p.nb_cur = log_sum_exp(p.nb_cur, lp + p.nb_prev);
         }
-        const int qi = trie.child(pi, c);     // may reallocate trie.nodes
+        bool fresh = false;
+        const int qi = trie.child(pi, c, &fresh);     // may reallocate trie.nodes
+        if (lm && fresh) trie.nodes[qi].lm = lm_term(qi);
         const Node& p = trie.nodes[pi];
         Node& q = trie.nodes[qi];
         float log_p = kNegInf;
         if (c == p.ch && p.b_prev > kNegInf) log_p = lp + p.b_prev;
         else if (c != p.ch) log_p = lp + p.score;
+        if (lm) {                               // :122-127: float += float, then float += double
+          log_p += q.lm;
+          log_p = (float)((double)log_p + beta);
+        }
         q.nb_cur = log_sum_exp(q.nb_cur, log_p);
         if (q.stamp != t) { q.stamp = t; q.slot = nbm + i * nc + k; touched.push_back(qi); }
       }
@@ -291,7 +327,7 @@ __device__ __forceinline__ void topn_rounds(float* sh, int V, int N, int lane, b
 }
 
 __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, int V, int N, int is_logits,
-                                                  int32_t* __restrict__ out_idx, float* __restrict__ out_p) {
+                                                  int32_t* __restrict__ out_idx, float* __restrict__ out_p, float* __restrict__ out_blank) {
   extern __shared__ __align__(16) float sh[];
   __shared__ float cv[GT_CAP + EQ_CAP];
   __shared__ int ci[GT_CAP + EQ_CAP];
@@ -349,6 +385,7 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
     for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
     denom = s;
   }
+  if (out_blank && lane == 0) out_blank[frame] = is_logits ? __expf(sh[V - 1] - mx) / denom : sh[V - 1];
   if (N > 64) {
     topn_rounds(sh, V, N, lane, is_logits, mx, denom, out_idx, out_p);
     return;
@@ -418,7 +455,7 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
 // registers.
 template <int NR>
 __global__ __launch_bounds__(64) void topn_reg_kernel(const float* __restrict__ x, int V, int N, int is_logits,
-                                                      int32_t* __restrict__ out_idx, float* __restrict__ out_p) {
+                                                      int32_t* __restrict__ out_idx, float* __restrict__ out_p, float* __restrict__ out_blank) {
   __shared__ float cv[GT_CAP + EQ_CAP];
   __shared__ int ci[GT_CAP + EQ_CAP];
   const int lane = threadIdx.x;
@@ -454,6 +491,10 @@ __global__ __launch_bounds__(64) void topn_reg_kernel(const float* __restrict__ 
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
     denom = s;
+  }
+  if (out_blank && lane == 0) {             // the scorer's searches only: the blank's probability, read again (an L2 hit)
+    const float vb = row[V - 1];
+    out_blank[frame] = is_logits ? __expf(vb - mx) / denom : vb;
   }
   int rank = 0;
 #pragma unroll
@@ -539,15 +580,24 @@ extern "C" {
 int mi355asr_beam_host_impl(const float* probs, const int32_t* in_len, int B, int T, int V, int beam_size,
                             double cutoff_prob, int cutoff_top_n, int num_threads, int max_len, int32_t* ids,
                             int32_t* lens, float* scores, int32_t* n_hyp) {
+  return mi355asr_beam_host_lm_impl(probs, in_len, B, T, V, beam_size, cutoff_prob, cutoff_top_n, num_threads, max_len, nullptr,
+                                    ids, lens, scores, n_hyp);
+}
+
+int mi355asr_beam_host_lm_impl(const float* probs, const int32_t* in_len, int B, int T, int V, int beam_size,
+                               double cutoff_prob, int cutoff_top_n, int num_threads, int max_len, const BeamLm* sc,
+                               int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp) {
   run_batch(B, num_threads, [&](int b) {
     Search s;
+    s.set_scorer(sc);
     s.reset(beam_size, V - 1);
     std::vector<Cand> cands;
     std::vector<int> order;
     const int n = in_len ? std::max(0, std::min(in_len[b], T)) : T;
     for (int t = 0; t < n; ++t) {
-      pruned_from_row(probs + ((size_t)b * T + t) * V, V, cutoff_prob, cutoff_top_n, cands, order);
-      s.step(t, cands);
+      const float* row = probs + ((size_t)b * T + t) * V;
+      pruned_from_row(row, V, cutoff_prob, cutoff_top_n, cands, order);
+      s.step(t, cands, row[V - 1]);
     }
     n_hyp[b] = s.finish(max_len, ids + (size_t)b * beam_size * max_len, lens + (size_t)b * beam_size,
                         scores + (size_t)b * beam_size);
@@ -558,15 +608,24 @@ int mi355asr_beam_host_impl(const float* probs, const int32_t* in_len, int B, in
 int mi355asr_beam_topn_impl(const int32_t* top_idx, const float* top_p, const int32_t* in_len, int B, int T, int V,
                             int N, int beam_size, double cutoff_prob, int cutoff_top_n, int num_threads, int max_len,
                             int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp) {
+  return mi355asr_beam_topn_lm_impl(top_idx, top_p, nullptr, in_len, B, T, V, N, beam_size, cutoff_prob, cutoff_top_n, num_threads,
+                                    max_len, nullptr, ids, lens, scores, n_hyp);
+}
+
+int mi355asr_beam_topn_lm_impl(const int32_t* top_idx, const float* top_p, const float* blank_p, const int32_t* in_len,
+                               int B, int T, int V, int N, int beam_size, double cutoff_prob, int cutoff_top_n,
+                               int num_threads, int max_len, const BeamLm* sc, int32_t* ids, int32_t* lens, float* scores,
+                               int32_t* n_hyp) {
   run_batch(B, num_threads, [&](int b) {
     Search s;
+    s.set_scorer(sc);
     s.reset(beam_size, V - 1);
     std::vector<Cand> cands;
     const int n = in_len ? std::max(0, std::min(in_len[b], T)) : T;
     for (int t = 0; t < n; ++t) {
       const size_t o = ((size_t)b * T + t) * N;
       pruned_from_topn(top_idx + o, top_p + o, N, cutoff_prob, cutoff_top_n, cands);
-      s.step(t, cands);
+      s.step(t, cands, blank_p ? blank_p[(size_t)b * T + t] : 0.f);
     }
     n_hyp[b] = s.finish(max_len, ids + (size_t)b * beam_size * max_len, lens + (size_t)b * beam_size,
                         scores + (size_t)b * beam_size);
@@ -575,11 +634,11 @@ int mi355asr_beam_topn_impl(const int32_t* top_idx, const float* top_p, const in
 }
 
 int mi355asr_launch_topn(const float* x_dev, int frames, int V, int N, int is_logits, int32_t* idx_dev, float* p_dev,
-                         hipStream_t s) {
+                         float* blank_p_dev, hipStream_t s) {
   static const bool reg_off = mi355_env("MI355ASR_TOPN_REG", -1) == 0;
   if (N <= 64 && V >= 64 && V <= 64 * 144 && !reg_off) {
     const int nr = (V + 63) / 64;
-#define TOPN_REG(NR) hipLaunchKernelGGL(topn_reg_kernel<NR>, dim3(frames), dim3(64), 0, s, x_dev, V, N, is_logits, idx_dev, p_dev)
+#define TOPN_REG(NR) hipLaunchKernelGGL(topn_reg_kernel<NR>, dim3(frames), dim3(64), 0, s, x_dev, V, N, is_logits, idx_dev, p_dev, blank_p_dev)
     if (nr <= 24) TOPN_REG(24);
     else if (nr <= 64) TOPN_REG(64);
     else if (nr <= 96) TOPN_REG(96);
@@ -593,7 +652,7 @@ int mi355asr_launch_topn(const float* x_dev, int frames, int V, int N, int is_lo
     if (hipFuncSetAttribute((const void*)topn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return -2;
   }
-  hipLaunchKernelGGL(topn_kernel, dim3(frames), dim3(64), lds, s, x_dev, V, N, is_logits, idx_dev, p_dev);
+  hipLaunchKernelGGL(topn_kernel, dim3(frames), dim3(64), lds, s, x_dev, V, N, is_logits, idx_dev, p_dev, blank_p_dev);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -608,7 +667,11 @@ struct BeamState {
 };
 
 void* mi355asr_beam_state_new(int V, int beam_size, double cutoff_prob, int cutoff_top_n) {
+  return mi355asr_beam_state_new_lm(V, beam_size, cutoff_prob, cutoff_top_n, nullptr);
+}
+void* mi355asr_beam_state_new_lm(int V, int beam_size, double cutoff_prob, int cutoff_top_n, const BeamLm* sc) {
   auto* st = new BeamState();
+  st->s.set_scorer(sc);
   st->V = V; st->beam = beam_size; st->cutoff_prob = cutoff_prob; st->cutoff_top_n = cutoff_top_n; st->frame = 0;
   st->s.reset(beam_size, V - 1);       // BeamDecoder: blank_id = vocabulary.size() - 1 (:238-240)
   return st;
@@ -623,8 +686,9 @@ int mi355asr_beam_state_decode(void* h, const float* probs, int T, int max_len, 
                                float* scores) {
   auto* st = static_cast<BeamState*>(h);
   for (int t = 0; t < T; ++t) {
-    pruned_from_row(probs + (size_t)t * st->V, st->V, st->cutoff_prob, st->cutoff_top_n, st->cands, st->order);
-    st->s.step(st->frame++, st->cands);          // the stamp must be unique over the decoder's lifetime
+    const float* row = probs + (size_t)t * st->V;
+    pruned_from_row(row, st->V, st->cutoff_prob, st->cutoff_top_n, st->cands, st->order);
+    st->s.step(st->frame++, st->cands, row[st->V - 1]);          // the stamp must be unique over the decoder's lifetime
   }
   // BeamDecoder::decode sorts the beam before returning (:389-392); the order carries over to the next call
   return st->s.finish(max_len, ids, lens, scores);

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cstdint>
+#include <type_traits>
 
 #include "beam.h"
 #include "refmath.h"
@@ -162,6 +163,25 @@ struct Shared {
   int kept_j[BMAX];
   __align__(16) int hpos[2][HASH];   // [beam buffer]: open-addressed set of 1 + entry position, keyed by id mod HASH (0: free cell)
 };
+// What the search with a scorer keeps besides (ctc_beam_search_decoder.cpp:64-73, 84-86, 111-128 in character-based mode;
+// lm_table.h).  Only the scorer's instantiation has it: the scorer-less kernels keep the Shared above as it is.
+struct SharedLM : Shared {
+  int lmhist[2][kLmMaxOrder - 1][BMAX];   // [beam buffer][age, 0 = last token][entry]: LM words of the entry's last order - 1 tokens, "<s>"-padded
+  float lmterm[2][BMAX];                // [beam buffer][entry]: the entry's own LM term (float)(cond * alpha): a node's term depends on the node only
+  int cw[2][NMAX];                      // [frame parity][candidate]: LM word of the candidate's class
+  double logpb[2];                      // [frame parity]: log of the frame's blank probability (min_cutoff, :70-71)
+  float kept_lm[NT];                    // select_radix: LM term of every kept child, next to keys / kept_j
+};
+// the scorer as the kernel sees it
+struct LmRun {
+  LmView view;
+  double alpha, beta;
+  float min_cutoff;                      // this frame's (:70-71)
+  bool full_beam;
+};
+template <bool LM> struct LmRunOpt { };
+template <> struct LmRunOpt<true> : LmRun { };
+
 // Two lookups replace list scans on the per-frame path (a thread scanning 40 candidates and up to 128 ids cost 2 500 of
 // the 3 400 clocks of the entry phase):
 //   class table (dynamic LDS, V bytes per frame parity): tab[c] = 1 + position of class c among the frame's candidates,
@@ -223,9 +243,10 @@ __device__ __forceinline__ float key_score(u64 key) {             // inverse of 
 // by one thread each.  Ends with a barrier; returns the size of the next beam.
 constexpr unsigned kNegHi = 0xFF7FFFFFu;   // first key word of a score of -FLT_MAX: ~(~bits(-FLT_MAX))
 struct RadixProf { long long keys, select, install; };
-template <int JPT, int NW>                 // entries per wave, waves: nbm <= NW * JPT
-__device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx, const Cands& K, const u64* exist, int nbm,
-                                            int beam, int t, int2* arena, const Lookup& L, bool profiling, RadixProf& rp) {
+template <int JPT, int NW, bool LM, class SH>   // entries per wave, waves: nbm <= NW * JPT; with the scorer; Shared or SharedLM
+__device__ __forceinline__ int select_radix(SH& sh, const Beam& C, Beam& Nx, const Cands& K, const u64* exist, int nbm,
+                                            int beam, int t, int2* arena, const Lookup& L, bool profiling, RadixProf& rp,
+                                            const LmRunOpt<LM>& lm, int cur) {
   const int tid = threadIdx.x, k = tid & 63, w = tid >> 6;
   long long c0 = 0;
   if (profiling) c0 = clock64();
@@ -234,6 +255,9 @@ __device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx,
   const int c = cand ? K.c[k] : 0;
   const float clp = cand ? K.lp[k] : 0.f;
   u64 ekey = ~0ull, ck[JPT];
+  float cl[LM ? JPT : 1];                   // scorer: the LM term of each child key
+  int cwk = 0;
+  if constexpr (LM) cwk = cand ? sh.cw[t & 1][k] : 0;
   int counts = 0;                           // valid keys + (finite keys << 16)
   u64 kmin = ~0ull;
   if (tid < nbm) {
@@ -248,17 +272,38 @@ __device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx,
   const u64 ex_l = exist[jl];
   const int ch_l = C.ch[jl];
   const float b_l = C.b[jl], s_l = C.score[jl];
+  int h_l[kLmMaxOrder - 1];
+  if constexpr (LM) {
+#pragma unroll
+    for (int i = 0; i < kLmMaxOrder - 1; ++i) h_l[i] = sh.lmhist[cur][i][jl];
+  }
 #pragma unroll
   for (int g = 0; g < JPT; ++g) {
     const int j = w + NW * g;
     u64 key = ~0ull;
+    if constexpr (LM) cl[g] = 0.f;
     if (j < nbm) {                          // wave-uniform
       const u64 ex = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(ex_l >> 32), g) << 32) | (unsigned)__builtin_amdgcn_readlane((int)ex_l, g);
       const int chj = __builtin_amdgcn_readlane(ch_l, g);
       const float bj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b_l), g));
       const float sj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s_l), g));
-      if (cand && !((ex >> k) & 1ull)) {
-        const float lp = c == chj ? (bj > kNegInf ? clp + bj : kNegInf) : clp + sj;
+      int32_t r[kLmMaxOrder] = {0, 0, 0, 0, 0, 0};   // scorer: the n-gram backwards; the entry's words are wave-uniform reads
+      if constexpr (LM) {
+        r[0] = cwk;
+#pragma unroll
+        for (int i = 1; i < kLmMaxOrder; ++i) r[i] = __builtin_amdgcn_readlane(h_l[i - 1], g);
+      }
+      bool live = cand && !((ex >> k) & 1ull);
+      // the scorer's pruning as a filter per pair, before the lookup: a pruned pair costs nothing
+      if constexpr (LM) live = live && !(lm.full_beam && clp + sj < lm.min_cutoff);
+      if (live) {
+        float lp = c == chj ? (bj > kNegInf ? clp + bj : kNegInf) : clp + sj;
+        if constexpr (LM) {
+          const float sc = (float)((double)lm_cond(lm.view, r) * lm.alpha);
+          lp += sc;                                    // :126, float += float
+          lp = (float)((double)lp + lm.beta);          // :127, float += double
+          cl[g] = sc;
+        }
         key = make_key(lp, c, nbm + j * nc + k);
         counts += 1 + (((unsigned)(key >> 32) != kNegHi) << 16);
         kmin = key < kmin ? key : kmin;
@@ -333,7 +378,11 @@ __device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx,
     if (ekey != ~0ull && (ekey >> shift_keep) <= thr_s) { sh.keys[pos] = ekey; sh.kept_j[pos] = -1 - tid; ++pos; }
 #pragma unroll
     for (int i = 0; i < JPT; ++i)
-      if (ck[i] != ~0ull && (ck[i] >> shift_keep) <= thr_s) { sh.keys[pos] = ck[i]; sh.kept_j[pos] = w + NW * i; ++pos; }
+      if (ck[i] != ~0ull && (ck[i] >> shift_keep) <= thr_s) {
+        sh.keys[pos] = ck[i]; sh.kept_j[pos] = w + NW * i;
+        if constexpr (LM) sh.kept_lm[pos] = cl[i];
+        ++pos;
+      }
   }
   __syncthreads();
   {
@@ -363,6 +412,20 @@ __device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx,
     if (mine && half == 0) {
       if (j < 0) keep_entry(sh, C, Nx, L, -1 - j, rank);
       else keep_child(C, Nx, L, arena, 1 + t * beam + rank, j, (int)((key >> 16) & 0xffff) - 1, key_score(key), rank);
+      if constexpr (LM) {                   // the new entry's history and its own LM term
+        const int src = j < 0 ? -1 - j : j;
+        if (j < 0) {
+#pragma unroll
+          for (int i = 0; i < kLmMaxOrder - 1; ++i) sh.lmhist[cur ^ 1][i][rank] = sh.lmhist[cur][i][src];
+          sh.lmterm[cur ^ 1][rank] = sh.lmterm[cur][src];
+        } else {
+          const int kk = (int)(key & 0xffff) - nbm - j * nc;      // the candidate's position, from the key's slot word
+          sh.lmhist[cur ^ 1][0][rank] = sh.cw[t & 1][kk];
+#pragma unroll
+          for (int i = 1; i < kLmMaxOrder - 1; ++i) sh.lmhist[cur ^ 1][i][rank] = sh.lmhist[cur][i - 1][src];
+          sh.lmterm[cur ^ 1][rank] = sh.kept_lm[kidx];
+        }
+      }
     }
   }
   __syncthreads();
@@ -377,10 +440,15 @@ __device__ __forceinline__ int select_radix(Shared& sh, const Beam& C, Beam& Nx,
 // beam + 1 are almost never kept.  "Almost" is made exact: the frame is accepted only when the beam is full and its worst
 // kept score is strictly above the best score any skipped child could have (lp[ncap] + the best entry score); otherwise
 // (ties at the beam boundary, under-full beams) the frame is redone by select_radix over all candidates.
-template <bool SMALL>
-__global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDeviceArgs a) {
+// LM: with the scorer (l), always through select_radix (the small path's acceptance bound does not hold once children carry LM
+// terms); the scorer-less instantiations are the code they were before the scorer existed.
+template <bool SMALL, bool LM>
+__device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const BeamLmDeviceArgs* l) {
+  static_assert(!(SMALL && LM), "the scorer's search is the radix path");
   constexpr int NTT = SMALL ? NT : NTW, NWV = NTT / 64;      // threads / waves of this instantiation
-  __shared__ Shared sh;
+  __shared__ std::conditional_t<LM, SharedLM, Shared> sh;
+  LmRunOpt<LM> lm;
+  if constexpr (LM) { lm.view = l->view; lm.alpha = l->alpha; lm.beta = l->beta; lm.min_cutoff = kNegInf; lm.full_beam = false; }
   extern __shared__ __align__(16) unsigned char class_tab[];     // [frame parity][tab_stride(V)]
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
@@ -398,6 +466,11 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
     B0.id[0] = 1; B0.par[0] = 0; B0.ch[0] = -1; B0.arena[0] = 0; B0.kc[0] = -1;
     B0.score[0] = 0.f; B0.b[0] = 0.f; B0.nb[0] = kNegInf;
     arena[0] = make_int2(-1, -1);
+    if constexpr (LM) {                     // the root: "<s>" all the way back, no term of its own
+#pragma unroll
+      for (int i = 0; i < kLmMaxOrder - 1; ++i) sh.lmhist[0][i][0] = lm.view.bos;
+      sh.lmterm[0][0] = 0.f;
+    }
   }
   long long p_entries = 0, p_keys = 0, p_keep = 0, p_radix = 0, p_redone = 0;
   RadixProf rprof = {0, 0, 0};
@@ -410,9 +483,15 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
   const int pl = tid - (NTT - 64);           // the last wave ("wave 3" in the comments: it is with four waves)
   float p_nx = 0.f;
   int c_nx = 0;
+  int w_nx = 0;                             // scorer: the LM word of c_nx, and (lane 0) the frame's blank probability
+  float pb_nx = 0.f;
   if (pl >= 0 && pl < N && frames > 0) {
     p_nx = a.top_p[(size_t)b * T * N + pl];
     c_nx = a.top_idx[(size_t)b * T * N + pl];
+    if constexpr (LM) {
+      w_nx = l->top_w[(size_t)b * T * N + pl];
+      if (pl == 0) pb_nx = l->blank_p[(size_t)b * T];
+    }
   }
   auto prepare = [&](int tt) {              // wave 3 only: candidates of frame tt into cands[tt & 1]
     Cands& K = sh.cands[tt & 1];
@@ -447,6 +526,10 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
       tab[c_nx] = (unsigned char)(pl + 1);
       K.c[pl] = c_nx;
       K.lp[pl] = (float)refmath::ref_log((double)p_nx + (double)FLT_MIN, sh.math.log);
+      if constexpr (LM) sh.cw[tt & 1][pl] = w_nx;
+    }
+    if constexpr (LM) {                     // std::log(prob[blank_id]) (:71): log(0) = -inf prunes nothing
+      if (pl == 0) sh.logpb[tt & 1] = pb_nx > 0.f ? refmath::ref_log((double)pb_nx, sh.math.log) : -(double)INFINITY;
     }
     const u64 bm = __ballot(mine && c_nx == V - 1);
     if (pl == 0) {
@@ -457,6 +540,10 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
       const size_t fn = ((size_t)b * T + tt + 1) * N + pl;
       p_nx = a.top_p[fn];
       c_nx = a.top_idx[fn];
+      if constexpr (LM) {
+        w_nx = l->top_w[fn];
+        if (pl == 0) pb_nx = l->blank_p[(size_t)b * T + tt + 1];
+      }
     }
     if (profiling3) p_prep += clock64() - q0;
   };
@@ -490,19 +577,39 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
       if ((tid & 63) == 0) sh.max_score = best;
     }
     // ---- 2. existing entries: blank update, repetition, extension by the parent if that is in the beam
+    if constexpr (LM) {
+      // the scorer's pruning (:64-73): the beam is in rank order, its last entry is the worst; every thread forms the same value
+      lm.full_beam = nbm == beam;
+      lm.min_cutoff = (float)((double)C.score[nbm - 1] + sh.logpb[t & 1] - fmax(0.0, lm.beta));
+    }
     if (tid < nbm) {
       const int i = tid;
       const int kc = C.kc[i];
       const u64 pid = C.par[i];
       const float nb_i = C.nb[i];
-      const float bc = kb >= 0 ? K.lp[kb] + C.score[i] : kNegInf;  // log_sum_exp(-inf, x) = x
+      float bc = kb >= 0 ? K.lp[kb] + C.score[i] : kNegInf;  // log_sum_exp(-inf, x) = x
+      if constexpr (LM) {
+        if (kb >= 0 && lm.full_beam && K.lp[kb] + C.score[i] < lm.min_cutoff) bc = kNegInf;      // (:84-86) as a filter per pair
+      }
       float nbc = kNegInf;
       if (kc >= 0) {
         nbc = K.lp[kc] + nb_i;
+        if constexpr (LM) {
+          if (lm.full_beam && K.lp[kc] + C.score[i] < lm.min_cutoff) nbc = kNegInf;
+        }
         const int j = hash_find(sh.hpos[cur], C, nbm, pid);
         if (profiling) p_scan += clock64() - t0;
         if (j >= 0) {
-          nbc = lse(sh.math, nbc, child_lp(C, K, j, kc));
+          if constexpr (LM) {
+            if (!(lm.full_beam && K.lp[kc] + C.score[j] < lm.min_cutoff)) {
+              float e = child_lp(C, K, j, kc);
+              e += sh.lmterm[cur][i];                      // the cached term of this node (:126)
+              e = (float)((double)e + lm.beta);            // :127
+              nbc = lse(sh.math, nbc, e);
+            }
+          } else {
+            nbc = lse(sh.math, nbc, child_lp(C, K, j, kc));
+          }
           atomicOr(&exist[j], 1ull << kc);
         }
       }
@@ -579,7 +686,7 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
         if (tid == 0) sh.kmin[t & 1] = ~0ull;
         __syncthreads();
       }
-      newn = select_radix<(SMALL ? SMALL_BEAM : BMAX) / NWV, NWV>(sh, C, Nx, K, exist, nbm, beam, t, arena, L, profiling, rprof);
+      newn = select_radix<(SMALL ? SMALL_BEAM : BMAX) / NWV, NWV, LM>(sh, C, Nx, K, exist, nbm, beam, t, arena, L, profiling, rprof, lm, cur);
       if (profiling) p_radix += clock64() - t3;
     }
     cur ^= 1;
@@ -622,6 +729,10 @@ __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDevic
   }
 }
 
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDeviceArgs a) { beam_search_body<SMALL, false>(a, nullptr); }
+__global__ __launch_bounds__(NTW) void beam_search_lm_kernel(BeamDeviceArgs a, BeamLmDeviceArgs l) { beam_search_body<false, true>(a, &l); }
+
 // the device's evaluation of refmath.h, for the parity test against the host's libm (tests/test_gpu_parity.py)
 __global__ __launch_bounds__(256) void refmath_eval_kernel(int kind, const float* __restrict__ in, void* __restrict__ out, int n) {
   __shared__ MathTabs m;
@@ -652,6 +763,11 @@ constexpr int kLdsBytes = 160 * 1024;
 constexpr int kMaxClasses = std::min(65534, ((kLdsBytes - (int)sizeof(Shared) - 512) / 2) & ~15);
 static_assert(kMaxClasses >= 32768, "the static LDS of the search left too little for the class tables");
 bool mi355asr_beam_device_applicable(int V, int N, int beam) { return beam >= 1 && beam <= BMAX && N >= 1 && N <= NMAX && V <= kMaxClasses; }
+constexpr int kMaxClassesLm = std::min(65534, ((kLdsBytes - (int)sizeof(SharedLM) - 512) / 2) & ~15);
+static_assert(kMaxClassesLm >= 32768, "the static LDS of the scorer's search left too little for the class tables");
+bool mi355asr_beam_device_lm_applicable(int V, int N, int beam, int order) {
+  return beam >= 1 && beam <= BMAX && N >= 1 && N <= NMAX && V <= kMaxClassesLm && order >= 1 && order <= kLmMaxOrder;
+}
 
 size_t mi355asr_beam_device_carve(char* ws, int B, int T, int beam, int max_len, BeamDeviceArgs* a, int32_t** d_len, long long** prof) {
   size_t off = 0;
@@ -689,6 +805,21 @@ int mi355asr_launch_beam_device(const BeamDeviceArgs* a, hipStream_t s) {
   }
   if (small) hipLaunchKernelGGL(beam_search_kernel<true>, dim3(a->B), dim3(NT), dyn, s, *a);
   else hipLaunchKernelGGL(beam_search_kernel<false>, dim3(a->B), dim3(NTW), dyn, s, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int mi355asr_launch_beam_device_lm(const BeamDeviceArgs* a, const BeamLmDeviceArgs* l, hipStream_t s) {
+  const int dyn = 2 * tab_stride(a->V);
+  if (!mi355asr_beam_device_lm_applicable(a->V, a->N, a->beam, l->view.order)) return -2;
+  static bool allowed_on[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
+  if (!allowed_on[dev]) {
+    if (hipFuncSetAttribute((const void*)beam_search_lm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tab_stride(kMaxClassesLm)) != hipSuccess)
+      return -2;
+    allowed_on[dev] = true;
+  }
+  hipLaunchKernelGGL(beam_search_lm_kernel, dim3(a->B), dim3(NTW), dyn, s, *a, *l);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

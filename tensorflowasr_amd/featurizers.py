@@ -119,6 +119,14 @@ class TextFeaturizer:
             self.num_classes += 1
         self.pad = 0
         self.stop = -1
+        # lm_config {lm_path, alpha, beta} (utils/text_featurizers.py:20-24): the prefix beam search's external scorer
+        lm = self.decoder_config.get("lm_config")
+        if lm and lm.get("lm_path"):
+            if self.decoder_config["blank_at_zero"]:
+                raise NotImplementedError("lm_config: the prefix beam search takes the blank as the LAST class (blank_at_zero: False)")
+            from .ngram import NGramScorer
+            vocab = [self.index_to_token[i] for i in range(self.num_classes) if i != self.blank]
+            self.scorer = NGramScorer(lm.get("alpha", 0.0), lm.get("beta", 0.0), os.path.expanduser(lm["lm_path"]), vocab)
 
     def startid(self):
         return self.token_to_index["<S>"]

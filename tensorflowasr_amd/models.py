@@ -805,9 +805,18 @@ class ConformerCTC(_ModelBase):
         return ConformerEncoder.conformer_block(self, index, x, stack=stack)
 
 
+def _check_scorer(ext_scorer):
+    from .ngram import NGramScorer
+    if not isinstance(ext_scorer, NGramScorer):
+        raise NotImplementedError("ext_scorer must be a tensorflowasr_amd.ngram.NGramScorer (character-based n-gram model); the "
+                                  "reference's KenLM / OpenFST Scorer objects are not part of this build")
+
+
 def ctc_prefix_beam_decode(x, input_length=None, beam_width=10, cutoff_prob=0.99, cutoff_top_n=40, is_logits=False,
-                           num_threads=None, max_len=None):
-    """Scorer-less CTC prefix beam search of externals/ctc_decoders (ctc_beam_search_decoder_batch).
+                           num_threads=None, max_len=None, ext_scorer=None):
+    """CTC prefix beam search of externals/ctc_decoders (ctc_beam_search_decoder_batch), scorer-less or -- with
+    `ext_scorer`, an `ngram.NGramScorer` over the V - 1 non-blank classes -- with its character-based n-gram scoring
+    (`mi355asr_ctc_prefix_beam_lm*`; alpha and beta are read from the scorer at every call).
 
     x: [B, T, V] probabilities (or logits with is_logits=True), blank = class V-1.  A CUDA tensor goes through the
     GPU top-n selection kernel + host search (`mi355asr_ctc_prefix_beam`, needs cutoff_prob < 1); a NumPy array / CPU
@@ -835,22 +844,30 @@ def ctc_prefix_beam_decode(x, input_length=None, beam_width=10, cutoff_prob=0.99
         il = np.ascontiguousarray(input_length.cpu().numpy() if torch.is_tensor(input_length) else input_length, np.int32)
     ilp = il.ctypes.data_as(ctypes.c_void_p) if il is not None else ctypes.c_void_p()
     outs = [a.ctypes.data_as(ctypes.c_void_p) for a in (ids, lens, scores, n_hyp)]
+    lm = ()
+    if ext_scorer is not None:
+        _check_scorer(ext_scorer)
+        if len(ext_scorer.vocabulary) != V - 1:
+            raise ValueError("ext_scorer was built for %d classes, x has %d + blank" % (len(ext_scorer.vocabulary), V - 1))
+        lm = (ext_scorer.handle(), float(ext_scorer.alpha), float(ext_scorer.beta))
     if on_gpu:
         xd = x.to(torch.float32).contiguous()
         nbytes = ctypes.c_size_t()
-        _lib.check(lib.mi355asr_ctc_prefix_beam_workspace_bytes(B, T, int(cutoff_top_n), int(beam_width), max_len, ctypes.byref(nbytes)))
+        ws_fn = lib.mi355asr_ctc_prefix_beam_lm_workspace_bytes if lm else lib.mi355asr_ctc_prefix_beam_workspace_bytes
+        _lib.check(ws_fn(B, T, int(cutoff_top_n), int(beam_width), max_len, ctypes.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=xd.device)
         with torch.cuda.device(xd.device):
             st = ctypes.c_void_p(torch.cuda.current_stream(xd.device).cuda_stream)
-            _lib.check(lib.mi355asr_ctc_prefix_beam(_p(xd), int(bool(is_logits)), ilp, B, T, V, beam_width,
-                                                   float(cutoff_prob), cutoff_top_n, nthreads, max_len, *outs,
-                                                   _p(ws), ws.numel(), st))
+            fn = lib.mi355asr_ctc_prefix_beam_lm if lm else lib.mi355asr_ctc_prefix_beam
+            _lib.check(fn(_p(xd), int(bool(is_logits)), ilp, B, T, V, beam_width, float(cutoff_prob), cutoff_top_n, nthreads,
+                          max_len, *lm, *outs, _p(ws), ws.numel(), st))
     else:
         if is_logits:
             raise ValueError("host path takes probabilities (the reference's input); pass is_logits only with CUDA tensors")
         xh = np.ascontiguousarray(x.numpy() if torch.is_tensor(x) else x, np.float32)
-        _lib.check(lib.mi355asr_ctc_prefix_beam_host(xh.ctypes.data_as(ctypes.c_void_p), ilp, B, T, V, beam_width,
-                                                    float(cutoff_prob), cutoff_top_n, nthreads, max_len, *outs))
+        fn = lib.mi355asr_ctc_prefix_beam_lm_host if lm else lib.mi355asr_ctc_prefix_beam_host
+        _lib.check(fn(xh.ctypes.data_as(ctypes.c_void_p), ilp, B, T, V, beam_width, float(cutoff_prob), cutoff_top_n, nthreads,
+                      max_len, *lm, *outs))
     return ids, lens, scores, n_hyp
 
 
@@ -948,9 +965,10 @@ class ChunkBeamPipeline:
     `predict`, while the caller's stream already recognises the next batch.  `push(wav)` returns the beams of the PREVIOUS
     batch (None for the first), `flush()` the last one's: (ids, lens, scores, n_hyp) as `ctc_prefix_beam_decode`."""
 
-    def __init__(self, model, beam_width=10, cutoff_prob=0.99, cutoff_top_n=40):
+    def __init__(self, model, beam_width=10, cutoff_prob=0.99, cutoff_top_n=40, ext_scorer=None):
         from concurrent.futures import ThreadPoolExecutor
-        self.model, self.kw = model, dict(beam_width=beam_width, cutoff_prob=cutoff_prob, cutoff_top_n=cutoff_top_n)
+        self.model, self.kw = model, dict(beam_width=beam_width, cutoff_prob=cutoff_prob, cutoff_top_n=cutoff_top_n,
+                                          ext_scorer=ext_scorer)
         self.device = model._h.device
         self.side = torch.cuda.Stream(device=self.device)
         self.pool = ThreadPoolExecutor(max_workers=1)
@@ -984,19 +1002,28 @@ class ChunkBeamPipeline:
 
 class BeamDecoder:
     """Stateful prefix beam search: externals/ctc_decoders `BeamDecoder(vocabulary, beam_size, cutoff_prob,
-    cutoff_top_n)` with `.decode(probs_seq)` / `.reset()` (ctc_beam_search_decoder.cpp:217-405, no external scorer).
-    `vocabulary` includes the blank as its LAST entry, as the reference class expects.  decode() returns the current
+    cutoff_top_n, ext_scorer)` with `.decode(probs_seq)` / `.reset()` (ctc_beam_search_decoder.cpp:217-405).
+    `vocabulary` includes the blank as its LAST entry, as the reference class expects; `ext_scorer` is an
+    `ngram.NGramScorer` over the classes in front of it, whose alpha and beta are read when the decoder is made.  decode() returns the current
     beam as [(log_prob, text)], best first, after consuming the given frames; `decode_ids` returns token ids."""
 
     def __init__(self, vocabulary, beam_size, cutoff_prob=1.0, cutoff_top_n=40, ext_scorer=None):
-        if ext_scorer is not None:
-            raise NotImplementedError("external scorer (KenLM / OpenFST) is not part of this build")
         self.vocabulary = list(vocabulary)
         self.beam_size = int(beam_size)
         self.lib = _lib.lib()
         self.ptr = ctypes.c_void_p()
-        _lib.check(self.lib.mi355asr_beam_create(len(self.vocabulary), self.beam_size, float(cutoff_prob),
-                                                 int(cutoff_top_n), ctypes.byref(self.ptr)))
+        self.ext_scorer = ext_scorer                       # keeps the model alive as long as the decoder reads it
+        if ext_scorer is not None:
+            _check_scorer(ext_scorer)
+            if len(ext_scorer.vocabulary) != len(self.vocabulary) - 1:
+                raise ValueError("ext_scorer was built for %d classes, the vocabulary has %d + blank"
+                                 % (len(ext_scorer.vocabulary), len(self.vocabulary) - 1))
+            _lib.check(self.lib.mi355asr_beam_create_lm(len(self.vocabulary), self.beam_size, float(cutoff_prob), int(cutoff_top_n),
+                                                        ext_scorer.handle(), float(ext_scorer.alpha), float(ext_scorer.beta),
+                                                        ctypes.byref(self.ptr)))
+        else:
+            _lib.check(self.lib.mi355asr_beam_create(len(self.vocabulary), self.beam_size, float(cutoff_prob),
+                                                     int(cutoff_top_n), ctypes.byref(self.ptr)))
 
     def __del__(self):
         try:
