@@ -208,6 +208,18 @@ int mi355asr_ctc_prefix_beam(const float* x_dev, int32_t is_logits, const int32_
  * evaluates glibc's own algorithms (csrc/refmath.h).  kind 0: out f32[i] = expf(in[i]), in [-17.5, 0];
  * 1: out f32[i] = logf(in[i]), in [1, 2]; 2: out f64[i] = log((double)in[i] + FLT_MIN), in [0, 1];
  * 3: out f32[i] = log_sum_exp(in[i], in[n + i]) (in holds 2 n values).  Device pointers. */
+/* Which search the last mi355asr_ctc_prefix_beam / mi355asr_ctc_prefix_beam_lm call of the CALLING THREAD ran: 0 none yet;
+ * 1 the host search on the device's top-n lists (outside the device search's limits, a workspace below
+ * mi355asr_ctc_prefix_beam*_workspace_bytes, or MI355ASR_BEAM_DEVICE=0); 2 the device search's one-key-per-thread kernel;
+ * 3 its radix kernel; 4 the device search with a scorer.  All of them return the same arrays, so this is the only way to
+ * tell them apart; it is set on the host from the conditions that choose the launch.
+ * mi355asr_beam_device_limits: the limits those conditions use -- the device search serves V <= max_classes, beam_size <=
+ * max_beam, min(cutoff_top_n, V) <= max_top_n; without a scorer the one-key-per-thread kernel runs when beam_size <=
+ * small_beam and beam_size * (min(N, beam_size + 2) + 1) <= 256 with N = min(cutoff_top_n, V) (small_beam is 0 with one). */
+int32_t mi355asr_beam_last_path(void);
+int mi355asr_beam_device_limits(int32_t with_scorer, int32_t* max_classes, int32_t* max_beam, int32_t* max_top_n,
+                                int32_t* small_beam);
+
 int mi355asr_beam_math_eval(int32_t kind, const float* in_dev, void* out_dev, int32_t n, void* stream);
 
 /* Stateful prefix beam search for streaming recognition.

@@ -16,6 +16,8 @@ int prefix_beam_impl(const float* x, int32_t is_logits, const int32_t* in_len, i
                      int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t num_threads,
                      int32_t max_len, const BeamLm* sc, int32_t* ids, int32_t* lens, float* scores, int32_t* n_hyp, void* ws,
                      size_t ws_bytes, void* stream);
+// what the calling thread's last mi355asr_ctc_prefix_beam / _lm call ran (mi355asr_beam_last_path): written where the search is chosen
+thread_local int32_t last_path = 0;
 }  // namespace
 
 extern "C" {
@@ -50,6 +52,16 @@ int mi355asr_ctc_prefix_beam_lm_workspace_bytes(int32_t B, int32_t T, int32_t cu
   if (!bytes || B <= 0 || T <= 0 || cutoff_top_n <= 0 || beam_size <= 0 || max_len <= 0) return fail(MI355ASR_EINVAL, "bad argument");
   const size_t need = (size_t)B * T * (std::min(cutoff_top_n, 128) * 12 + 4);     // classes, probabilities, LM words; the blank's probability
   *bytes = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
+  return 0;
+}
+
+int32_t mi355asr_beam_last_path(void) { return last_path; }
+
+int mi355asr_beam_device_limits(int32_t with_scorer, int32_t* max_classes, int32_t* max_beam, int32_t* max_top_n, int32_t* small_beam) {
+  if (!max_classes || !max_beam || !max_top_n || !small_beam) return fail(MI355ASR_EINVAL, "null pointer");
+  int v[4];
+  mi355asr_beam_device_limit_values(with_scorer != 0, &v[0], &v[1], &v[2], &v[3]);
+  *max_classes = v[0]; *max_beam = v[1]; *max_top_n = v[2]; *small_beam = v[3];
   return 0;
 }
 
@@ -97,13 +109,14 @@ int prefix_beam_impl(const float* x, int32_t is_logits, const int32_t* in_len, i
   int32_t* d_w = lm ? (int32_t*)(d_p + frames * N) : nullptr;
   float* d_blank = lm ? (float*)(d_w + frames * N) : nullptr;
   if (mi355asr_launch_topn(x, (int)frames, V, N, is_logits, d_idx, d_p, d_blank, s) != 0)
-    return fail(MI355ASR_EHIP, "top-n kernel launch failed (V=%d needs %zu bytes of LDS)", V, (size_t)V * 4);
+    return fail(MI355ASR_EHIP, "top-n kernel launch failed (V=%d, cutoff_top_n=%d)", V, N);
   // MI355ASR_BEAM_DEVICE=0: the prefix search on host threads (beam.hip) instead of the device kernel (beam_device.hip)
   static const bool dev_env = mi355_env("MI355ASR_BEAM_DEVICE", 1) != 0;
   const size_t need_dev = ((need + 255) & ~(size_t)255) + mi355asr_beam_device_ws_bytes(B, T, beam_size, max_len);
   const bool fits = lm ? mi355asr_beam_device_lm_applicable(V, N, beam_size, mi355asr_lm_host_view(lm)->order)
                        : mi355asr_beam_device_applicable(V, N, beam_size);
   if (dev_env && fits && ws_bytes >= need_dev) {
+    last_path = lm ? 4 : mi355asr_beam_device_small(N, beam_size) ? 2 : 3;
     char* w = (char*)ws + ((need + 255) & ~(size_t)255);
     BeamDeviceArgs a{};
     a.top_idx = d_idx; a.top_p = d_p; a.B = B; a.T = T; a.V = V; a.N = N; a.beam = beam_size;
@@ -175,6 +188,7 @@ int prefix_beam_impl(const float* x, int32_t is_logits, const int32_t* in_len, i
     }
     return 0;
   }
+  last_path = 1;
   std::vector<int32_t> h_idx(frames * N);
   std::vector<float> h_p(frames * N);
   HIP_TRY(hipMemcpyAsync(h_idx.data(), d_idx, h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));

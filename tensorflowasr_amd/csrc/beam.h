@@ -38,6 +38,8 @@ struct BeamDeviceArgs {
   long long* prof;          // null, or 9 counters of utterance 0 (MI355ASR_BEAM_PROF)
 };
 bool mi355asr_beam_device_applicable(int V, int N, int beam);
+bool mi355asr_beam_device_small(int N, int beam);    // which scorer-less kernel a call gets: one key per thread (true) or the radix path
+void mi355asr_beam_device_limit_values(int with_scorer, int* max_classes, int* max_beam, int* max_top_n, int* small_beam);
 size_t mi355asr_beam_device_ws_bytes(int B, int T, int beam, int max_len);
 // the ONE place that lays the device search's buffers out in its workspace (16-byte aligned segments; ws null: size only):
 // fills a->arena / ids / lens / scores / n_hyp, *d_len (staging of in_len) and *prof (9 x int64 counters); returns the bytes used

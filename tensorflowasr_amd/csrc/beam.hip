@@ -326,14 +326,48 @@ __device__ __forceinline__ void topn_rounds(float* sh, int V, int N, int lane, b
   }
 }
 
+// The same rounds over a row that stays where it is (global memory, read-only): instead of knocking the selected class out,
+// round n takes the best class that comes AFTER the previous round's in (value descending, class ascending) order.
+__device__ __forceinline__ void topn_rounds_ro(const float* row, int V, int N, int lane, bool is_logits, float mx, float denom,
+                                               int32_t* out_idx, float* out_p) {
+  float last_v = INFINITY;
+  int last_i = -1;
+  for (int n = 0; n < N; ++n) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+      const float v = row[i];
+      if ((v < last_v || (v == last_v && i > last_i)) && v > best) { best = v; bi = i; }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float ov = __shfl_xor(best, off);
+      const int oi = __shfl_xor(bi, off);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) {
+      out_idx[n] = bi;
+      out_p[n] = is_logits ? __expf(best - mx) / denom : best;
+    }
+    last_v = best;
+    last_i = bi;
+  }
+}
+
+// STAGED: the row is copied to LDS once and every later pass reads it there.  !STAGED (rows too long for the CU's LDS, V above
+// ~40 000): the same passes read the row in global memory again (L2 hits) -- the same classes per lane, the same order of the
+// soft-max sum, the same selection.
+template <bool STAGED>
 __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, int V, int N, int is_logits,
                                                   int32_t* __restrict__ out_idx, float* __restrict__ out_p, float* __restrict__ out_blank) {
-  extern __shared__ __align__(16) float sh[];
+  extern __shared__ __align__(16) float sh_row[];
   __shared__ float cv[GT_CAP + EQ_CAP];
   __shared__ int ci[GT_CAP + EQ_CAP];
   const int lane = threadIdx.x;
   const size_t frame = blockIdx.x;
   const float* row = x + frame * V;
+  float* sh = STAGED ? sh_row : nullptr;
+  const float* src = STAGED ? sh_row : row;      // where the passes after the first read the row
   out_idx += frame * N;
   out_p += frame * N;
   // stage the row; mx = the maximum of what this lane staged (any partition of the classes over the lanes serves the
@@ -353,7 +387,7 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int i = i0 + 64 * u + lane;
-        if (i < V4) sh4[i] = v[u];
+        if (STAGED && i < V4) sh4[i] = v[u];
         mx = fmaxf(fmaxf(mx, fmaxf(v[u].x, v[u].y)), fmaxf(v[u].z, v[u].w));
       }
     }
@@ -368,7 +402,7 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int i = i0 + 64 * u + lane;
-        if (i < V) sh[i] = v[u];
+        if (STAGED && i < V) sh[i] = v[u];
         mx = fmaxf(mx, v[u]);
       }
     }
@@ -380,14 +414,15 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
   if (is_logits) {
     float s = 0.f;
 #pragma unroll 8
-    for (int i = lane; i < V; i += 64) s += __expf(sh[i] - mx);
+    for (int i = lane; i < V; i += 64) s += __expf(src[i] - mx);
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
     denom = s;
   }
-  if (out_blank && lane == 0) out_blank[frame] = is_logits ? __expf(sh[V - 1] - mx) / denom : sh[V - 1];
+  if (out_blank && lane == 0) out_blank[frame] = is_logits ? __expf(src[V - 1] - mx) / denom : src[V - 1];
   if (N > 64) {
-    topn_rounds(sh, V, N, lane, is_logits, mx, denom, out_idx, out_p);
+    if constexpr (STAGED) topn_rounds(sh, V, N, lane, is_logits, mx, denom, out_idx, out_p);
+    else topn_rounds_ro(row, V, N, lane, is_logits, mx, denom, out_idx, out_p);
     return;
   }
   // T0: the lane maximum of rank N - 1 (ranks made distinct by the lane number)
@@ -405,7 +440,7 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
 #pragma unroll 4
   for (int i0 = 0; i0 < V; i0 += 64) {
     const int i = i0 + lane;
-    const float v = i < V ? sh[i] : -INFINITY;
+    const float v = i < V ? src[i] : -INFINITY;
     const bool gt = i < V && v > T0, eq = i < V && v == T0;
     const unsigned long long bg = __ballot(gt), be = __ballot(eq);
     if ((bg | be) == 0) continue;
@@ -416,7 +451,8 @@ __global__ __launch_bounds__(64) void topn_kernel(const float* __restrict__ x, i
     E = min(E + __popcll(be), EQ_CAP);
   }
   if (G > GT_CAP) {
-    topn_rounds(sh, V, N, lane, is_logits, mx, denom, out_idx, out_p);
+    if constexpr (STAGED) topn_rounds(sh, V, N, lane, is_logits, mx, denom, out_idx, out_p);
+    else topn_rounds_ro(row, V, N, lane, is_logits, mx, denom, out_idx, out_p);
     return;
   }
   // candidates: [0, G) and [GT_CAP, GT_CAP + Eu); position of each in (value descending, class ascending) order
@@ -647,12 +683,17 @@ int mi355asr_launch_topn(const float* x_dev, int frames, int V, int N, int is_lo
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
   const size_t lds = (size_t)V * sizeof(float);
-  if (lds > 160 * 1024) return -1;
+  // a row that does not fit the CU's 160 KB next to the kernel's own candidate lists stays in global memory (V above 40 320: the
+  // device search's class tables reach further than that, beam_device.hip kMaxClasses)
+  if (lds + (GT_CAP + EQ_CAP) * (sizeof(float) + sizeof(int)) > 160 * 1024) {
+    hipLaunchKernelGGL(topn_kernel<false>, dim3(frames), dim3(64), 0, s, x_dev, V, N, is_logits, idx_dev, p_dev, blank_p_dev);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
   if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute((const void*)topn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)topn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return -2;
   }
-  hipLaunchKernelGGL(topn_kernel, dim3(frames), dim3(64), lds, s, x_dev, V, N, is_logits, idx_dev, p_dev, blank_p_dev);
+  hipLaunchKernelGGL(topn_kernel<true>, dim3(frames), dim3(64), lds, s, x_dev, V, N, is_logits, idx_dev, p_dev, blank_p_dev);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -769,6 +769,16 @@ bool mi355asr_beam_device_lm_applicable(int V, int N, int beam, int order) {
   return beam >= 1 && beam <= BMAX && N >= 1 && N <= NMAX && V <= kMaxClassesLm && order >= 1 && order <= kLmMaxOrder;
 }
 
+// the ONE dispatch rule of the scorer-less search: the launch below and mi355asr_beam_last_path both read it
+bool mi355asr_beam_device_small(int N, int beam) { return beam <= SMALL_BEAM && beam * (std::min(N, beam + 2) + 1) <= NT; }
+// the constants the two applicability functions above compare against (mi355asr_beam_device_limits)
+void mi355asr_beam_device_limit_values(int with_scorer, int* max_classes, int* max_beam, int* max_top_n, int* small_beam) {
+  *max_classes = with_scorer ? kMaxClassesLm : kMaxClasses;
+  *max_beam = BMAX;
+  *max_top_n = NMAX;
+  *small_beam = with_scorer ? 0 : SMALL_BEAM;      // the scorer's search is the radix path at every width
+}
+
 size_t mi355asr_beam_device_carve(char* ws, int B, int T, int beam, int max_len, BeamDeviceArgs* a, int32_t** d_len, long long** prof) {
   size_t off = 0;
   auto seg = [&](size_t bytes) { char* p = ws ? ws + off : nullptr; off += (bytes + 15) & ~(size_t)15; return p; };
@@ -789,7 +799,7 @@ size_t mi355asr_beam_device_ws_bytes(int B, int T, int beam, int max_len) {
 }
 
 int mi355asr_launch_beam_device(const BeamDeviceArgs* a, hipStream_t s) {
-  const bool small = a->beam <= SMALL_BEAM && a->beam * (std::min(a->N, a->beam + 2) + 1) <= NT;
+  const bool small = mi355asr_beam_device_small(a->N, a->beam);
   const int dyn = 2 * tab_stride(a->V);     // the class tables
   if (a->V > kMaxClasses) return -2;       // mi355asr_beam_device_applicable
   // per DEVICE: the attribute belongs to the kernel's code object on the device that is current (a process that drives

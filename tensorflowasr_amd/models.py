@@ -871,6 +871,23 @@ def ctc_prefix_beam_decode(x, input_length=None, beam_width=10, cutoff_prob=0.99
     return ids, lens, scores, n_hyp
 
 
+BEAM_PATHS = {0: "none", 1: "host search on the device's top-n lists", 2: "device, one key per thread", 3: "device, radix",
+              4: "device, with a scorer"}
+
+
+def beam_last_path():
+    """`mi355asr_beam_last_path`: which search the last `ctc_prefix_beam_decode` of this thread on a CUDA tensor ran (a key of
+    BEAM_PATHS).  Every path returns the same arrays; this is how a caller, or a test, tells the device search from its fallback."""
+    return int(_lib.lib().mi355asr_beam_last_path())
+
+
+def beam_device_limits(with_scorer=False):
+    """`mi355asr_beam_device_limits` -> dict(max_classes, max_beam, max_top_n, small_beam): what the device search serves"""
+    v = [ctypes.c_int32() for _ in range(4)]
+    _lib.check(_lib.lib().mi355asr_beam_device_limits(int(bool(with_scorer)), *[ctypes.byref(x) for x in v]))
+    return dict(zip(("max_classes", "max_beam", "max_top_n", "small_beam"), (int(x.value) for x in v)))
+
+
 def _ctc_lattice_inputs(x, labels, input_length, label_length, blank, device):
     """the common argument handling of ctc_loss / ctc_forced_align: x f32 [B,T,V] and labels i32 [B,U] on the device, lengths
     i32 [B] there (input_length may stay None = T).  Labels that arrive on the host are checked here (inside [0, V), not the

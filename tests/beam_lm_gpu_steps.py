@@ -14,11 +14,18 @@ for p in (ROOT, HERE):
         sys.path.insert(0, p)
 
 from tensorflowasr_amd import ngram                                    # noqa: E402
-from tensorflowasr_amd.models import ctc_prefix_beam_decode           # noqa: E402
+from tensorflowasr_amd.models import beam_last_path, ctc_prefix_beam_decode   # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden")
 ARPA = {3: os.path.join(GOLDEN, "lm_small.arpa"), 4: os.path.join(GOLDEN, "lm_small4.arpa")}
 NAMES = ("ids", "lens", "scores", "n_hyp")
+PATH_HOST, PATH_SMALL, PATH_RADIX, PATH_SCORER = 1, 2, 3, 4            # mi355asr_beam_last_path
+
+
+def ran(path, what):
+    """the search the last device-side call ran: every path returns the same arrays, so equality alone cannot tell"""
+    got = beam_last_path()
+    assert got == path, "%s: ran path %d, expected %d" % (what, got, path)
 HANZI_CLASSES = 9160                                                   # the ChunkConformer's text head: 9 159 characters + blank
 
 
@@ -88,6 +95,7 @@ def step_fixtures():
         p = K["probs_%d" % i][None]
         host = ctc_prefix_beam_decode(p, None, m["beam"], m["cutoff_prob"], m["cutoff_top_n"], num_threads=1, ext_scorer=s)
         dev = ctc_prefix_beam_decode(torch.from_numpy(p).cuda(), None, m["beam"], m["cutoff_prob"], m["cutoff_top_n"], ext_scorer=s)
+        ran(PATH_SCORER, "fixture case %d" % i)
         same(dev, host, "fixture case %d %s" % (i, m))
         assert np.array_equal(dev[2][0, :m["n"]].astype(np.float64), K["scores_%d" % i]), i      # and so the reference's scores
         done += 1
@@ -103,11 +111,13 @@ def step_config5():
         for alpha, beta in ((0.8, 0.4), (0.0, 0.0)):
             s = hanzi_scorer(alpha, beta)
             dev = ctc_prefix_beam_decode(pd, lens, beam, 0.99, 40, ext_scorer=s)
+            ran(PATH_SCORER, "config 5 beam %d alpha %g" % (beam, alpha))
             host = ctc_prefix_beam_decode(ph, lens, beam, 0.99, 40, ext_scorer=s, num_threads=16)
             same(dev, host, "config 5 beam %d alpha %g" % (beam, alpha))
             print("config 5 batch, beam %d, alpha %g beta %g: device == host on %d hypotheses; best lengths %s" %
                   (beam, alpha, beta, int(host[3].sum()), host[1][:4, 0].tolist()))
         dev0 = ctc_prefix_beam_decode(pd, lens, beam, 0.99, 40)
+        ran(PATH_SMALL if beam == 10 else PATH_RADIX, "config 5 beam %d scorer-less" % beam)
         host0 = ctc_prefix_beam_decode(ph, lens, beam, 0.99, 40, num_threads=16)
         same(dev0, host0, "config 5 beam %d scorer-less" % beam)
         assert not np.array_equal(dev0[2], dev[2])
@@ -119,6 +129,7 @@ def step_fallback():
     s = hanzi_scorer(0.8, 0.4)
     for beam, topn in ((130, 40), (10, 50)):
         dev = ctc_prefix_beam_decode(probs.cuda(), lens, beam, 0.99, topn, ext_scorer=s)
+        ran(PATH_HOST, "fallback beam %d top_n %d" % (beam, topn))
         host = ctc_prefix_beam_decode(probs.numpy(), lens, beam, 0.99, topn, ext_scorer=s, num_threads=4)
         same(dev, host, "fallback beam %d top_n %d" % (beam, topn))
         print("beam %d, cutoff_top_n %d (outside the device search): the call ran the host search and agrees" % (beam, topn))
@@ -150,8 +161,10 @@ def step_pipeline(tmp):
     for xx, res in zip(xs, outs[1:]):
         lgs, cs = m.predict(xx)
         seq = ctc_prefix_beam_decode(lgs, cs, 10, 0.99, 40, is_logits=True, ext_scorer=s)
+        ran(PATH_SCORER, "pipeline, sequential call")
         same(res, seq, "pipeline")
         plain = ctc_prefix_beam_decode(lgs, cs, 10, 0.99, 40, is_logits=True)
+        ran(PATH_SMALL, "pipeline, scorer-less call")
     assert not np.array_equal(plain[2], seq[2])
     print("ChunkBeamPipeline with a scorer == the sequential calls on 3 batches; frames per utterance %s" % cs.tolist())
 
@@ -179,6 +192,7 @@ def step_chunk_asr(tmp):
     text = asr.offline_stt(path)
     logits, _ = asr.runner.predict(asr.load_wav(path).reshape([1, -1, 1]))
     ids, lens, sc, n = ctc_prefix_beam_decode(logits, None, 4, is_logits=True, ext_scorer=asr.text_featurizer.scorer)
+    ran(PATH_SCORER, "ChunkASR's search")
     want = "".join(asr.text_featurizer.iextract([int(t) for t in ids[0, 0, :lens[0, 0]] if t != 0]))
     assert text == want, (text, want)
     conf["tar_config"]["beam_width"] = 1

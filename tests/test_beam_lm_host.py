@@ -1,6 +1,9 @@
 """The n-gram scorer of the CTC prefix beam search on the host: the ARPA reader, `mi355asr_lm_score`, the host search and the
-stateful decoder with a scorer against the reference's own decoder (tests/golden/beam_lm_kat.npz, recorded by
-tests/golden/make_beam_lm_golden.py from the reference's unmodified sources), and the Python surface.  No GPU."""
+stateful decoder with a scorer against the reference's own decoder (tests/golden/beam_lm_kat.npz: orders 3 and 4, recorded by
+tests/golden/make_beam_lm_golden.py from the reference's unmodified sources; tests/golden/beam_lm_orders_kat.npz: orders 1, 2,
+5, 6 and an order-6 model too wide for packed table keys, at the beam widths where the device search changes kernels, recorded
+by make_beam_lm_orders_golden.py), and the Python surface.  No GPU."""
+import ctypes
 import gzip
 import json
 import os
@@ -17,8 +20,21 @@ from tensorflowasr_amd.models import BeamDecoder, ctc_prefix_beam_decode
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 K = np.load(os.path.join(GOLDEN, "beam_lm_kat.npz"))
 VOCAB = json.loads(str(K["vocabulary"]))
-ARPA = {3: os.path.join(GOLDEN, "lm_small.arpa"), 4: os.path.join(GOLDEN, "lm_small4.arpa")}
+KO = np.load(os.path.join(GOLDEN, "beam_lm_orders_kat.npz"))
+assert json.loads(str(KO["vocabulary"])) == VOCAB
+ARPA = {3: os.path.join(GOLDEN, "lm_small.arpa"), 4: os.path.join(GOLDEN, "lm_small4.arpa"), 1: os.path.join(GOLDEN, "lm_small1.arpa"),
+        2: os.path.join(GOLDEN, "lm_small2.arpa"), 5: os.path.join(GOLDEN, "lm_small5.arpa"), 6: os.path.join(GOLDEN, "lm_small6.arpa"),
+        "w6": os.path.join(GOLDEN, "lm_wide6.arpa")}
+MODELS = [3, 4, 1, 2, 5, 6, "w6"]                                       # a model's name in the fixtures is str() of these
 _scorers = {}
+
+
+def order_of(model):
+    return 6 if model == "w6" else model
+
+
+def fixture_of(model):
+    return K if model in (3, 4) else KO
 
 
 def scorer(order, alpha=1.0, beta=0.0):
@@ -30,19 +46,24 @@ def scorer(order, alpha=1.0, beta=0.0):
 
 
 # ---- ARPA reader -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("order", [3, 4])
-def test_arpa_reader_round_trips_the_fixture(order, tmp_path):
-    m = ngram.read_arpa(ARPA[order])
-    o, counts, grams = ny.parse_arpa(ARPA[order])                       # the direct parse
+@pytest.mark.parametrize("model", MODELS)
+def test_arpa_reader_round_trips_the_fixture(model, tmp_path):
+    order = order_of(model)
+    m = ngram.read_arpa(ARPA[model])
+    o, counts, grams = ny.parse_arpa(ARPA[model])                       # the direct parse
     assert m.order == o == order and m.counts == [counts[k] for k in range(1, o + 1)]
-    assert 150 <= len(m.words) <= 250 and sum(m.counts) >= 2000
+    if model == "w6":
+        assert len(m.words) >= 2100 and len(m.words).bit_length() * order > 64
+    else:
+        assert 150 <= len(m.words) <= 250 and sum(m.counts) >= (2000 if model in (3, 4) else len(m.words))
+    assert all(c > 0 for c in m.counts)
     for k in range(1, o + 1):
         assert len(grams[k]) == m.counts[k - 1]
         for row, lp, bo in zip(m.ids[k - 1].tolist(), m.logp[k - 1], m.backoff[k - 1]):
             e = grams[k][tuple(m.words[i - 1] for i in row)]
             assert lp == np.float32(e[0]) and bo == np.float32(e[1] or 0.0)
     gz = tmp_path / "lm.arpa.gz"
-    with open(ARPA[order], "rb") as f, gzip.open(gz, "wb") as g:
+    with open(ARPA[model], "rb") as f, gzip.open(gz, "wb") as g:
         shutil.copyfileobj(f, g)
     z = ngram.read_arpa(str(gz))
     assert z.words == m.words and z.counts == m.counts
@@ -80,11 +101,13 @@ def test_word_based_model_is_refused(tmp_path):
 
 
 # ---- get_log_cond_prob / mi355asr_lm_score -----------------------------------------------------------------------------
-@pytest.mark.parametrize("order", [3, 4])
-def test_lm_score_equals_the_reference_scorer(order):
-    s = scorer(order)
-    q = json.loads(str(K["ngram_queries"]))[str(order)]
-    ref = K["cond_%d" % order]
+@pytest.mark.parametrize("model", MODELS)
+def test_lm_score_equals_the_reference_scorer(model):
+    order, F = order_of(model), fixture_of(model)
+    s = scorer(model)
+    q = json.loads(str(F["ngram_queries"]))[str(model)]
+    ref = F["cond_%s" % model]
+    assert len(ref) == len(q["ngrams"]) >= 200
     assert s.is_character_based() and s.get_max_order() == order and s.get_dict_size() == 0
     assert (ref == -1000.0).any() and (ref != -1000.0).any()
     full = [i for i, g in enumerate(q["ngrams"]) if len(g) == order]
@@ -94,19 +117,21 @@ def test_lm_score_equals_the_reference_scorer(order):
     ids = np.array([[s.word_id(w) for w in q["ngrams"][i]] for i in full], np.int32)
     lib = s.score_ids(ids)
     assert lib.dtype == np.float32 and np.array_equal(lib.astype(np.float64), ref[full])
-    for words, r in zip(q["sentences"], K["sent_%d" % order]):
+    assert len(q["sentences"]) == len(F["sent_%s" % model]) >= 10
+    for words, r in zip(q["sentences"], F["sent_%s" % model]):
         assert s.get_sent_log_prob(words) == r, words
 
 
-@pytest.mark.parametrize("order", [3, 4])
-def test_lm_score_against_the_float64_yardstick(order):
-    s = scorer(order)
-    y = ny.BackoffLM(ARPA[order])
-    rng = np.random.default_rng(order)
+@pytest.mark.parametrize("model", MODELS)
+def test_lm_score_against_the_float64_yardstick(model):
+    order = order_of(model)
+    s = scorer(model)
+    y = ny.BackoffLM(ARPA[model])
+    rng = np.random.default_rng(order + 10 * (model == "w6"))
     n_words = len(s.model.words)
     ids = rng.integers(1, n_words + 1, size=(3000, order)).astype(np.int32)
     seen = np.concatenate([np.pad(s.model.ids[k], ((0, 0), (order - 1 - k, 0)), constant_values=s.bos_word) for k in range(order)])
-    ids = np.concatenate([ids, seen[rng.choice(len(seen), 1500, replace=False)]])
+    ids = np.concatenate([ids, seen[rng.choice(len(seen), min(1500, len(seen)), replace=False)]])
     ids[rng.choice(len(ids), 50, replace=False), rng.integers(order, size=50)] = 0      # OOV somewhere
     got = s.score_ids(ids)
     unk = s.model.word_to_id["<unk>"]
@@ -122,8 +147,8 @@ def test_lm_score_against_the_float64_yardstick(order):
         assert abs(float(g) - want) <= margin, (words, float(g), want, terms)
         worst = max(worst, abs(float(g) - want))
         backed += len(terms) > 1
-    print("order %d: %d n-grams, %d backed off, max |lib - float64| = %.3g" % (order, len(ids), backed, worst))
-    assert backed > 1000
+    print("model %s: %d n-grams, %d backed off, max |lib - float64| = %.3g" % (model, len(ids), backed, worst))
+    assert backed > 1000 if order > 1 else backed == 0                   # a unigram model has nothing to back off from
 
 
 def test_hashed_keys_for_models_too_wide_to_pack():
@@ -147,10 +172,35 @@ def test_hashed_keys_for_models_too_wide_to_pack():
     assert n > 4000
 
 
+class _LmView(ctypes.Structure):
+    """LmView of csrc/lm_table.h"""
+    _fields_ = [("cells", ctypes.c_void_p), ("shift", ctypes.c_uint32), ("mask", ctypes.c_uint32), ("order", ctypes.c_int32),
+                ("bits", ctypes.c_int32), ("bos", ctypes.c_int32)]
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_table_key_mode_of_every_fixture_model(model):
+    """the wide model's table really is in hashed mode (bits = 0), the others keep their word ids in the key"""
+    from tensorflowasr_amd import _lib
+    fn = _lib.lib().mi355asr_lm_host_view
+    fn.restype, fn.argtypes = ctypes.POINTER(_LmView), [ctypes.c_void_p]
+    s = scorer(model)
+    v = fn(s.handle()).contents
+    n_words = len(s.model.words)
+    assert v.order == order_of(model) and v.bos == s.bos_word and v.mask + 1 >= 2 * sum(s.model.counts)
+    if model == "w6":
+        assert v.bits == 0 and n_words.bit_length() * v.order > 64
+    else:
+        assert v.bits == n_words.bit_length() and v.bits * v.order <= 64
+
+
 # ---- the searches ------------------------------------------------------------------------------------------------------
-def _check(ids, lens, sc, n, ref_ids, ref_lens, ref_sc, what):
+def _check(ids, lens, sc, n, ref_ids, ref_lens, ref_sc, what, live_only=False):
     """scores bit for bit; hypotheses exactly where the reference specifies them (no tied scores), else as test_host.py treats
-    beam_long_kat.npz: which of several prefixes of equal score survives is left to std::nth_element there"""
+    beam_long_kat.npz: which of several prefixes of equal score survives is left to std::nth_element there.
+    live_only (the orders fixture, whose cutoff_top_n 1 and 2 cases fill the beam with prefixes that lost ALL their probability:
+    score -FLT_MAX, every one tied with every other): a rank whose score no other rank shares holds the reference's hypothesis,
+    and the nine-tenths overlap is asked of the hypotheses that still have a probability."""
     nn = len(ref_sc)
     assert n == nn, what
     assert np.array_equal(sc[:nn].astype(np.float64), ref_sc), what
@@ -160,7 +210,12 @@ def _check(ids, lens, sc, n, ref_ids, ref_lens, ref_sc, what):
     tied = np.array([(ref_sc == v).sum() > 1 for v in ref_sc])
     if not tied.any():
         assert ours == ref and np.array_equal(lens[:nn], ref_lens), what
-    assert len(set(ours) & set(ref)) >= 0.9 * nn, what
+    if live_only:
+        assert all(ours[j] == ref[j] for j in range(nn) if not tied[j]), what
+        live = ref_sc > -np.finfo(np.float32).max
+        assert len(set(o for o, a in zip(ours, live) if a) & set(r for r, a in zip(ref, live) if a)) >= 0.9 * live.sum(), what
+    else:
+        assert len(set(ours) & set(ref)) >= 0.9 * nn, what
     return not tied.any()
 
 
@@ -181,7 +236,53 @@ def test_host_search_reproduces_the_reference_with_a_scorer():
     assert exact >= 10
 
 
+def _orders_cases(model):
+    return [(i, m) for i, m in enumerate(json.loads(str(KO["meta"]))) if m["model"] == str(model)]
+
+
+def test_orders_fixture_holds_the_cases_it_is_for():
+    meta = json.loads(str(KO["meta"]))
+    pruned = [m for m in meta if m["cutoff_prob"] < 1.0]
+    assert {m["model"] for m in meta} == {"1", "2", "5", "6", "w6"} and {m["order"] for m in meta} == {1, 2, 5, 6}
+    assert {m["beam"] for m in pruned} >= {1, 2, 15, 16, 17, 64, 65, 127, 128} and {m["cutoff_top_n"] for m in pruned} >= {1, 2, 15, 40}
+    assert sum(m["cutoff_prob"] == 1.0 for m in meta) >= 2 and sum(m["T"] >= 400 and m["order"] == 6 for m in meta) >= 2
+    assert any(m["order"] >= 5 and m["longest"] >= 6 for m in meta)      # every age of the history holds a real word somewhere
+    for name in ("1", "2", "5", "6", "w6"):
+        mine = [m for m in meta if m["model"] == name]
+        assert any(m["alpha"] > 0 for m in mine) and any(m["alpha"] == 0 and m["beta"] == 0 for m in mine)
+        assert 2 * sum(m["differs_from_scorerless"] for m in mine if m["alpha"] > 0) >= sum(m["alpha"] > 0 for m in mine)
+    short = [m for m in meta if m["T"] <= 100]
+    assert 3 * sum(not m["tied"] for m in short) >= 2 * len(short)
+    assert sorted(m["order"] for m in json.loads(str(KO["stateful_meta"]))) == [1, 2, 5, 6]
+
+
+@pytest.mark.parametrize("model", [1, 2, 5, 6, "w6"])
+def test_host_search_reproduces_the_reference_at_the_other_orders_and_widths(model):
+    cases = _orders_cases(model)
+    assert len(cases) >= 15
+    exact = 0
+    for i, m in cases:
+        s = scorer(model, m["alpha"], m["beta"])
+        assert s.get_max_order() == m["order"] and os.path.basename(ARPA[model]) == m["arpa"]
+        ids, lens, sc, n = ctc_prefix_beam_decode(KO["probs_%d" % i][None], None, m["beam"], m["cutoff_prob"], m["cutoff_top_n"],
+                                                  num_threads=1, ext_scorer=s)
+        exact += _check(ids[0], lens[0], sc[0], n[0], KO["ids_%d" % i], KO["lens_%d" % i], KO["scores_%d" % i], "case %d %s" % (i, m), live_only=True)
+        if m["differs_from_scorerless"]:
+            i0, l0, _, _ = ctc_prefix_beam_decode(KO["probs_%d" % i][None], None, m["beam"], m["cutoff_prob"], m["cutoff_top_n"], num_threads=1)
+            assert tuple(i0[0, 0, :l0[0, 0]]) != tuple(ids[0, 0, :lens[0, 0]]), i
+    assert 3 * exact >= 2 * len(cases)
+
+
 def test_stateful_decoder_with_a_scorer_fed_in_pieces():
+    _stateful_in_pieces(K)
+
+
+def test_stateful_decoder_at_orders_1_2_5_6_fed_in_pieces():
+    _stateful_in_pieces(KO)
+
+
+def _stateful_in_pieces(F):
+    K = F
     for k, m in enumerate(json.loads(str(K["stateful_meta"]))):
         s = scorer(m["order"], m["alpha"], m["beta"])
         p = K["st_probs_%d" % k]
@@ -195,7 +296,7 @@ def test_stateful_decoder_with_a_scorer_fed_in_pieces():
             for r, (_, t) in enumerate(res):
                 ids[r, :len(t)] = t
             _check(ids, np.array([len(t) for _, t in res], np.int32), np.array([x for x, _ in res], np.float32), len(res),
-                   K["st_ids_%d_%d" % (k, j)], K["st_lens_%d_%d" % (k, j)], ref_sc, "stateful %d piece %d" % (k, j))
+                   K["st_ids_%d_%d" % (k, j)], K["st_lens_%d_%d" % (k, j)], ref_sc, "stateful %d piece %d" % (k, j), live_only=F is KO)
         one = ctc_prefix_beam_decode(p[None], None, m["beam"], m["cutoff_prob"], m["cutoff_top_n"], num_threads=1, ext_scorer=s)
         assert [x for x, _ in res] == one[2][0, :one[3][0]].tolist()
         assert [t for _, t in res] == [one[0][0, j, :one[1][0, j]].tolist() for j in range(one[3][0])]

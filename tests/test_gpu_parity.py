@@ -974,12 +974,32 @@ def test_prefix_beam_device_search_long_inputs_vs_reference_decoder_and_host(tor
     same way: beam.hip Search::better)."""
     torch = torch_cuda
     from test_host import _long_kat_check
-    from tensorflowasr_amd.models import ctc_prefix_beam_decode
-    dev = _long_kat_check(lambda p, beam, cp, tn: ctc_prefix_beam_decode(torch.from_numpy(p).cuda(), None, beam, cp, tn))
+    from tensorflowasr_amd.models import beam_last_path, ctc_prefix_beam_decode
+    paths = set()
+
+    def on_device(p, beam, cp, tn):
+        r = ctc_prefix_beam_decode(torch.from_numpy(p).cuda(), None, beam, cp, tn)
+        assert beam_last_path() == _scorerless_device_path(p.shape[-1], beam, tn), (beam, tn, beam_last_path())
+        paths.add(beam_last_path())
+        return r
+
+    dev = _long_kat_check(on_device)
+    assert paths and paths <= {2, 3}                      # the device search, never its host fallback
     host = _long_kat_check(lambda p, beam, cp, tn: ctc_prefix_beam_decode(p, None, beam, cp, tn, num_threads=1))
     for d, h in zip(dev, host):
         for a, b in zip(d, h):
             assert np.array_equal(a, b)
+
+
+def _scorerless_device_path(V, beam, top_n):
+    """what mi355asr_beam_last_path has to report for a scorer-less call: the dispatch rule of include/mi355asr.h on the limits
+    the library reports (1 host search on the top-n lists, 2 one-key-per-thread kernel, 3 radix kernel)"""
+    from tensorflowasr_amd.models import beam_device_limits
+    lim = beam_device_limits(False)
+    N = min(top_n, V)
+    if V > lim["max_classes"] or beam > lim["max_beam"] or N > lim["max_top_n"]:
+        return 1
+    return 2 if beam <= lim["small_beam"] and beam * (min(N, beam + 2) + 1) <= 256 else 3
 
 
 @pytest.mark.parametrize("beam", [1, 4, 10, 14, 15, 40, 100])
@@ -989,7 +1009,7 @@ def test_prefix_beam_device_search_equals_host_search(torch_cuda, beam):
     same probabilities: peaked rows (the cumulative cut keeps a handful of classes), flat rows (all 40 candidates,
     closely spaced scores), blank-dominated rows; ragged lengths including 0 and 1."""
     torch = torch_cuda
-    from tensorflowasr_amd.models import ctc_prefix_beam_decode
+    from tensorflowasr_amd.models import beam_last_path, ctc_prefix_beam_decode
     rng = np.random.default_rng(100 + beam)
     B, T, V = 6, 90, 300
     z = rng.standard_normal((B, T, V)).astype(np.float32)
@@ -1006,6 +1026,8 @@ def test_prefix_beam_device_search_equals_host_search(torch_cuda, beam):
     in_len = np.array([T, T, 61, T, 1, 0], np.int32)
     for cutoff_prob, top_n in ((0.99, 40), (0.9999, 25)):
         d = ctc_prefix_beam_decode(torch.from_numpy(p).cuda(), in_len, beam, cutoff_prob, top_n)
+        # the device search itself, and the kernel the dispatch rule names (every path returns the same arrays)
+        assert beam_last_path() == _scorerless_device_path(V, beam, top_n) == (2 if beam <= 14 else 3)
         h = ctc_prefix_beam_decode(p, in_len, beam, cutoff_prob, top_n)
         assert np.array_equal(d[3], h[3])
         assert np.array_equal(d[2], h[2])                  # the ranked scores, bit for bit
