@@ -211,7 +211,7 @@ int mi355asr_ctc_prefix_beam(const float* x_dev, int32_t is_logits, const int32_
 /* Which search the last mi355asr_ctc_prefix_beam / mi355asr_ctc_prefix_beam_lm call of the CALLING THREAD ran: 0 none yet;
  * 1 the host search on the device's top-n lists (outside the device search's limits, a workspace below
  * mi355asr_ctc_prefix_beam*_workspace_bytes, or MI355ASR_BEAM_DEVICE=0); 2 the device search's one-key-per-thread kernel;
- * 3 its radix kernel; 4 the device search with a scorer.  All of them return the same arrays, so this is the only way to
+ * 3 its radix kernel; 4 the device search with a scorer; 5, 6, 7: mi355asr_beam_streams_step (below).  All of them return the same arrays, so this is the only way to
  * tell them apart; it is set on the host from the conditions that choose the launch.
  * mi355asr_beam_device_limits: the limits those conditions use -- the device search serves V <= max_classes, beam_size <=
  * max_beam, min(cutoff_top_n, V) <= max_top_n; without a scorer the one-key-per-thread kernel runs when beam_size <=
@@ -239,6 +239,9 @@ int mi355asr_beam_decode(mi355asr_beam* d, const float* probs_host, int32_t T, i
                          int32_t* lens_host, float* scores_host, int32_t* n_hyp_host);
 int mi355asr_beam_reset(mi355asr_beam* d);
 int mi355asr_beam_destroy(mi355asr_beam* d);
+/* a copy of the decoder as it stands (trie, frame count, scorer reference): feeding the copy leaves the original untouched --
+ * how a caller looks at provisional frames */
+int mi355asr_beam_clone(const mi355asr_beam* d, mi355asr_beam** out);
 
 /* The external scorer of the prefix beam search: a back-off n-gram language model in CHARACTER-BASED mode.
  * replaces: Scorer(alpha, beta, lm_path, vocab_list) of externals/ctc_decoders (scorer.h, scorer.cpp; KenLM behind
@@ -470,6 +473,48 @@ int mi355asr_chunk_streams_reset(mi355asr_model* m, void* state_dev, int32_t n_s
 int mi355asr_chunk_streams_step(mi355asr_model* m, void* state_dev, int32_t n_streams, const int32_t* slots_host,
                                 int32_t n, const float* packets_dev, const int32_t* n_samples_host,
                                 const mi355asr_chunk_streams_outputs* outs, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ---- prefix beam search for many live streams, state on the device ---------------------------------------------
+ * The stateful search of the mi355asr_beam handle, with or without a scorer, for n_streams streams at once, a few frames per call:
+ * stream b's result after k committed frames is that of the one-shot search over those k frames, whatever else shares the
+ * call.  A stream lives in a SLOT of a state buffer the caller allocates on the device: its beam in rank order, with a
+ * scorer every entry's LM history and own LM term, and a back-pointer arena of max_frames * beam_size + 1 cells
+ * (bytes per slot: 16 + beam_size * 36 (60 with a scorer) rounded up to 16, + 8 * (max_frames * beam_size + 1) rounded up
+ * to 16).  A new state buffer is reset as a whole first.
+ * A step gives stream i = slot slots_host[i] the rows x_dev[i, 0 .. n_commit_dev[i]) as FINAL frames, followed by
+ * n_peek_dev[i] PROVISIONAL frames (NULL: none): the reported beam is the one after all of them, the state keeps the beam
+ * after the final ones only -- a peek leaves no trace (what the text decoder's "unvalid" rows need: they are run again with
+ * more right context).  Both counts are DEVICE arrays, clamped to 0 .. T and 0 .. T - n_commit; rows behind them are padding
+ * and may hold anything.  A stream whose committed + commit + peek frames exceed max_frames consumes nothing, keeps its
+ * state, reports its unchanged beam and status 1 (decided on the device; a reset makes the slot usable again).
+ * There is NO host fallback: a configuration outside mi355asr_beam_device_limits (for the scorer or scorer-less search), a
+ * cutoff_prob outside (0, 1), a slot out of range or named twice, n_best outside 1 .. beam_size or a workspace below
+ * mi355asr_beam_streams_bytes is MI355ASR_EINVAL / MI355ASR_EWORKSPACE before anything is launched.  The step makes no host
+ * synchronisation (a scorer is uploaded to the device once, on its first use); mi355asr_beam_last_path reports 5 (radix
+ * kernel), 6 (with a scorer) or 7 (one key per thread: beam_size <= small_beam, scorer-less) for it.
+ * Outputs (device), n = streams of the call: */
+typedef struct {
+  int32_t* ids;             /* i32 [n, n_best, max_len]  best first, padded with -1, cut at max_len                   */
+  int32_t* lens;            /* i32 [n, n_best]           full lengths                                                 */
+  float*   scores;          /* f32 [n, n_best]           -FLT_MAX where there is no hypothesis                        */
+  int32_t* n_hyp;           /* i32 [n]                   min(entries of the beam, n_best)                             */
+  int32_t* frames;          /* i32 [n]                   frames committed after the call                              */
+  int32_t* status;          /* i32 [n]                   0 ok, 1 over capacity                                        */
+} mi355asr_beam_streams_outputs;
+/* bytes of the state for n_streams slots and of the workspace of a step over up to n_streams streams of up to T_max rows */
+int mi355asr_beam_streams_bytes(int32_t n_streams, int32_t V, int32_t beam_size, int32_t cutoff_top_n, int32_t max_frames,
+                                const mi355asr_lm* lm_or_null, int32_t T_max, size_t* state_bytes, size_t* ws_bytes);
+/* the n slots of slots_host (NULL: all n_streams) become fresh streams */
+int mi355asr_beam_streams_reset(void* state_dev, int32_t n_streams, int32_t V, int32_t beam_size, int32_t cutoff_top_n,
+                                int32_t max_frames, const mi355asr_lm* lm_or_null, const int32_t* slots_host, int32_t n,
+                                void* stream);
+/* x_dev f32 [n, T, V] probabilities, or logits with is_logits (blank = class V - 1) */
+int mi355asr_beam_streams_step(void* state_dev, int32_t n_streams, int32_t V, int32_t beam_size, double cutoff_prob,
+                               int32_t cutoff_top_n, int32_t max_frames, const mi355asr_lm* lm_or_null, double alpha,
+                               double beta, const int32_t* slots_host, int32_t n, const float* x_dev, int32_t is_logits,
+                               const int32_t* n_commit_dev, const int32_t* n_peek_dev, int32_t T, int32_t n_best,
+                               int32_t max_len, const mi355asr_beam_streams_outputs* outs, void* ws_dev, size_t ws_bytes,
+                               void* stream);
 
 /* ---- Translator: phoneme ids + encoder output -> text logits -------------------------------
  * replaces: Translator(inp_classes, tar_classes, dmodel, num_blocks, head_size, num_heads, kernel_size, dropout,

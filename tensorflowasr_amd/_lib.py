@@ -56,6 +56,11 @@ class ChunkStreamsOutputs(ctypes.Structure):
                                                "phone_logits", "text_logits", "picker_hidden")]
 
 
+class BeamStreamsOutputs(ctypes.Structure):
+    """mirror of `mi355asr_beam_streams_outputs`."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("ids", "lens", "scores", "n_hyp", "frames", "status")]
+
+
 class Mi355AsrError(RuntimeError):
     pass
 
@@ -102,6 +107,11 @@ SIGNATURES = {
     "mi355asr_beam_decode": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mi355asr_beam_reset": (ctypes.c_int, [_P]),
     "mi355asr_beam_destroy": (ctypes.c_int, [_P]),
+    "mi355asr_beam_clone": (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    "mi355asr_beam_streams_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "mi355asr_beam_streams_reset": (ctypes.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "mi355asr_beam_streams_step": (ctypes.c_int, [_P, _I, _I, _I, ctypes.c_double, _I, _I, _P, ctypes.c_double, ctypes.c_double, _P, _I,
+                                                  _P, _I, _P, _P, _I, _I, _I, ctypes.POINTER(BeamStreamsOutputs), _P, _SZ, _P]),
     "mi355asr_lm_create": (ctypes.c_int, [_I, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(_P)]),
     "mi355asr_lm_destroy": (ctypes.c_int, [_P]),
     "mi355asr_lm_score": (ctypes.c_int, [_P, _P, _I, _P, _I, _P]),

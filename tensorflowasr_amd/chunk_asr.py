@@ -214,6 +214,11 @@ class _Stream:
         self.valid = _Greedy(text_blank)        # over the final text frames
         self.n_valid = 0
         self.unvalid = []                       # the text frames that still wait for right context (of the last decoder run)
+        self.beam_ids = []                      # beam_width > 1: the best hypothesis after the last decoder run
+
+
+class BeamStateOverflow(RuntimeError):
+    """a stream's text has more frames than the server's beam state holds (`max_text_frames`)"""
 
 
 class ChunkStreamingServer:
@@ -228,9 +233,18 @@ class ChunkStreamingServer:
     that have a full packet; the tuples are those `stream_call` appends, one per packet completed.  The per-frame argmax
     comes from the head kernels; each stream's greedy text is continued on the host from its frame ids instead of being
     decoded again from all logits.  `stepper` (default: the recogniser's model) is anything with `open_streams`,
-    `reset_streams` and `stream_step` of `ChunkConformer`."""
+    `reset_streams` and `stream_step` of `ChunkConformer`.
 
-    def __init__(self, chunk_asr, n_streams, stepper=None):
+    `beam_width` > 1: a tuple's text is the best hypothesis of the prefix beam search (with `ext_scorer`, an n-gram scorer)
+    over the stream's final text frames plus, as a peek, the frames that still wait for right context -- `ChunkASR._beam_text`
+    (cutoff_prob 0.99, cutoff_top_n 40) on the rows the greedy text reads, kept on the device by a `BeamStreams` of
+    `max_text_frames` frames per stream and stepped inside the tick.  With a text decoder of win_back 0
+    the reference's unvalid part is zeros_like(valid logits): rows that only ever add id 0 to a greedy text, where it is dropped.
+    They are not fed to the search: the text is the committed beam's best.  A stream that outgrows `max_text_frames` gets a
+    `BeamStateOverflow` in the place of its tuple -- returned, not raised, as `StreamingASRServer` does for its history, so
+    that the other streams go on; `open()` resets a slot's beam with the rest of its state."""
+
+    def __init__(self, chunk_asr, n_streams, stepper=None, beam_width=1, ext_scorer=None, max_text_frames=1500, beam_host=False):
         from .models import StreamGuard
         self.asr = chunk_asr
         self.stepper = stepper if stepper is not None else chunk_asr.runner
@@ -241,6 +255,14 @@ class ChunkStreamingServer:
         self.streams = {}
         self.free = list(range(self.n_streams - 1, -1, -1))
         self.win_back = int(getattr(self.state, "win_back", 0))
+        self.beam = None
+        if int(beam_width) > 1:
+            from .models import BeamStreams
+            kw = {} if beam_host else {"device": getattr(self.stepper, "_h").device}
+            self.beam = BeamStreams(self.n_streams, chunk_asr.text_featurizer.num_classes, int(beam_width), 0.99, 40, ext_scorer,
+                                    max_frames=int(max_text_frames), host=bool(beam_host), **kw)
+        elif ext_scorer is not None:
+            raise ValueError("ext_scorer needs beam_width > 1: the greedy text has no use for a scorer")
 
     def open(self):
         if not self.free:
@@ -248,6 +270,8 @@ class ChunkStreamingServer:
         slot = self.free.pop()
         self.stepper.reset_streams(self.state, [slot])
         self.guard.reset([slot])
+        if self.beam is not None:
+            self.beam.reset([slot])
         self.streams[slot] = _Stream(self.asr.phone_featurizer.num_classes - 1, self.asr.text_featurizer.num_classes - 1)
         return slot
 
@@ -264,9 +288,12 @@ class ChunkStreamingServer:
             self._stream(s)
         lens = [len(r) for r in rows]
         self.guard.check(slots, lens)
-        res = self.stepper.stream_step(self.state, slots, rows)
+        if self.beam is not None:
+            res = self.stepper.stream_step(self.state, slots, rows, beam=self.beam)
+        else:
+            res = self.stepper.stream_step(self.state, slots, rows)
         self.guard.commit(slots, lens)
-        out = {}
+        out, full = {}, []
         sr = self.asr.speech_featurizer.sample_rate
         for s in slots:
             st, r = self.streams[s], res[s]
@@ -281,12 +308,20 @@ class ChunkStreamingServer:
                 st.n_valid += nv
                 # (win_back 0: the reference returns zeros_like(valid logits) as the unvalid part -- nv frames of class 0)
                 st.unvalid = list(r["text_ids"][nv:]) if self.win_back else [0] * nv
+                if self.beam is not None:
+                    if r["beam_status"] != 0:
+                        full.append(s)
+                    st.beam_ids = [int(t) for t in r["beam_ids"] if t != 0]
             out[s] = None
             if st.n_valid + len(st.unvalid) == 0 or st.n_phone_frames == 0:
                 continue
-            text = self.asr.text_featurizer.iextract(st.valid.fork().feed(st.unvalid).text())
+            ids = st.beam_ids if self.beam is not None else st.valid.fork().feed(st.unvalid).text()
+            text = self.asr.text_featurizer.iextract(ids)
             phone = self.asr.phone_featurizer.iextract(st.phones.text())
             out[s] = (st.packets * self.wav_buf_length / sr, " ".join(phone), "".join(text))
+        for s in full:                          # in the slot's place, returned and not raised: the other streams go on
+            out[s] = BeamStateOverflow("slot %d: more than max_text_frames = %d text frames in one stream (its search consumed "
+                                       "nothing of this tick); close and reopen it" % (s, self.beam.max_frames))
         return out
 
     def send(self, audio):

@@ -256,4 +256,131 @@ int mi355asr_beam_destroy(mi355asr_beam* d) {
   delete d;
   return 0;
 }
+int mi355asr_beam_clone(const mi355asr_beam* d, mi355asr_beam** out) {
+  if (!d || !out) return fail(MI355ASR_EINVAL, "null argument");
+  *out = new mi355asr_beam{mi355asr_beam_state_clone(d->st), d->V, d->beam};
+  return 0;
+}
+
+// ---- the device search for many live streams (beam_device.hip STREAM kernels) ----------
+namespace {
+// what every streams entry point checks first: the search is inside the device limits (no host fallback here)
+int check_streams_config(int32_t n_streams, int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n, int32_t max_frames,
+                         const mi355asr_lm* lm) {
+  if (n_streams < 1 || V < 2 || beam_size < 1 || cutoff_top_n < 1 || max_frames < 1)
+    return fail(MI355ASR_EINVAL, "beam streams: need n_streams >= 1, V >= 2, beam_size >= 1, cutoff_top_n >= 1, max_frames >= 1 (got %d, %d, %d, %d, %d)",
+                n_streams, V, beam_size, cutoff_top_n, max_frames);
+  if (!(cutoff_prob > 0.0) || !(cutoff_prob < 1.0))
+    return fail(MI355ASR_EINVAL, "beam streams: cutoff_prob %g: the device search needs 0 < cutoff_prob < 1 (at 1 the reference visits "
+                "every class); use one host mi355asr_beam per stream for that mode", cutoff_prob);
+  int lim[4];
+  mi355asr_beam_device_limit_values(lm != nullptr, &lim[0], &lim[1], &lim[2], &lim[3]);
+  if (V > lim[0]) return fail(MI355ASR_EINVAL, "beam streams: V=%d is above the device search's max_classes=%d", V, lim[0]);
+  if (beam_size > lim[1]) return fail(MI355ASR_EINVAL, "beam streams: beam_size=%d is above the device search's max_beam=%d", beam_size, lim[1]);
+  if (std::min(cutoff_top_n, V) > lim[2])
+    return fail(MI355ASR_EINVAL, "beam streams: cutoff_top_n=%d is above the device search's max_top_n=%d", cutoff_top_n, lim[2]);
+  if (lm && !mi355asr_beam_device_lm_applicable(V, std::min(cutoff_top_n, V), beam_size, mi355asr_lm_host_view(lm)->order))
+    return fail(MI355ASR_EINVAL, "beam streams: language model order %d is outside the device search", mi355asr_lm_host_view(lm)->order);
+  if ((size_t)max_frames * beam_size + 1 > (size_t)0x7fffffff)
+    return fail(MI355ASR_EINVAL, "beam streams: max_frames * beam_size = %zu cells do not fit the arena's 31-bit links", (size_t)max_frames * beam_size);
+  return 0;
+}
+// workspace of a step over n streams of T frames: top-n lists (+ LM words, blank probabilities), the slot table
+size_t streams_ws(size_t n, size_t T, int N, bool lm, size_t* off_slots) {
+  const size_t frames = n * T;
+  size_t need = frames * N * (sizeof(int32_t) + sizeof(float)) + (lm ? frames * N * sizeof(int32_t) + frames * sizeof(float) : 0);
+  need = (need + 255) & ~(size_t)255;
+  if (off_slots) *off_slots = need;
+  return need + ((n * sizeof(int32_t) + 255) & ~(size_t)255);
+}
+}  // namespace
+
+int mi355asr_beam_streams_bytes(int32_t n_streams, int32_t V, int32_t beam_size, int32_t cutoff_top_n, int32_t max_frames,
+                                const mi355asr_lm* lm, int32_t T_max, size_t* state_bytes, size_t* ws_bytes) {
+  if (!state_bytes || !ws_bytes) return fail(MI355ASR_EINVAL, "null pointer");
+  if (T_max < 1) return fail(MI355ASR_EINVAL, "beam streams: T_max must be >= 1 (got %d)", T_max);
+  if (int rc = check_streams_config(n_streams, V, beam_size, 0.5, cutoff_top_n, max_frames, lm)) return rc;
+  *state_bytes = (size_t)n_streams * mi355asr_beam_stream_slot_bytes(beam_size, max_frames, lm != nullptr);
+  *ws_bytes = streams_ws((size_t)n_streams, (size_t)T_max, std::min(cutoff_top_n, V), lm != nullptr, nullptr);
+  return 0;
+}
+
+int mi355asr_beam_streams_reset(void* state_dev, int32_t n_streams, int32_t V, int32_t beam_size, int32_t cutoff_top_n, int32_t max_frames,
+                                const mi355asr_lm* lm, const int32_t* slots_host, int32_t n, void* stream) {
+  if (!state_dev || ((uintptr_t)state_dev & 15)) return fail(MI355ASR_EINVAL, "beam streams: state_dev must be a 16-byte aligned device pointer");
+  if (int rc = check_streams_config(n_streams, V, beam_size, 0.5, cutoff_top_n, max_frames, lm)) return rc;
+  if (slots_host) {
+    if (n < 1) return fail(MI355ASR_EINVAL, "beam streams: reset of %d slots", n);
+    for (int i = 0; i < n; ++i)
+      if (slots_host[i] < 0 || slots_host[i] >= n_streams) return fail(MI355ASR_EINVAL, "beam streams: slot %d out of range 0 .. %d", slots_host[i], n_streams - 1);
+  }
+  if (mi355asr_launch_beam_stream_reset(state_dev, n_streams, beam_size, max_frames, lm != nullptr, lm ? mi355asr_lm_host_view(lm)->bos : 0,
+                                        slots_host, n, (hipStream_t)stream) != 0)
+    return fail(MI355ASR_EHIP, "beam streams: reset kernel launch failed");
+  return 0;
+}
+
+int mi355asr_beam_streams_step(void* state_dev, int32_t n_streams, int32_t V, int32_t beam_size, double cutoff_prob, int32_t cutoff_top_n,
+                               int32_t max_frames, const mi355asr_lm* lm, double alpha, double beta, const int32_t* slots_host, int32_t n,
+                               const float* x_dev, int32_t is_logits, const int32_t* n_commit_dev, const int32_t* n_peek_dev, int32_t T,
+                               int32_t n_best, int32_t max_len, const mi355asr_beam_streams_outputs* outs, void* ws_dev, size_t ws_bytes,
+                               void* stream) {
+  if (!state_dev || !slots_host || !x_dev || !n_commit_dev || !outs || !ws_dev) return fail(MI355ASR_EINVAL, "null pointer");
+  if (!outs->ids || !outs->lens || !outs->scores || !outs->n_hyp || !outs->frames || !outs->status) return fail(MI355ASR_EINVAL, "null output pointer");
+  if ((uintptr_t)state_dev & 15) return fail(MI355ASR_EINVAL, "beam streams: state_dev must be 16-byte aligned");
+  if (int rc = check_streams_config(n_streams, V, beam_size, cutoff_prob, cutoff_top_n, max_frames, lm)) return rc;
+  if (int rc = check_scorer(lm, V, alpha, beta)) return rc;
+  if (n < 1 || n > n_streams || T < 1 || max_len < 1) return fail(MI355ASR_EINVAL, "beam streams: need 1 <= n <= n_streams, T >= 1, max_len >= 1 (got %d, %d, %d)", n, T, max_len);
+  if (n_best < 1 || n_best > beam_size) return fail(MI355ASR_EINVAL, "beam streams: n_best=%d must be 1 .. beam_size=%d", n_best, beam_size);
+  {
+    std::vector<char> seen((size_t)n_streams, 0);
+    for (int i = 0; i < n; ++i) {
+      const int sl = slots_host[i];
+      if (sl < 0 || sl >= n_streams) return fail(MI355ASR_EINVAL, "beam streams: slot %d out of range 0 .. %d", sl, n_streams - 1);
+      if (seen[sl]) return fail(MI355ASR_EINVAL, "beam streams: slot %d is named twice in one step", sl);
+      seen[sl] = 1;
+    }
+  }
+  const int N = std::min(cutoff_top_n, V);
+  size_t off_slots = 0;
+  const size_t need = streams_ws((size_t)n, (size_t)T, N, lm != nullptr, &off_slots);
+  if (ws_bytes < need) return fail(MI355ASR_EWORKSPACE, "beam streams: workspace too small: %zu < %zu bytes", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t frames = (size_t)n * T;
+  int32_t* d_idx = (int32_t*)ws_dev;
+  float* d_p = (float*)((char*)ws_dev + frames * N * sizeof(int32_t));
+  int32_t* d_w = lm ? (int32_t*)(d_p + frames * N) : nullptr;
+  float* d_blank = lm ? (float*)(d_w + frames * N) : nullptr;
+  int32_t* d_slots = (int32_t*)((char*)ws_dev + off_slots);
+  // the slot table comes from pageable host memory: the runtime stages it before the call returns, nothing is waited for
+  HIP_TRY(hipMemcpyAsync(d_slots, slots_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  // The selection runs over all n * T rows of the padded input; rows past commit + peek are padding whose lists the search never
+  // reads (its frame loop and its prefetch end at commit + peek).  topn_kernel / topn_reg_kernel are bounded by V and N whatever a
+  // row holds: every loop runs to V, N, 64 or G + min(E, N) <= GT_CAP + EQ_CAP, and every store is behind pg < GT_CAP, pe < EQ_CAP
+  // or before < N; lm_map_kernel maps a class outside [0, V - 1) to word 0.
+  if (mi355asr_launch_topn(x_dev, (int)frames, V, N, is_logits, d_idx, d_p, d_blank, s) != 0)
+    return fail(MI355ASR_EHIP, "top-n kernel launch failed (V=%d, cutoff_top_n=%d)", V, N);
+  BeamDeviceArgs a{};
+  a.top_idx = d_idx; a.top_p = d_p; a.B = n; a.T = T; a.V = V; a.N = N; a.beam = beam_size;
+  a.cutoff_top_n = cutoff_top_n; a.max_len = max_len; a.cutoff_prob = cutoff_prob;
+  a.ids = outs->ids; a.lens = outs->lens; a.scores = outs->scores; a.n_hyp = outs->n_hyp;
+  BeamStreamArgs sa{};
+  sa.state = (char*)state_dev; sa.slot_bytes = mi355asr_beam_stream_slot_bytes(beam_size, max_frames, lm != nullptr);
+  sa.slots = d_slots; sa.n_commit = n_commit_dev; sa.n_peek = n_peek_dev; sa.max_frames = max_frames; sa.n_best = n_best;
+  sa.frames = outs->frames; sa.status = outs->status;
+  int path;
+  if (lm) {
+    BeamLmDeviceArgs l{};
+    const int32_t* d_map = nullptr;
+    if (mi355asr_lm_device_view(lm, &l.view, &d_map) != 0) return fail(MI355ASR_EHIP, "language model upload failed");
+    if (mi355asr_launch_lm_map(d_idx, frames * N, d_map, V - 1, d_w, s) != 0) return fail(MI355ASR_EHIP, "LM word kernel launch failed");
+    l.top_w = d_w; l.blank_p = d_blank; l.alpha = alpha; l.beta = beta;
+    path = mi355asr_launch_beam_stream(&a, &l, &sa, s);
+  } else {
+    path = mi355asr_launch_beam_stream(&a, nullptr, &sa, s);
+  }
+  if (path < 0) return fail(MI355ASR_EHIP, "beam streams: search kernel launch failed");
+  last_path = path;
+  return 0;
+}
 }  // extern "C"

@@ -76,4 +76,38 @@ bool mi355asr_beam_device_lm_applicable(int V, int N, int beam, int order);
 int mi355asr_launch_lm_map(const int32_t* top_idx, size_t n, const int32_t* class_word_dev, int n_classes, int32_t* top_w,
                            hipStream_t s);
 int mi355asr_launch_beam_device_lm(const BeamDeviceArgs* a, const BeamLmDeviceArgs* l, hipStream_t s);
+void* mi355asr_beam_state_clone(const void* h);      // a copy of a stateful host decoder, trie and scorer included
+
+// ---- the device search for many live streams (beam_device.hip STREAM) ----
+// what a stream call reads besides BeamDeviceArgs (B = streams of the call, T = frames per stream in x; in_len and arena unused;
+// ids / lens / scores are [B, n_best, ...]); device pointers
+struct BeamStreamArgs {
+  char* state;              // [n_streams] slots of slot_bytes
+  size_t slot_bytes;
+  const int32_t* slots;     // [B] slot of each stream of the call
+  const int32_t* n_commit;  // [B] final frames
+  const int32_t* n_peek;    // [B] provisional frames behind them, or null
+  int max_frames, n_best;
+  int32_t* frames;          // [B] frames committed after the call
+  int32_t* status;          // [B] 0 ok, 1 over capacity (nothing consumed)
+};
+size_t mi355asr_beam_stream_slot_bytes(int beam, int max_frames, int with_lm);
+int mi355asr_launch_beam_stream_reset(void* state, int n_streams, int beam, int max_frames, int with_lm, int bos, const int32_t* slots_host,
+                                      int n, hipStream_t s);
+int mi355asr_launch_beam_stream(const BeamDeviceArgs* a, const BeamLmDeviceArgs* l, const BeamStreamArgs* sa, hipStream_t s);
+}
+
+// One slot: header int4 (entries, committed frames, 0, 0) | the Beam fields of `beam` entries, in rank order | with a scorer
+// lmhist [kLmMaxOrder - 1][beam] and lmterm [beam] | back-pointer arena int2 [max_frames * beam + 1], cell 1 + frame * beam + rank.
+// bytes = 16 + beam * (36 + 24 with a scorer), rounded up to 16, + 8 * (max_frames * beam + 1), rounded up to 16.
+struct BeamStreamLayout { unsigned id, par, ch, arena_i, score, b, nb, lmhist, lmterm, arena; size_t bytes; };   // beam <= 128: the offsets in front of the arena are small
+__host__ __device__ inline BeamStreamLayout beam_stream_layout(int beam, int max_frames, bool with_lm) {
+  BeamStreamLayout l;
+  const unsigned n = (unsigned)beam;
+  l.id = 16; l.par = l.id + 8 * n; l.ch = l.par + 8 * n; l.arena_i = l.ch + 4 * n; l.score = l.arena_i + 4 * n;
+  l.b = l.score + 4 * n; l.nb = l.b + 4 * n; l.lmhist = l.nb + 4 * n;
+  l.lmterm = l.lmhist + (with_lm ? 4 * (unsigned)(kLmMaxOrder - 1) * n : 0);
+  l.arena = (l.lmterm + (with_lm ? 4 * n : 0) + 15) & ~15u;
+  l.bytes = ((size_t)l.arena + 8 * ((size_t)max_frames * n + 1) + 15) & ~(size_t)15;
+  return l;
 }

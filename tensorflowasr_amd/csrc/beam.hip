@@ -718,6 +718,8 @@ void* mi355asr_beam_state_new_lm(int V, int beam_size, double cutoff_prob, int c
   return st;
 }
 void mi355asr_beam_state_free(void* h) { delete static_cast<BeamState*>(h); }
+// every member is a value or a pointer into the scorer, which the decoder does not own: the copy constructor is the clone
+void* mi355asr_beam_state_clone(const void* h) { return new BeamState(*static_cast<const BeamState*>(h)); }
 void mi355asr_beam_state_reset(void* h) {
   auto* st = static_cast<BeamState*>(h);
   st->s.reset(st->beam, st->V - 1);

@@ -442,8 +442,11 @@ __device__ __forceinline__ int select_radix(SH& sh, const Beam& C, Beam& Nx, con
 // (ties at the beam boundary, under-full beams) the frame is redone by select_radix over all candidates.
 // LM: with the scorer (l), always through select_radix (the small path's acceptance bound does not hold once children carry LM
 // terms); the scorer-less instantiations are the code they were before the scorer existed.
-template <bool SMALL, bool LM>
-__device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const BeamLmDeviceArgs* l) {
+// STREAM (round 7): the same search for one live stream of many, a few frames per launch.  The beam is
+// loaded from the slot's state in global memory instead of being the root, the call's first `commit` frames are final and
+// the beam after them is stored back; the `peek` frames behind them are provisional and only shape the beam this call reports.
+template <bool SMALL, bool LM, bool STREAM = false>
+__device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const BeamLmDeviceArgs* l, const BeamStreamArgs* sa = nullptr) {
   static_assert(!(SMALL && LM), "the scorer's search is the radix path");
   constexpr int NTT = SMALL ? NT : NTW, NWV = NTT / 64;      // threads / waves of this instantiation
   __shared__ std::conditional_t<LM, SharedLM, Shared> sh;
@@ -458,10 +461,54 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
   for (int i = tid; i < 2 * HASH / 4; i += NTT) reinterpret_cast<int4*>(sh.hpos)[i] = make_int4(0, 0, 0, 0);
   if (tid < 2) sh.cands[tid].n = 0;
   load_math_tabs(sh.math, tid, NTT);
-  const int frames = a.in_len ? max(0, min(a.in_len[b], T)) : T;
-  int2* arena = a.arena + (size_t)b * ((size_t)T * beam + 1);
+  // Frames are numbered over the stream's life: this call walks t0 <= t < tend, frame t being row t - t0 of x, so that the
+  // arena cell 1 + t * beam + rank is the absolute one and the frame parity of every table is t & 1 as in the one-shot search
+  // (t0 = 0, tend = frames there).
+  int t0 = 0, tend;
+  size_t row0;                              // (row of the lists that holds frame 0) -- b * T - t0
+  int2* arena;
   int cur = 0, nbm = 1;                     // current beam buffer, number of entries
-  if (tid == 0) {
+  int tcommit = -1;                         // STREAM: the call's last final frame (t0 - 1: none)
+  char* slot_state = nullptr;
+  if constexpr (STREAM) {
+    // ---- resume instead of root: the slot's beam as the last commit left it (a reset slot holds the root entry)
+    slot_state = sa->state + (size_t)sa->slots[b] * sa->slot_bytes;
+    const BeamStreamLayout lay = beam_stream_layout(beam, sa->max_frames, LM);
+    const int4 hdr = *reinterpret_cast<const int4*>(slot_state);
+    nbm = min(max(hdr.x, 1), beam);
+    const int f0 = min(max(hdr.y, 0), sa->max_frames);
+    int commit = min(max(sa->n_commit[b], 0), T);
+    const int peek = sa->n_peek ? min(max(sa->n_peek[b], 0), T - commit) : 0;
+    int frames = commit + peek, status = 0;
+    // capacity, decided here on the device before any arena cell is written: the call's last frame would write cells up to
+    // (f0 + frames) * beam, the arena ends there at max_frames.  A stream over it consumes nothing and reports what it has.
+    if (f0 + frames > sa->max_frames) { status = 1; commit = 0; frames = 0; }
+    if (tid == 0) { sa->frames[b] = f0 + commit; sa->status[b] = status; }
+    t0 = f0; tend = f0 + frames; tcommit = f0 + commit - 1;
+    row0 = (size_t)b * T - (size_t)f0;      // (wraps below zero for b = 0: only row0 + t with t >= t0 is ever formed)
+    arena = reinterpret_cast<int2*>(slot_state + lay.arena);
+    if (tid < nbm) {
+      Beam& B0 = sh.beams[0];
+      B0.id[tid] = reinterpret_cast<const u64*>(slot_state + lay.id)[tid];
+      B0.par[tid] = reinterpret_cast<const u64*>(slot_state + lay.par)[tid];
+      B0.ch[tid] = reinterpret_cast<const int*>(slot_state + lay.ch)[tid];
+      B0.arena[tid] = reinterpret_cast<const int*>(slot_state + lay.arena_i)[tid];
+      B0.score[tid] = reinterpret_cast<const float*>(slot_state + lay.score)[tid];
+      B0.b[tid] = reinterpret_cast<const float*>(slot_state + lay.b)[tid];
+      B0.nb[tid] = reinterpret_cast<const float*>(slot_state + lay.nb)[tid];
+      B0.kc[tid] = -1;                      // derived data: computed below, against this call's first frame
+      if constexpr (LM) {
+#pragma unroll
+        for (int i = 0; i < kLmMaxOrder - 1; ++i) sh.lmhist[0][i][tid] = reinterpret_cast<const int*>(slot_state + lay.lmhist)[i * beam + tid];
+        sh.lmterm[0][tid] = reinterpret_cast<const float*>(slot_state + lay.lmterm)[tid];
+      }
+    }
+  } else {
+    tend = a.in_len ? max(0, min(a.in_len[b], T)) : T;
+    row0 = (size_t)b * T;
+    arena = a.arena + (size_t)b * ((size_t)T * beam + 1);
+  }
+  if (!STREAM && tid == 0) {
     Beam& B0 = sh.beams[0];
     B0.id[0] = 1; B0.par[0] = 0; B0.ch[0] = -1; B0.arena[0] = 0; B0.kc[0] = -1;
     B0.score[0] = 0.f; B0.b[0] = 0.f; B0.nb[0] = kNegInf;
@@ -485,12 +532,12 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
   int c_nx = 0;
   int w_nx = 0;                             // scorer: the LM word of c_nx, and (lane 0) the frame's blank probability
   float pb_nx = 0.f;
-  if (pl >= 0 && pl < N && frames > 0) {
-    p_nx = a.top_p[(size_t)b * T * N + pl];
-    c_nx = a.top_idx[(size_t)b * T * N + pl];
+  if (pl >= 0 && pl < N && tend > t0) {
+    p_nx = a.top_p[(row0 + t0) * N + pl];
+    c_nx = a.top_idx[(row0 + t0) * N + pl];
     if constexpr (LM) {
-      w_nx = l->top_w[(size_t)b * T * N + pl];
-      if (pl == 0) pb_nx = l->blank_p[(size_t)b * T];
+      w_nx = l->top_w[(row0 + t0) * N + pl];
+      if (pl == 0) pb_nx = l->blank_p[row0 + t0];
     }
   }
   auto prepare = [&](int tt) {              // wave 3 only: candidates of frame tt into cands[tt & 1]
@@ -522,6 +569,7 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
     }
     const bool mine = pl < n;
     if (profiling3) p_cum += clock64() - q0;
+    if constexpr (STREAM) c_nx = min(max(c_nx, 0), V - 1);   // a live stream's row may hold NaN (no list is written for it): stay inside the table
     if (mine) {
       tab[c_nx] = (unsigned char)(pl + 1);
       K.c[pl] = c_nx;
@@ -536,26 +584,37 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
       K.n = n;
       K.blank = bm ? (int)__builtin_ctzll(bm) : -1;
     }
-    if (pl < N && tt + 1 < frames) {
-      const size_t fn = ((size_t)b * T + tt + 1) * N + pl;
+    if (pl < N && tt + 1 < tend) {
+      const size_t fn = (row0 + tt + 1) * N + pl;
       p_nx = a.top_p[fn];
       c_nx = a.top_idx[fn];
       if constexpr (LM) {
         w_nx = l->top_w[fn];
-        if (pl == 0) pb_nx = l->blank_p[(size_t)b * T + tt + 1];
+        if (pl == 0) pb_nx = l->blank_p[row0 + tt + 1];
       }
     }
     if (profiling3) p_prep += clock64() - q0;
   };
   __syncthreads();                          // the cleared tables, K.n = 0
-  if (tid == 0) sh.hpos[0][1 & (HASH - 1)] = 1;      // the root's id is 1
-  if (pl >= 0 && frames > 0) prepare(0);
+  if (!STREAM && tid == 0) sh.hpos[0][1 & (HASH - 1)] = 1;      // the root's id is 1
+  if (pl >= 0 && tend > t0) prepare(t0);
   if (tid < 256) { sh.hist[0][tid] = 0; sh.hist[1][tid] = 0; }
-  if (tid < BMAX) sh.exist_mask[0][tid] = 0;
+  if (tid < BMAX) sh.exist_mask[t0 & 1][tid] = 0;
   if (tid < 2) sh.kmin[tid] = ~0ull;
   __syncthreads();
+  if constexpr (STREAM) {
+    // kc and the parent hash are derived data: when the state was saved, the frame they are computed against had not arrived.
+    // From prepare(0)'s class table and a hash_claim per entry, as keep_entry / keep_child do one frame ahead.
+    if (tid < nbm && tend > t0) {
+      Beam& B0 = sh.beams[0];
+      const int ch = B0.ch[tid];
+      B0.kc[tid] = ch >= 0 && ch < V ? (int)class_tab[(t0 & 1) * vstride + ch] - 1 : -1;
+      hash_claim(sh.hpos[0], B0.id[tid], tid);
+    }
+    __syncthreads();
+  }
 
-  for (int t = 0; t < frames; ++t) {
+  for (int t = t0; t < tend; ++t) {
     const Beam& C = sh.beams[cur];
     Beam& Nx = sh.beams[cur ^ 1];
     const Cands& K = sh.cands[t & 1];
@@ -564,7 +623,7 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
     long long t0 = 0;
     if (profiling) t0 = clock64();
     // ---- 1. (wave 3) the next frame's candidates
-    if (pl >= 0 && t + 1 < frames) prepare(t + 1);
+    if (pl >= 0 && t + 1 < tend) prepare(t + 1);
     if (tid < BMAX) sh.exist_mask[(t + 1) & 1][tid] = 0;
     if (tid < HASH / 4) reinterpret_cast<int4*>(sh.hpos[cur ^ 1])[tid] = make_int4(0, 0, 0, 0);   // HASH = 1024 cells = 256 int4
     const Lookup L = {class_tab + ((t + 1) & 1) * vstride, sh.hpos[cur ^ 1]};
@@ -691,38 +750,76 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
     }
     cur ^= 1;
     nbm = newn;
+    if constexpr (STREAM) {
+      // ---- commit: the beam after the call's last final frame goes back to the slot (the frame ended with a barrier).  The
+      // peek frames that follow write arena cells at or past 1 + (f0 + commit) * beam only: the beam saved here never points
+      // to them, and the next committed frames overwrite them -- a peek leaves no trace and needs no copy of the state.
+      if (t == tcommit) {
+        const Beam& S = sh.beams[cur];
+        const BeamStreamLayout lay = beam_stream_layout(beam, sa->max_frames, LM);   // (formed again here: not kept live over the frames)
+        int e = tid;                          // opaque: the per-thread addresses below would otherwise be formed ahead of the frame
+        asm volatile("" : "+v"(e));           // loop and held in registers across it (16 VGPRs; the scorer's kernel has none to spare)
+        if (e < nbm) {
+          reinterpret_cast<u64*>(slot_state + lay.id)[e] = S.id[e];
+          reinterpret_cast<u64*>(slot_state + lay.par)[e] = S.par[e];
+          reinterpret_cast<int*>(slot_state + lay.ch)[e] = S.ch[e];
+          reinterpret_cast<int*>(slot_state + lay.arena_i)[e] = S.arena[e];
+          reinterpret_cast<float*>(slot_state + lay.score)[e] = S.score[e];
+          reinterpret_cast<float*>(slot_state + lay.b)[e] = S.b[e];
+          reinterpret_cast<float*>(slot_state + lay.nb)[e] = S.nb[e];
+          if constexpr (LM) {
+#pragma unroll
+            for (int i = 0; i < kLmMaxOrder - 1; ++i) reinterpret_cast<int*>(slot_state + lay.lmhist)[i * beam + e] = sh.lmhist[cur][i][e];
+            reinterpret_cast<float*>(slot_state + lay.lmterm)[e] = sh.lmterm[cur][e];
+          }
+        }
+        if (tid == 0) *reinterpret_cast<int4*>(slot_state) = make_int4(nbm, t + 1, 0, 0);
+      }
+    }
   }
   if (profiling) {
     a.prof[0] = p_entries; a.prof[1] = p_keys; a.prof[2] = p_keep; a.prof[3] = p_radix; a.prof[4] = p_redone;
-    a.prof[5] = rprof.keys; a.prof[6] = rprof.select; a.prof[7] = rprof.install; a.prof[8] = frames;
+    a.prof[5] = rprof.keys; a.prof[6] = rprof.select; a.prof[7] = rprof.install; a.prof[8] = tend;
     a.prof[9] = p_own; a.prof[10] = p_scan;
   }
   if (profiling3) { a.prof[11] = p_prep; a.prof[12] = p_cum; }
 
   // ---- finish: rank by prefix_compare (+ slot), read the paths back
+  // (nout rows per utterance: the whole beam; a stream call reports its n_best <= beam best)
+  int nout = beam, cells = 0x7fffffff;
+  if constexpr (STREAM) { nout = sa->n_best; cells = sa->max_frames * beam + 1; }
   const Beam& C = sh.beams[cur];
-  const int n = min(nbm, beam);
-  int32_t* ids = a.ids + (size_t)b * beam * a.max_len;
-  int32_t* lens = a.lens + (size_t)b * beam;
-  float* scores = a.scores + (size_t)b * beam;
+  const int n = min(nbm, nout);
+  int32_t* ids = a.ids + (size_t)b * nout * a.max_len;
+  int32_t* lens = a.lens + (size_t)b * nout;
+  float* scores = a.scores + (size_t)b * nout;
   if (tid == 0) a.n_hyp[b] = n;
   for (int i = tid; i < beam; i += NTT) {
     if (i >= nbm) continue;
     const u64 ki = make_key(C.score[i], C.ch[i], i);
     int rank = 0;
     for (int j = 0; j < nbm; ++j) rank += make_key(C.score[j], C.ch[j], j) < ki;
-    if (rank >= beam) continue;
+    if (rank >= nout) continue;
     int len = 0;
-    for (int p = C.arena[i]; p > 0; p = arena[p].x) ++len;
+    if constexpr (STREAM) {                 // a state that was never reset must not send the walk anywhere: links stay inside the slot's arena
+      for (int p = C.arena[i]; p > 0 && p < cells && len < sa->max_frames; p = arena[p].x) ++len;
+    } else {
+      for (int p = C.arena[i]; p > 0; p = arena[p].x) ++len;
+    }
     lens[rank] = len;
     scores[rank] = C.score[i];
     int32_t* row = ids + (size_t)rank * a.max_len;
     for (int q = len; q < a.max_len; ++q) row[q] = -1;
     int q = len - 1;
-    for (int p = C.arena[i]; p > 0; p = arena[p].x, --q)
-      if (q < a.max_len) row[q] = arena[p].y;
+    if constexpr (STREAM) {
+      for (int p = C.arena[i]; p > 0 && p < cells && q >= 0; p = arena[p].x, --q)
+        if (q < a.max_len) row[q] = arena[p].y;
+    } else {
+      for (int p = C.arena[i]; p > 0; p = arena[p].x, --q)
+        if (q < a.max_len) row[q] = arena[p].y;
+    }
   }
-  for (int i = n + tid; i < beam; i += NTT) {
+  for (int i = n + tid; i < nout; i += NTT) {
     lens[i] = 0;
     scores[i] = kNegInf;
     for (int q = 0; q < a.max_len; ++q) ids[(size_t)i * a.max_len + q] = -1;
@@ -732,6 +829,37 @@ __device__ __forceinline__ void beam_search_body(const BeamDeviceArgs& a, const 
 template <bool SMALL>
 __global__ __launch_bounds__(SMALL ? NT : NTW) void beam_search_kernel(BeamDeviceArgs a) { beam_search_body<SMALL, false>(a, nullptr); }
 __global__ __launch_bounds__(NTW) void beam_search_lm_kernel(BeamDeviceArgs a, BeamLmDeviceArgs l) { beam_search_body<false, true>(a, &l); }
+// the stream instantiations (mi355asr_beam_streams_step): one workgroup per stream of the call
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? NT : NTW) void beam_stream_kernel(BeamDeviceArgs a, BeamStreamArgs sa) { beam_search_body<SMALL, false, true>(a, nullptr, &sa); }
+__global__ __launch_bounds__(NTW) void beam_stream_lm_kernel(BeamDeviceArgs a, BeamLmDeviceArgs l, BeamStreamArgs sa) { beam_search_body<false, true, true>(a, &l, &sa); }
+
+// a fresh stream: the root entry the one-shot kernel starts from, no committed frames.  One workgroup per slot named.
+struct BeamStreamResetArgs {
+  char* state;
+  size_t slot_bytes;
+  int beam, max_frames, with_lm, bos, n;    // n < 0: every slot, the grid is the number of slots
+  int slots[64];
+};
+__global__ __launch_bounds__(64) void beam_stream_reset_kernel(BeamStreamResetArgs r) {
+  if (threadIdx.x != 0) return;
+  const int slot = r.n < 0 ? (int)blockIdx.x : r.slots[blockIdx.x];
+  char* st = r.state + (size_t)slot * r.slot_bytes;
+  const BeamStreamLayout lay = beam_stream_layout(r.beam, r.max_frames, r.with_lm != 0);
+  *reinterpret_cast<int4*>(st) = make_int4(1, 0, 0, 0);
+  reinterpret_cast<u64*>(st + lay.id)[0] = 1;
+  reinterpret_cast<u64*>(st + lay.par)[0] = 0;
+  reinterpret_cast<int*>(st + lay.ch)[0] = -1;
+  reinterpret_cast<int*>(st + lay.arena_i)[0] = 0;
+  reinterpret_cast<float*>(st + lay.score)[0] = 0.f;
+  reinterpret_cast<float*>(st + lay.b)[0] = 0.f;
+  reinterpret_cast<float*>(st + lay.nb)[0] = kNegInf;
+  reinterpret_cast<int2*>(st + lay.arena)[0] = make_int2(-1, -1);
+  if (r.with_lm) {                          // "<s>" all the way back, no term of its own
+    for (int i = 0; i < kLmMaxOrder - 1; ++i) reinterpret_cast<int*>(st + lay.lmhist)[i * r.beam] = r.bos;
+    reinterpret_cast<float*>(st + lay.lmterm)[0] = 0.f;
+  }
+}
 
 // the device's evaluation of refmath.h, for the parity test against the host's libm (tests/test_gpu_parity.py)
 __global__ __launch_bounds__(256) void refmath_eval_kernel(int kind, const float* __restrict__ in, void* __restrict__ out, int n) {
@@ -831,6 +959,50 @@ int mi355asr_launch_beam_device_lm(const BeamDeviceArgs* a, const BeamLmDeviceAr
   }
   hipLaunchKernelGGL(beam_search_lm_kernel, dim3(a->B), dim3(NTW), dyn, s, *a, *l);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+
+// ---- streams (api_beam.hip checks the limits before it comes here) ----
+size_t mi355asr_beam_stream_slot_bytes(int beam, int max_frames, int with_lm) { return beam_stream_layout(beam, max_frames, with_lm != 0).bytes; }
+
+int mi355asr_launch_beam_stream_reset(void* state, int n_streams, int beam, int max_frames, int with_lm, int bos, const int32_t* slots_host,
+                                      int n, hipStream_t s) {
+  BeamStreamResetArgs r{};
+  r.state = (char*)state; r.slot_bytes = mi355asr_beam_stream_slot_bytes(beam, max_frames, with_lm);
+  r.beam = beam; r.max_frames = max_frames; r.with_lm = with_lm; r.bos = bos;
+  if (!slots_host) {
+    r.n = -1;
+    hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(n_streams), dim3(64), 0, s, r);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  for (int i0 = 0; i0 < n; i0 += 64) {      // the slots travel as kernel arguments: no staging buffer, no copy to wait for
+    r.n = std::min(64, n - i0);
+    for (int i = 0; i < r.n; ++i) r.slots[i] = slots_host[i0 + i];
+    hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(r.n), dim3(64), 0, s, r);
+    if (hipGetLastError() != hipSuccess) return -2;
+  }
+  return 0;
+}
+
+// -> the kernel that ran as mi355asr_beam_last_path reports it (5 radix, 6 with a scorer, 7 one key per thread), < 0 on failure
+int mi355asr_launch_beam_stream(const BeamDeviceArgs* a, const BeamLmDeviceArgs* l, const BeamStreamArgs* sa, hipStream_t s) {
+  const int dyn = 2 * tab_stride(a->V);
+  if (l ? !mi355asr_beam_device_lm_applicable(a->V, a->N, a->beam, l->view.order) : !mi355asr_beam_device_applicable(a->V, a->N, a->beam)) return -2;
+  static bool allowed_on[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
+  if (!allowed_on[dev]) {
+    if (hipFuncSetAttribute((const void*)beam_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tab_stride(kMaxClasses)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)beam_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tab_stride(kMaxClasses)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)beam_stream_lm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tab_stride(kMaxClassesLm)) != hipSuccess)
+      return -2;
+    allowed_on[dev] = true;
+  }
+  int path;
+  if (l) { path = 6; hipLaunchKernelGGL(beam_stream_lm_kernel, dim3(a->B), dim3(NTW), dyn, s, *a, *l, *sa); }
+  else if (mi355asr_beam_device_small(a->N, a->beam)) { path = 7; hipLaunchKernelGGL(beam_stream_kernel<true>, dim3(a->B), dim3(NT), dyn, s, *a, *sa); }
+  else { path = 5; hipLaunchKernelGGL(beam_stream_kernel<false>, dim3(a->B), dim3(NTW), dyn, s, *a, *sa); }
+  return hipGetLastError() == hipSuccess ? path : -2;
 }
 
 }  // extern "C"

@@ -872,7 +872,9 @@ def ctc_prefix_beam_decode(x, input_length=None, beam_width=10, cutoff_prob=0.99
 
 
 BEAM_PATHS = {0: "none", 1: "host search on the device's top-n lists", 2: "device, one key per thread", 3: "device, radix",
-              4: "device, with a scorer"}
+              4: "device, with a scorer", 5: "device streams, radix", 6: "device streams, with a scorer",
+              7: "device streams, one key per thread"}
+BEAM_STREAM_PATHS = (5, 6, 7)
 
 
 def beam_last_path():
@@ -1070,6 +1072,214 @@ class BeamDecoder:
 
     def decode(self, probs_seq):
         return [(sc, "".join(self.vocabulary[t] for t in toks)) for sc, toks in self.decode_ids(probs_seq)]
+
+    def fork(self):
+        """`mi355asr_beam_clone`: a copy of the decoder as it stands, scorer included.  Feeding the copy leaves this one
+        untouched: how provisional frames are looked at."""
+        d = BeamDecoder.__new__(BeamDecoder)
+        d.vocabulary, d.beam_size, d.lib, d.ext_scorer = self.vocabulary, self.beam_size, self.lib, self.ext_scorer
+        d._frames = getattr(self, "_frames", 0)
+        d.ptr = ctypes.c_void_p()
+        _lib.check(self.lib.mi355asr_beam_clone(self.ptr, ctypes.byref(d.ptr)))
+        return d
+
+
+class BeamStreams:
+    """The stateful prefix beam search for `n_streams` live streams, a few frames per tick (`mi355asr_beam_streams_*`,
+    DESIGN.md section 15): after k committed frames a slot's beam is that of the one-shot search over those k frames.
+
+        bs = BeamStreams(64, 9160, 10, cutoff_prob=0.99, ext_scorer=scorer, max_frames=1500)
+        res = bs.step(slots, logits, n_commit, n_peek)       # device tensors, no synchronisation
+        ids, lens, scores, n_hyp, frames, status = (bs.read(res)[k] for k in BeamStreams.FIELDS)
+
+    `num_classes` includes the blank (the last class).  step: x [n, T, V] on the device, row i for slot slots[i]; its first
+    n_commit[i] rows are final, the n_peek[i] rows behind them provisional: the reported beam is the one after all of them,
+    the state keeps the beam after the final ones.  n_commit / n_peek are int32 device tensors (or anything array-like).
+    A slot whose frames would exceed `max_frames` consumes nothing and reports status 1; `reset` makes it usable again.
+    The search runs on the device and only there: outside `beam_device_limits` the constructor raises and names the limit.
+    `host=True` is the same interface on one host `BeamDecoder` per slot (`fork()` for the peek): the stand-in without a
+    GPU, and the explicit way to run beams above 128, cutoff_top_n above 40 or cutoff_prob 1."""
+
+    FIELDS = ("ids", "lens", "scores", "n_hyp", "frames", "status")
+
+    def __init__(self, n_streams, num_classes, beam_size, cutoff_prob=1.0, cutoff_top_n=40, ext_scorer=None, max_frames=1500,
+                 device="cuda:0", host=False):
+        self.n_streams, self.num_classes, self.beam_size = int(n_streams), int(num_classes), int(beam_size)
+        self.cutoff_prob, self.cutoff_top_n, self.max_frames = float(cutoff_prob), int(cutoff_top_n), int(max_frames)
+        self.ext_scorer, self.host = ext_scorer, bool(host)
+        if self.n_streams < 1 or self.max_frames < 1 or self.beam_size < 1:
+            raise ValueError("BeamStreams: n_streams, beam_size and max_frames must be >= 1")
+        if ext_scorer is not None:
+            _check_scorer(ext_scorer)
+            if len(ext_scorer.vocabulary) != self.num_classes - 1:
+                raise ValueError("ext_scorer was built for %d classes, the streams have %d + blank"
+                                 % (len(ext_scorer.vocabulary), self.num_classes - 1))
+        if self.host:
+            vocab = [""] * self.num_classes
+            self.decoders = [BeamDecoder(vocab, self.beam_size, self.cutoff_prob, self.cutoff_top_n, ext_scorer)
+                             for _ in range(self.n_streams)]
+            self.committed = [0] * self.n_streams
+            return
+        lim = beam_device_limits(ext_scorer is not None)
+        for name, value, top in (("max_classes", self.num_classes, lim["max_classes"]), ("max_beam", self.beam_size, lim["max_beam"]),
+                                 ("max_top_n", min(self.cutoff_top_n, self.num_classes), lim["max_top_n"])):
+            if value > top:
+                raise ValueError("BeamStreams: %d is above the device search's %s = %d; host=True runs one host BeamDecoder per "
+                                 "stream instead" % (value, name, top))
+        if not 0.0 < self.cutoff_prob < 1.0:
+            raise ValueError("BeamStreams: the device search needs 0 < cutoff_prob < 1 (got %g: at 1 the reference visits every "
+                             "class); host=True runs one host BeamDecoder per stream instead" % self.cutoff_prob)
+        self.lib = _lib.lib()
+        self.device = torch.device(device)
+        self.state = self.ws = None
+        self._ws_T = 0
+        sb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(self.lib.mi355asr_beam_streams_bytes(*self._config()[:2], self.beam_size, self.cutoff_top_n, self.max_frames,
+                                                        self._lm()[0], 1, ctypes.byref(sb), ctypes.byref(wb)))
+        self.state_bytes = sb.value
+        self.state = torch.empty(sb.value, dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def _config(self):
+        return self.n_streams, self.num_classes
+
+    def _lm(self):
+        s = self.ext_scorer
+        return (s.handle(), float(s.alpha), float(s.beta)) if s is not None else (None, 0.0, 0.0)
+
+    def bytes_per_stream(self):
+        return self.state_bytes // self.n_streams
+
+    def reset(self, slots=None):
+        """the given slots (None: all) become fresh streams"""
+        tab = None if slots is None else [int(v) for v in slots]
+        if self.host:
+            for s in (range(self.n_streams) if tab is None else tab):
+                if not 0 <= s < self.n_streams:
+                    raise ValueError("slot %d out of range 0 .. %d" % (s, self.n_streams - 1))
+                self.decoders[s].reset()
+                self.committed[s] = 0
+            return
+        arr = None if tab is None else np.ascontiguousarray(tab, np.int32)
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(self.lib.mi355asr_beam_streams_reset(_p(self.state), self.n_streams, self.num_classes, self.beam_size,
+                                                            self.cutoff_top_n, self.max_frames, self._lm()[0],
+                                                            arr.ctypes.data_as(ctypes.c_void_p) if arr is not None else None,
+                                                            0 if arr is None else len(arr), st))
+
+    @staticmethod
+    def result_ints(n, n_best, max_len):
+        """int32 words of one step's results (`out=` of step): ids | lens | score bits | n_hyp | frames | status"""
+        return n * n_best * max_len + 2 * n * n_best + 3 * n
+
+    @staticmethod
+    def carve(buf, n, n_best, max_len):
+        o, r = 0, {}
+        for name, k, shape in (("ids", n * n_best * max_len, (n, n_best, max_len)), ("lens", n * n_best, (n, n_best)),
+                               ("scores", n * n_best, (n, n_best)), ("n_hyp", n, (n,)), ("frames", n, (n,)), ("status", n, (n,))):
+            r[name] = buf[o:o + k].reshape(shape)
+            o += k
+        r["scores"] = r["scores"].view(torch.float32 if torch.is_tensor(buf) else np.float32)
+        return r
+
+    def _check_step(self, slots, n_best, max_len):
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot is named twice in one step: %s" % (sorted(slots),))
+        for s in slots:
+            if not 0 <= s < self.n_streams:
+                raise ValueError("slot %d out of range 0 .. %d" % (s, self.n_streams - 1))
+        if not 1 <= n_best <= self.beam_size:
+            raise ValueError("n_best=%d must be 1 .. beam_size=%d" % (n_best, self.beam_size))
+        if max_len < 1 or not slots:
+            raise ValueError("a step needs at least one slot and max_len >= 1")
+
+    def step(self, slots, x, n_commit, n_peek=None, is_logits=True, n_best=1, max_len=None, out=None):
+        """-> dict of FIELDS: ids i32 [n, n_best, max_len] (-1 padded), lens i32 [n, n_best], scores f32 [n, n_best], n_hyp,
+        frames (committed after the call), status i32 [n] -- device tensors, nothing is waited for.  `out`: an int32 device
+        tensor of result_ints(...) words to put them in (one read-back shared with the caller's other integers)."""
+        slots = [int(v) for v in slots]
+        n, n_best = len(slots), int(n_best)
+        max_len = int(max_len or self.max_frames)
+        self._check_step(slots, n_best, max_len)
+        if self.host:
+            return self._step_host(slots, x, n_commit, n_peek, is_logits, n_best, max_len)
+        dev = self.device
+        xd = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(device=dev, dtype=torch.float32).contiguous()
+        if xd.dim() != 3 or xd.shape[0] != n or xd.shape[2] != self.num_classes:
+            raise ValueError("x: [%d, T, %d], got %s" % (n, self.num_classes, tuple(xd.shape)))
+        T = int(xd.shape[1])
+
+        def counts(v):
+            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+            t = t.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+            if t.numel() != n:
+                raise ValueError("%d slots, %d frame counts" % (n, t.numel()))
+            return t
+        nc = counts(n_commit)
+        npk = counts(n_peek) if n_peek is not None else None
+        if T > self._ws_T:
+            wb, sb = ctypes.c_size_t(), ctypes.c_size_t()
+            _lib.check(self.lib.mi355asr_beam_streams_bytes(self.n_streams, self.num_classes, self.beam_size, self.cutoff_top_n,
+                                                            self.max_frames, self._lm()[0], T, ctypes.byref(sb), ctypes.byref(wb)))
+            self.ws, self._ws_T = torch.empty(wb.value, dtype=torch.uint8, device=dev), T
+        words = self.result_ints(n, n_best, max_len)
+        if out is None:
+            out = torch.empty(words, dtype=torch.int32, device=dev)
+        elif out.numel() != words or out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError("out: a contiguous int32 tensor of %d words" % words)
+        res = self.carve(out, n, n_best, max_len)
+        outs = _lib.BeamStreamsOutputs(**{k: res[k].data_ptr() for k in self.FIELDS})
+        tab = np.asarray(slots, np.int32)
+        lm, alpha, beta = self._lm()
+        with torch.cuda.device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(self.lib.mi355asr_beam_streams_step(_p(self.state), self.n_streams, self.num_classes, self.beam_size, self.cutoff_prob,
+                                                           self.cutoff_top_n, self.max_frames, lm, alpha, beta,
+                                                           tab.ctypes.data_as(ctypes.c_void_p), n, _p(xd), int(bool(is_logits)), _p(nc),
+                                                           _p(npk) if npk is not None else None, T, n_best, max_len, ctypes.byref(outs),
+                                                           _p(self.ws), self.ws.numel(), st))
+        res["_keep"] = (xd, nc, npk)                           # inputs of an asynchronous call
+        return res
+
+    def _step_host(self, slots, x, n_commit, n_peek, is_logits, n_best, max_len):
+        def host(v):
+            return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        xh = np.ascontiguousarray(host(x), np.float32)
+        n = len(slots)
+        if xh.ndim != 3 or xh.shape[0] != n or xh.shape[2] != self.num_classes:
+            raise ValueError("x: [%d, T, %d], got %s" % (n, self.num_classes, xh.shape))
+        T = xh.shape[1]
+        if is_logits:                                          # float32 soft-max on the host: not the device's bits
+            e = np.exp(xh - xh.max(-1, keepdims=True))
+            xh = (e / e.sum(-1, keepdims=True)).astype(np.float32)
+        nc = np.clip(host(n_commit).reshape(-1).astype(np.int64), 0, T)
+        npk = np.zeros(n, np.int64) if n_peek is None else np.minimum(np.clip(host(n_peek).reshape(-1).astype(np.int64), 0, T), T - nc)
+        res = self.carve(np.zeros(self.result_ints(n, n_best, max_len), np.int32), n, n_best, max_len)
+        res["ids"][:] = -1
+        res["scores"][:] = -np.finfo(np.float32).max
+        none = np.zeros((0, self.num_classes), np.float32)
+        for i, s in enumerate(slots):
+            d, c, k = self.decoders[s], int(nc[i]), int(npk[i])
+            if self.committed[s] + c + k > self.max_frames:
+                res["status"][i] = 1
+                hyp = d.decode_ids(none)
+            else:
+                hyp = d.decode_ids(xh[i, :c])
+                self.committed[s] += c
+                if k:
+                    hyp = d.fork().decode_ids(xh[i, c:c + k])
+            res["frames"][i] = self.committed[s]
+            res["n_hyp"][i] = min(len(hyp), n_best)
+            for j, (sc, toks) in enumerate(hyp[:n_best]):
+                res["lens"][i, j] = len(toks)
+                res["scores"][i, j] = sc
+                res["ids"][i, j, :min(len(toks), max_len)] = toks[:max_len]
+        return res
+
+    def read(self, result):
+        """the result of a step as NumPy arrays (one synchronising copy per field unless they share an `out` buffer)"""
+        return {k: (result[k].cpu().numpy() if torch.is_tensor(result[k]) else np.asarray(result[k])) for k in self.FIELDS}
 
 
 def _chunk_block_shapes(p, d, H, hs, k):
@@ -1387,11 +1597,14 @@ class ChunkConformer(_ModelBase):
                                                           0 if tab is None else len(tab), h._stream()))
         state.guard.reset(range(state.n_streams) if tab is None else tab.tolist())
 
-    def stream_step(self, state, slots, packets, n_samples=None, want_logits=False):
+    def stream_step(self, state, slots, packets, n_samples=None, want_logits=False, beam=None):
         """One tick: slot slots[i] takes packets[i] (wav_buf_length samples; a stream's last packet may be shorter: pass a
         list of arrays, or a padded [n, wav_buf_length] array with n_samples).  -> {slot: dict(phone_ids i32 [4], n_picked,
         text_ids i32 [n_valid + n_unvalid], n_valid, n_unvalid)}; with want_logits also phone_logits [4, Vp], text_logits
-        [n_valid + n_unvalid, Vt] and picker_hidden [4, d] (torch, on the device)."""
+        [n_valid + n_unvalid, Vt] and picker_hidden [4, d] (torch, on the device).
+        beam: a `BeamStreams` over the same slots -- its step is enqueued on the text logits behind the decoder, the n_valid
+        final rows as committed frames and (text decoder win_back > 0) the n_unvalid rows as the peek, before the tick's single
+        read-back, which then also brings beam_ids (the best hypothesis), beam_score and beam_status per slot."""
         h = self._h
         dev = h.device
         slots = [int(v) for v in slots]
@@ -1412,7 +1625,12 @@ class ChunkConformer(_ModelBase):
         state.guard.check(slots, lens)
         short = any(k != Wb for k in lens)
         TP, TPd = 4, state.win_back + 4
-        ints = torch.empty(n * (TP + TPd + 3), dtype=torch.int32, device=dev)     # every integer result: one copy back
+        on_dev = beam is not None and not beam.host
+        if beam is not None and (beam.n_streams != state.n_streams or beam.num_classes != self.txt_num_classes):
+            raise ValueError("beam: BeamStreams(%d slots, %d classes) for streams of %d slots and a text head of %d classes"
+                             % (beam.n_streams, beam.num_classes, state.n_streams, self.txt_num_classes))
+        n_beam = BeamStreams.result_ints(n, 1, beam.max_frames) if on_dev else 0
+        ints = torch.empty(n * (TP + TPd + 3) + n_beam, dtype=torch.int32, device=dev)     # every integer result: one copy back
         o = 0
         parts = {}
         for name, k in (("phone_argmax", n * TP), ("n_picked", n), ("text_argmax", n * TPd), ("n_valid", n), ("n_unvalid", n)):
@@ -1421,8 +1639,9 @@ class ChunkConformer(_ModelBase):
         bufs = {}
         if want_logits:
             bufs["phone_logits"] = torch.empty((n, TP, self.phone_num_classes), dtype=torch.float32, device=dev)
-            bufs["text_logits"] = torch.empty((n, TPd, self.txt_num_classes), dtype=torch.float32, device=dev)
             bufs["picker_hidden"] = torch.empty((n, TP, self.dmodel), dtype=torch.float32, device=dev)
+        if want_logits or beam is not None:
+            bufs["text_logits"] = torch.empty((n, TPd, self.txt_num_classes), dtype=torch.float32, device=dev)
         outs = _lib.ChunkStreamsOutputs(**{k: v.data_ptr() for k, v in list(parts.items()) + list(bufs.items())})
         tab = np.asarray(slots, np.int32)
         ns = np.asarray(lens, np.int32)
@@ -1431,10 +1650,22 @@ class ChunkConformer(_ModelBase):
                                                          _p(pk), ns.ctypes.data_as(ctypes.c_void_p) if short else None,
                                                          ctypes.byref(outs), _p(state.ws), state.ws.numel(), h._stream()))
         state.guard.commit(slots, lens)
+        peek = state.win_back > 0             # (win_back 0: no unvalid rows, the committed beam is the result)
+        if on_dev:
+            # rows past n_valid + n_unvalid of text_logits are padding: the search never reads their lists
+            beam.step(slots, bufs["text_logits"], parts["n_valid"], parts["n_unvalid"] if peek else None, is_logits=True, n_best=1,
+                      max_len=beam.max_frames, out=ints[o:])
+        self.stream_readbacks = getattr(self, "stream_readbacks", 0) + 1      # device-to-host copies of stream_step, counted
         r = ints.cpu().numpy()
+        bres = BeamStreams.carve(r[o:], n, 1, beam.max_frames) if on_dev else None
+        r = r[:o]
         pa, npk = r[:n * TP].reshape(n, TP), r[n * TP:n * TP + n]
         ta = r[n * TP + n:n * TP + n + n * TPd].reshape(n, TPd)
         nv, nu = r[-2 * n:-n], r[-n:]
+        if beam is not None and beam.host:    # the explicit host route: the logits come up too (a second copy)
+            self.stream_readbacks += 1
+            bres = beam.step(slots, bufs["text_logits"].cpu().numpy(), nv, nu if peek else None, is_logits=True, n_best=1,
+                             max_len=beam.max_frames)
         out = {}
         for i, slot in enumerate(slots):
             k = int(nv[i] + nu[i])
@@ -1443,6 +1674,10 @@ class ChunkConformer(_ModelBase):
             if want_logits:
                 out[slot].update(phone_logits=bufs["phone_logits"][i], text_logits=bufs["text_logits"][i, :k],
                                  picker_hidden=bufs["picker_hidden"][i])
+            if bres is not None:
+                ln = min(int(bres["lens"][i, 0]), beam.max_frames)
+                out[slot].update(beam_ids=bres["ids"][i, 0, :ln].copy(), beam_score=float(bres["scores"][i, 0]),
+                                 beam_status=int(bres["status"][i]))
         return out
 
     def feature_pick(self, encoder_hidden_states, ctc_outs, max_T=None):
