@@ -300,7 +300,8 @@ int mi355asr_recognize(mi355asr_model* m, const float* wav_dev, int32_t B, int32
  * frame argmax -1; ids are -1 padded as usual.  Workspace: that of [B, L] (mi355asr_workspace_bytes; ctc: ctc_workspace_bytes).
  * Each call reads the lengths back to check them (synchronises `stream` once, at entry).
  * Supported: the Melspectrogram frontend on the FFT STFT (mi355asr_stft_mode 1), chunk_size 0, add_wav_info 0, gemm_dtype 0,
- * dmodel 144, reduction_factor 4, more than 16 encoder frames in a row of L samples (pad L when every utterance is shorter), and
+ * dmodel 144, reduction_factor 4, head_size 36 and kernel_size 32 wherever the model has blocks (recognize_ragged: also
+ * ctcdecoder_kernel_size 32), more than 16 encoder frames in a row of L samples (pad L when every utterance is shorter), and
  * the default kernel switches; anything else returns MI355ASR_EINVAL with a message (mi355asr_last_error), checked before any
  * launch except for kernel switches, which are checked where the block reaches them.
  * ctc_forward_ragged and translator_forward_ragged also take dmodel 256 with 64-dim heads and a ConvModule kernel size of 32, in fp32 and (the CTC decoder) in the

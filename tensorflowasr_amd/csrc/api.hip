@@ -648,6 +648,13 @@ int ragged_config_ok(const mi355asr_model* m) {
                   : !m->fft_ok            ? "the dense DFT STFT (stft_mode 0)"
                                           : nullptr;
   if (why) return fail(MI355ASR_EINVAL, "ragged batches do not support %s", why);
+  // the kernels that apply lengths at dmodel 144: attention_split_kernel (head size 36) and the depthwise conv of 32 taps
+  if (c.num_blocks > 0 && c.head_size != 36)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support head_size %d: the length-aware attention kernels of dmodel 144 are "
+                "instantiated for head_size 36", c.head_size);
+  if (c.num_blocks > 0 && c.kernel_size != 32)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support kernel_size %d: the depthwise conv kernels that apply lengths take "
+                "kernel_size 32", c.kernel_size);
   return 0;
 }
 // the length-aware attention kernels take more than 16 rows per utterance (queries and keys): checked before anything is launched
@@ -693,6 +700,13 @@ static int encoder_call_ok(const mi355asr_model* m, bool need_ctc, bool ptrs_ok,
   if (rc) return rc;
   if (need_ctc && m->cfg.num_classes <= 0) return fail(MI355ASR_ESTATE, "model was created without a CTC head (num_classes=0)");
   if (ragged && (rc = ragged_config_ok(m))) return rc;
+  // ... and the CTC decoder's blocks behind the encoder (recognize): the same two kernels
+  if (ragged && need_ctc && m->cfg.ctc_num_blocks > 0 && m->cfg.head_size != 36)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support head_size %d: the length-aware attention kernels of dmodel 144 are "
+                "instantiated for head_size 36", m->cfg.head_size);
+  if (ragged && need_ctc && m->cfg.ctc_num_blocks > 0 && m->cfg.ctc_kernel_size != 32)
+    return fail(MI355ASR_EINVAL, "ragged batches do not support ctcdecoder_kernel_size %d: the depthwise conv kernels that apply lengths "
+                "take kernel_size 32", m->cfg.ctc_kernel_size);
   if (!ptrs_ok) return fail(MI355ASR_EINVAL, "null device pointer");
   if ((rc = geometry(m, B, L, g))) return rc;
   if (ragged && (rc = ragged_rows_ok(g->T, "T(L)"))) return rc;

@@ -93,6 +93,27 @@ DEV Frag<TERMS> split8(f32x4 lo, f32x4 hi) {
   return f;
 }
 
+// the prologue LayerNorm's two passes over N steps of a row (p = the lane's first value of the first step), all loads first
+template <int N>
+DEV void ln_row_sum(const float* p, float& sm) {
+  f32x4 u[N], v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { u[i] = ldg4(p + 32 * i); v[i] = ldg4(p + 32 * i + 16); }
+#pragma unroll
+  for (int i = 0; i < N; ++i) sm += ((u[i].x + u[i].y) + (u[i].z + u[i].w)) + ((v[i].x + v[i].y) + (v[i].z + v[i].w));
+}
+template <int N>
+DEV void ln_row_sq(const float* p, float mean, float& q) {
+  f32x4 u[N], v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { u[i] = ldg4(p + 32 * i); v[i] = ldg4(p + 32 * i + 16); }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const f32x4 du = u[i] - splat4(mean), dv = v[i] - splat4(mean);
+    q += ((du.x * du.x + du.y * du.y) + (du.z * du.z + du.w * du.w)) + ((dv.x * dv.x + dv.y * dv.y) + (dv.z * dv.z + dv.w * dv.w));
+  }
+}
+
 struct XRegs { f32x4 lo, hi; };                   // one lane's eight operand values of one k-step, before LN / split
 
 template <int EPI, bool LN, int RT, int RING, int TERMS, bool EDMA>
@@ -175,28 +196,17 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
         rstd[rt] = 1.0f / sqrtf(group_sum(q) / (float)a.K + a.eps);
       }
     } else {
+      // K is a multiple of 128, i.e. of four steps: whole groups of eight, then one of four (dmodel 128 / 384)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         float sm = 0.f;
-        for (int st0 = 0; st0 < steps; st0 += 8) {
-          f32x4 u[8], v[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) { u[i] = ldg4(xr[rt] + 32 * (st0 + i)); v[i] = ldg4(xr[rt] + 32 * (st0 + i) + 16); }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) sm += ((u[i].x + u[i].y) + (u[i].z + u[i].w)) + ((v[i].x + v[i].y) + (v[i].z + v[i].w));
-        }
+        int st0 = 0;
+        for (; st0 + 8 <= steps; st0 += 8) ln_row_sum<8>(xr[rt] + 32 * st0, sm);
+        if (st0 < steps) ln_row_sum<4>(xr[rt] + 32 * st0, sm);
         mean[rt] = group_sum(sm) / (float)a.K;
         float q = 0.f;
-        for (int st0 = 0; st0 < steps; st0 += 8) {
-          f32x4 u[8], v[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) { u[i] = ldg4(xr[rt] + 32 * (st0 + i)); v[i] = ldg4(xr[rt] + 32 * (st0 + i) + 16); }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const f32x4 du = u[i] - splat4(mean[rt]), dv = v[i] - splat4(mean[rt]);
-            q += ((du.x * du.x + du.y * du.y) + (du.z * du.z + du.w * du.w)) + ((dv.x * dv.x + dv.y * dv.y) + (dv.z * dv.z + dv.w * dv.w));
-          }
-        }
+        for (st0 = 0; st0 + 8 <= steps; st0 += 8) ln_row_sq<8>(xr[rt] + 32 * st0, mean[rt], q);
+        if (st0 < steps) ln_row_sq<4>(xr[rt] + 32 * st0, mean[rt], q);
         rstd[rt] = 1.0f / sqrtf(group_sum(q) / (float)a.K + a.eps);
       }
     }
