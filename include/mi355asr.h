@@ -95,6 +95,7 @@ int mi355asr_load_weight(mi355asr_model* m, const char* name, const float* data_
 #define MI355ASR_DT_F16 1
 #define MI355ASR_DT_BF16 2
 #define MI355ASR_DT_F64 3
+#define MI355ASR_DT_I16 4   /* mi355asr_resample input only */
 int mi355asr_load_weight_typed(mi355asr_model* m, const char* name, const void* data_host, int32_t dtype, int32_t rank,
                                const int64_t* dims);
 /* number of tensors the configuration expects / name of the i-th one (so loaders can iterate) */
@@ -591,6 +592,42 @@ int mi355asr_vad_enhancer_create(const mi355asr_vad_config* cfg, mi355asr_model*
  * handle from mi355asr_vad_create. */
 int mi355asr_vad_enhance(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
                          float* scores_dev, float* enhanced_dev, void* stream);
+
+/* ---- Polyphase resampling (scipy.signal.resample_poly, default Kaiser filter) ------------------------------------
+ * replaces: the host resampling of utils/speech_featurizers.py read_raw_audio (librosa.load at another rate).
+ * A ratio up / down (sr_out / sr_in in lowest terms, max(up, down) <= 640; anything else is MI355ASR_EINVAL naming it) has
+ * half = 10 max(up, down) and a filter h of 2 half + 1 taps that the CALLER designs (tensorflowasr_amd/resample.py
+ * design_filter) and hands over as a 16-byte aligned fp32 device table in phase-major order:
+ *   table[p * stride + m] = h[p + m * up] for p < up, m < taps, where p + m * up < 2 half + 1; 0 elsewhere,
+ * table_floats floats in all; taps, stride, table_floats and the kernel's output tile come from mi355asr_resample_plan.
+ * Output k of a row of L samples is sum_m table[p][m] x[jh - m] with c = k down + half, p = c mod up, jh = c div up and
+ * x = 0 outside [0, L): one fp32 FMA chain over m = 0 .. taps - 1, the same in every entry point below. */
+int mi355asr_resample_plan(int32_t up, int32_t down, int32_t* taps, int32_t* stride, int32_t* tile, int32_t* table_floats);
+/* x_dev [B, Lpad] of dtype MI355ASR_DT_F32 or MI355ASR_DT_I16 (converted as x / 32768, exact: the same bits as the
+ * float input); in_len_dev i32 [B] samples per row (clamped to [0, Lpad]); y_dev f32 [B, Opad].  Row b gets
+ * ceil(in_len[b] up / down) outputs, computed as if the row were alone; samples at or past in_len[b] are never read;
+ * columns past the row's output length (or all of Opad, if that is smaller) are written as 0.  Asynchronous on `stream`. */
+int mi355asr_resample(const void* x_dev, int32_t dtype, const int32_t* in_len_dev, int32_t B, int64_t Lpad, int32_t up,
+                      int32_t down, const float* filt_dev, float* y_dev, int64_t Opad, void* stream);
+/* Many live streams, one launch per step.  state_dev (state_bytes, caller-owned) holds per slot a ring of
+ * taps - 1 + max_packet samples; a stream's position (samples taken so far, 64-bit) is the CALLER's: pos_host[i] for the
+ * slot slots_host[i].  After N samples a stream has emitted E(N) = max(0, floor((N up - half - 1) / down) + 1) outputs,
+ * those whose taps are all final, so a step over a packet of n_in_host[i] <= max_packet samples (x_dev f32 [n, Ppad])
+ * writes E(N + n_in) - E(N) outputs to row i of y_dev f32 [n, out_cap] and that count to n_out_host[i]; with
+ * flush != 0 (x_dev, n_in_host unused) it writes the rest up to ceil(N up / down), zero-extended, after which the slot
+ * must be reset.  Concatenated, a stream's outputs equal mi355asr_resample of its concatenated input bit for bit.
+ * reset: slots_host NULL = every slot.  A slot out of range or named twice, a packet above max_packet or Ppad, an
+ * out_cap below the one mi355asr_resample_streams_bytes returns, or a workspace below ws_bytes is MI355ASR_EINVAL /
+ * MI355ASR_EWORKSPACE before anything is launched.  No call waits for the device. */
+int mi355asr_resample_streams_bytes(int32_t up, int32_t down, int32_t n_streams, int32_t max_packet, size_t* state_bytes,
+                                    size_t* ws_bytes, int32_t* out_cap);
+int mi355asr_resample_streams_reset(void* state_dev, int32_t up, int32_t down, int32_t n_streams, int32_t max_packet,
+                                    const int32_t* slots_host, int32_t n, void* stream);
+int mi355asr_resample_streams_step(void* state_dev, int32_t up, int32_t down, int32_t n_streams, int32_t max_packet,
+                                   const float* filt_dev, const int32_t* slots_host, const int64_t* pos_host,
+                                   const int32_t* n_in_host, int32_t n, int32_t flush, const float* x_dev, int32_t Ppad,
+                                   float* y_dev, int32_t out_cap, int32_t* n_out_host, void* ws_dev, size_t ws_bytes,
+                                   void* stream);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per

@@ -151,6 +151,11 @@ SIGNATURES = {
     "mi355asr_vad_forward": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "mi355asr_vad_enhancer_create": (ctypes.c_int, [ctypes.POINTER(VadConfig), ctypes.POINTER(_P)]),
     "mi355asr_vad_enhance": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "mi355asr_resample_plan": (ctypes.c_int, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mi355asr_resample": (ctypes.c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _I, _P, _P, ctypes.c_int64, _P]),
+    "mi355asr_resample_streams_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),
+    "mi355asr_resample_streams_reset": (ctypes.c_int, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    "mi355asr_resample_streams_step": (ctypes.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _SZ, _P]),
     "mi355asr_profile_enable": (ctypes.c_int, [_P, _I]),
     "mi355asr_profile_schemes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _I]),
     "mi355asr_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), _I, _I]),

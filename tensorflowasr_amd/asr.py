@@ -151,22 +151,70 @@ class ASR:
         return [(self.phone_featurizer.index_to_token[i], float(a) * period, float(b + 1) * period)
                 for i, (a, b) in zip(ids, spans)]
 
-    def offline_stt_batch(self, items, max_batch_samples=None):
+    def _resampler(self, rate):
+        """the device resampler from `rate` to the model's rate (one per rate, kept)"""
+        from .resample import Resampler
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if rate not in cache:
+            cache[rate] = Resampler(rate, self.speech_config["sample_rate"], device=self.device)
+        return cache[rate]
+
+    def offline_stt_batch(self, items, max_batch_samples=None, sample_rates=None):
         """offline_stt_wave for every item of a list -- paths or 1-D waveforms -- in ragged batches: one encoder, CTC and
         Translator call per batch (mi355asr_*_ragged), each row computed as if alone.  Returns [(phones, text), ...] in the
         order of `items`, what [offline_stt_wave(w) for w in items] returns.  max_batch_samples bounds B x Lmax of a batch
-        (the workspace grows with it); None: one batch.  Offline Melspectrogram encoders of dmodel 144 only."""
+        (the workspace grows with it, counted in samples at the model's rate); None: one batch.  Offline Melspectrogram encoders
+        of dmodel 144 only.
+
+        sample_rates: one rate per item, None for an item that is at the model's rate already (the default for all).  An
+        array item with a rate (float32, or int16 PCM) is resampled on the device from that rate; a path item with a rate is
+        read at the file's own rate (featurizers.read_wav_native), which has to be the stated one, and resampled on the
+        device.  Items of one rate in one batch share one resampler launch (resample.Resampler), and the resampled rows go
+        into the batch's device tensor without passing over the host."""
+        if sample_rates is None:
+            return self._stt_batch([np.asarray(self.speech_featurizer.load_wav(w) if isinstance(w, (str, os.PathLike)) else w,
+                                               np.float32).reshape(-1) for w in items], None, max_batch_samples)
+        from .featurizers import read_wav_native
+        from .resample import ratio
+        if len(sample_rates) != len(items):
+            raise ValueError("%d items, %d sample rates" % (len(items), len(sample_rates)))
+        model_rate = int(self.speech_config["sample_rate"])
+        waves, rates = [], []
+        for w, r in zip(items, sample_rates):
+            r = None if r is None or int(r) == model_rate else int(r)
+            if isinstance(w, (str, os.PathLike)):
+                if r is None:
+                    w = self.speech_featurizer.load_wav(w)
+                else:
+                    path = w
+                    w, file_rate = read_wav_native(path)
+                    if file_rate != r:
+                        raise ValueError("%s is a %d Hz file, sample_rates says %d" % (path, file_rate, r))
+            w = np.asarray(w).reshape(-1)
+            if r is None or w.dtype != np.int16:
+                w = w.astype(np.float32, copy=False)
+            if r is not None:
+                ratio(r, model_rate)                       # an unsupported ratio: before anything runs
+            waves.append(w)
+            rates.append(r)
+        return self._stt_batch(waves, rates, max_batch_samples)
+
+    def _stt_batch(self, waves, rates, max_batch_samples):
+        """offline_stt_batch on 1-D arrays; rates: None, or per item None / the rate it is resampled from on the device"""
         import torch
-        waves = [np.asarray(self.speech_featurizer.load_wav(w) if isinstance(w, (str, os.PathLike)) else w,
-                            np.float32).reshape(-1) for w in items]
+        from .resample import out_length, ratio
         mc, sc = self.model_config, self.speech_config
         # the length-aware attention kernels need more than 16 rows per utterance: pad the batch's L (and U) beyond that
         min_L = 16 * mc["reduction_factor"] * int(sc["stride_ms"] * sc["sample_rate"] // 1000) + 1
         out = [None] * len(waves)
-        order = sorted(range(len(waves)), key=lambda i: len(waves[i]))     # similar lengths together: less padding
+        model_rate = int(sc["sample_rate"])
+        # an item's samples at the model's rate: its length, or the length of its resampled output
+        n16 = [len(w) if rates is None or rates[i] is None else out_length(len(w), *ratio(rates[i], model_rate))
+               for i, w in enumerate(waves)]
+        order = sorted(range(len(waves)), key=lambda i: n16[i])     # similar lengths together: less padding
         batches, cur = [], []
         for i in order:
-            L = max(min_L, max([len(waves[j]) for j in cur] + [len(waves[i])]))
+            L = max(min_L, max([n16[j] for j in cur] + [n16[i]]))
             if cur and max_batch_samples is not None and (len(cur) + 1) * L > max_batch_samples:
                 batches.append(cur)
                 cur = []
@@ -175,10 +223,27 @@ class ASR:
             batches.append(cur)
         blank = self.phone_featurizer.num_classes - 1
         for idx in batches:
-            lens = np.array([len(waves[i]) for i in idx], np.int32)
-            x = np.zeros((len(idx), max(min_L, int(lens.max()))), np.float32)
+            lens = np.array([n16[i] for i in idx], np.int32)
+            W = max(min_L, int(lens.max()))
+            x = np.zeros((len(idx), W), np.float32)
+            groups = {}                                     # rate -> the rows of the batch to resample from it
             for r, i in enumerate(idx):
-                x[r, :lens[r]] = waves[i]
+                if rates is None or rates[i] is None:
+                    x[r, :lens[r]] = waves[i]
+                else:
+                    groups.setdefault(rates[i], []).append(r)
+            if groups:
+                x = torch.from_numpy(x).to(self.device)
+                for rate, rows in sorted(groups.items()):
+                    src = [waves[idx[r]] for r in rows]
+                    n_in = np.array([len(w) for w in src], np.int32)
+                    # int16 PCM goes up as it is (the kernel converts, x / 32768) unless the rate's rows are mixed
+                    pcm = all(w.dtype == np.int16 for w in src)
+                    xin = np.zeros((len(rows), max(1, int(n_in.max()))), np.int16 if pcm else np.float32)
+                    for k, w in enumerate(src):
+                        xin[k, :len(w)] = w if pcm or w.dtype != np.int16 else w.astype(np.float32) / 32768.0
+                    y, _ = self._resampler(rate)(xin, n_in, out_pad=W)       # one launch per distinct rate
+                    x[torch.as_tensor(rows, device=x.device)] = y
             enc, enc_len = self.encoder(x, training=False, lengths=lens)
             _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False, lengths=enc_len)
             ids, tok = ctc_greedy_decode(frame_ids, enc_len, blank=blank)

@@ -242,9 +242,14 @@ class ChunkStreamingServer:
     the reference's unvalid part is zeros_like(valid logits): rows that only ever add id 0 to a greedy text, where it is dropped.
     They are not fed to the search: the text is the committed beam's best.  A stream that outgrows `max_text_frames` gets a
     `BeamStateOverflow` in the place of its tuple -- returned, not raised, as `StreamingASRServer` does for its history, so
-    that the other streams go on; `open()` resets a slot's beam with the rest of its state."""
+    that the other streams go on; `open()` resets a slot's beam with the rest of its state.
 
-    def __init__(self, chunk_asr, n_streams, stepper=None, beam_width=1, ext_scorer=None, max_text_frames=1500, beam_host=False):
+    `input_rate` (e.g. 8000): `send` takes samples at that rate and resamples them to the model's on the device, one
+    `resample.StreamResampler` step per call for all streams named in it; the tuples are those of a server fed
+    the one-shot resampling of each stream's audio."""
+
+    def __init__(self, chunk_asr, n_streams, stepper=None, beam_width=1, ext_scorer=None, max_text_frames=1500, beam_host=False,
+                 input_rate=None, max_input_packet=None):
         from .models import StreamGuard
         self.asr = chunk_asr
         self.stepper = stepper if stepper is not None else chunk_asr.runner
@@ -263,6 +268,16 @@ class ChunkStreamingServer:
                                     max_frames=int(max_text_frames), host=bool(beam_host), **kw)
         elif ext_scorer is not None:
             raise ValueError("ext_scorer needs beam_width > 1: the greedy text has no use for a scorer")
+        # callers at another rate: one StreamResampler slot per stream slot, stepped once per send for every stream named in it
+        self.resampler = None
+        model_rate = int(chunk_asr.speech_featurizer.sample_rate)
+        if input_rate is not None and int(input_rate) != model_rate:
+            from .resample import StreamResampler
+            self.input_rate = int(input_rate)
+            # the longest piece one step takes (longer ones are cut): one second of input unless told otherwise
+            self.max_input_packet = int(max_input_packet or self.input_rate)
+            dev = getattr(getattr(self.stepper, "_h", None), "device", None) or getattr(chunk_asr, "device", "cuda:0")
+            self.resampler = StreamResampler(self.n_streams, self.input_rate, model_rate, self.max_input_packet, device=dev)
 
     def open(self):
         if not self.free:
@@ -272,6 +287,8 @@ class ChunkStreamingServer:
         self.guard.reset([slot])
         if self.beam is not None:
             self.beam.reset([slot])
+        if self.resampler is not None:
+            self.resampler.reset([slot])
         self.streams[slot] = _Stream(self.asr.phone_featurizer.num_classes - 1, self.asr.text_featurizer.num_classes - 1)
         return slot
 
@@ -325,8 +342,12 @@ class ChunkStreamingServer:
         return out
 
     def send(self, audio):
-        """{slot: float samples of any length} -> {slot: [(seconds_heard, phones, text), ...]}"""
+        """{slot: float samples of any length} -> {slot: [(seconds_heard, phones, text), ...]}.  The samples are at the model's
+        rate, or at the server's `input_rate`: then everything that arrived in this call goes through ONE resampler step for all
+        its slots (a piece above max_input_packet: one step per max_input_packet samples) and what that emits joins the buffers."""
         out = {}
+        if self.resampler is not None:
+            audio = self._resampled(audio)
         for s, x in audio.items():
             st = self._stream(s)
             st.buf = np.concatenate([st.buf, np.asarray(x, np.float32).reshape(-1)])
@@ -343,11 +364,37 @@ class ChunkStreamingServer:
                     out.setdefault(s, []).append(t)
         return out
 
+    def _resampled(self, audio):
+        """{slot: samples at input_rate} -> {slot: the samples at the model's rate that became final}"""
+        rows = {s: np.asarray(x, np.float32).reshape(-1) for s, x in audio.items()}
+        for s in rows:
+            self._stream(s)
+        out = {s: [] for s in rows}
+        M, off = self.max_input_packet, 0
+        while True:
+            part = {s: x[off:off + M] for s, x in rows.items() if len(x) > off}
+            if not part:
+                break
+            slots = sorted(part)
+            for s, y in self.resampler.step(slots, [part[s] for s in slots]).items():
+                out[s].append(y)
+            off += M
+        return {s: np.concatenate(v) if v else np.zeros(0, np.float32) for s, v in out.items()}
+
     def close(self, slot):
-        """the buffered tail as the stream's short last packet -> its tuples; the slot is free afterwards."""
+        """the buffered tail as the stream's short last packet -> its tuples; the slot is free afterwards.  With an input_rate
+        the slot's resampler is flushed first: the outputs that waited for samples after the stream's end."""
         st = self._stream(slot)
         try:
             out = []
+            if self.resampler is not None:
+                st.buf = np.concatenate([st.buf, self.resampler.flush([slot])[slot]])
+                W = self.wav_buf_length
+                while len(st.buf) >= W:                  # the flush can complete a packet
+                    pkt, st.buf = st.buf[:W], st.buf[W:]
+                    t = self.tick({slot: pkt})[slot]
+                    if t is not None:
+                        out.append(t)
             if len(st.buf):
                 t = self.tick({slot: st.buf})[slot]
                 if t is not None:

@@ -53,6 +53,21 @@ def read_raw_audio(audio, sample_rate=16000):
     return x
 
 
+def read_wav_native(audio):
+    """path | bytes -> (float32 mono in [-1, 1) at the FILE's rate, that rate): read_raw_audio's reading without its host
+    resampling, for callers that resample on the device (resample.Resampler)."""
+    if isinstance(audio, (str, os.PathLike)):
+        f = wave.open(os.path.expanduser(str(audio)), "rb")
+    elif isinstance(audio, bytes):
+        f = wave.open(io.BytesIO(audio), "rb")
+    else:
+        raise ValueError("input audio must be either a path or bytes")
+    with f:
+        sr, nch, sw = f.getframerate(), f.getnchannels(), f.getsampwidth()
+        x = _pcm_to_float(f.readframes(f.getnframes()), sw, nch)
+    return x, sr
+
+
 def normalize_signal(signal):
     """utils/speech_featurizers.py:34-37."""
     return signal * (1.0 / (np.max(np.abs(signal)) + 1e-9))

@@ -24,11 +24,30 @@ class ASRSession:
         self.offline_vad = OfflineVAD(sr=sample_rate)
         self.offline_vad.compile(vad)
 
-    def send(self, wav_path):
+    def send(self, wav_path, sample_rate=None):
         """wav path or 1-D array -> [{session, sentence_index, sentence_begin_time, best_text, sentence_end_time}],
         times in integer ms.  Like the reference, every dict carries session 'asr_1'.  Also sets `self.phones`, the
-        phone string behind each best_text."""
-        wav = read_raw_audio(wav_path, self.sample_rate) if not isinstance(wav_path, np.ndarray) else wav_path
+        phone string behind each best_text.
+
+        sample_rate: the rate of the recording when it is not the session's.  The recording (an array, float32 or int16 PCM,
+        or a file of that rate) is resampled on the device first (resample.Resampler) and then handled as one at the
+        session's rate: the times are those of the resampled recording, which spans the same milliseconds."""
+        if sample_rate is not None and int(sample_rate) != int(self.sample_rate):
+            from .featurizers import read_wav_native
+            from .resample import Resampler
+            wav = wav_path
+            if not isinstance(wav, np.ndarray):
+                wav, file_rate = read_wav_native(wav)
+                if file_rate != int(sample_rate):
+                    raise ValueError("%s is a %d Hz file, sample_rate says %d" % (wav_path, file_rate, int(sample_rate)))
+            wav = wav.reshape(-1)
+            cache = self.__dict__.setdefault("_resamplers", {})
+            if int(sample_rate) not in cache:
+                cache[int(sample_rate)] = Resampler(int(sample_rate), self.sample_rate, device=getattr(self.asr, "device", "cuda:0"))
+            y, _ = cache[int(sample_rate)](wav if wav.dtype == np.int16 else wav.astype(np.float32, copy=False))
+            wav = y[0].cpu().numpy() if len(wav) else np.zeros(0, np.float32)
+        else:
+            wav = read_raw_audio(wav_path, self.sample_rate) if not isinstance(wav_path, np.ndarray) else wav_path
         wav = np.asarray(wav, np.float32).reshape(-1)
         wav = wav[:len(wav) // 80 * 80]
         responses, self.phones = [], []
