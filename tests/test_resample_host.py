@@ -96,3 +96,22 @@ def test_plan_and_stream_sizes_of_the_library():
     assert lib.mi355asr_resample_plan(641, 1, None, None, None, None) == -1
     assert b"641/1" in lib.mi355asr_last_error()
     assert lib.mi355asr_resample_plan(1, 0, None, None, None, None) == -1
+
+
+def test_restated_plan_equals_the_library_and_names_the_staging_boundary():
+    """resample_ref.plan (what the GPU tests print and size their inputs by) against mi355asr_resample_plan, and the LDS figures at
+    the ratios chosen for them: 1/18 is staged with 80 720 of 81 920 bytes, 1/19 is not; 147/640 is staged with 77 920"""
+    import ctypes
+    from resample_ref import LARGE_K, MORE_RATIOS, SMALL_K, filter_gap, plan
+    from tensorflowasr_amd import _lib
+    lib = _lib.lib()
+    for up, down in sorted(set(RATIOS + MORE_RATIOS + SMALL_K + LARGE_K)):
+        v = [ctypes.c_int32() for _ in range(4)]
+        assert lib.mi355asr_resample_plan(up, down, *[ctypes.byref(c) for c in v]) == 0
+        p = plan(up, down)
+        assert [c.value for c in v] == [p["taps"], p["stride"], p["tile"], p["table_floats"]], (up, down)
+        assert filter_gap(up, down) <= 1e-12
+    assert (plan(1, 18)["staged"], plan(1, 18)["lds"]) == (True, 80720) and not plan(1, 19)["staged"]
+    assert (plan(147, 640)["staged"], plan(147, 640)["lds"]) == (True, 77920)
+    assert [plan(u, d)["staged"] for u, d in ((3, 61), (101, 640), (1, 640), (640, 1), (640, 441))] == [False, False, False, True, True]
+    assert plan(640, 441)["lds"] > 64 * 1024 > plan(640, 1)["lds"]

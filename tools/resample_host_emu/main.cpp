@@ -1,5 +1,6 @@
 // Driver of the host emulation of csrc/resample.hip: `oneshot` runs mi355asr_resample on files of raw arrays, `stream` feeds one slot
-// of mi355asr_resample_streams_* packet by packet and flushes it.  RESAMPLE_SOURCE is the kernel file with its include of model.h
+// of mi355asr_resample_streams_* packet by packet and flushes it, from position 0 or from the position given after the output file
+// (a fresh slot placed there: what lies before it is zero).  RESAMPLE_SOURCE is the kernel file with its include of model.h
 // replaced by shim.h and its LDS declaration by the emulation's block (the test makes that copy).
 #include RESAMPLE_SOURCE
 #include <string>
@@ -33,15 +34,16 @@ int main(int argc, char** argv) {
     if (mi355asr_resample_streams_bytes(up, down, nstreams, max_packet, &stb, &wsb, &oc)) { fprintf(stderr, "%s\n", g_err); return 2; }
     char* st = (char*)malloc(stb); memset(st, 0xff, stb); char* ws = (char*)malloc(wsb);
     if (mi355asr_resample_streams_reset(st, up, down, nstreams, max_packet, &slot, 1, nullptr)) return 2;
-    std::vector<float> out; int64_t pos = 0; float* y = (float*)malloc((size_t)oc * 4);
+    const int64_t start = argc > 9 ? atoll(argv[9]) : 0;
+    std::vector<float> out; int64_t pos = start; float* y = (float*)malloc((size_t)oc * 4);
     for (int i = 0; i <= ns; ++i) {
       int flush = i == ns; int32_t P = flush ? 0 : sizes[i], n_out = 0;
-      float* pk = (float*)malloc(std::max(P, 1) * 4); if (P) memcpy(pk, x + pos, P * 4);
+      float* pk = (float*)malloc(std::max(P, 1) * 4); if (P) memcpy(pk, x + (pos - start), P * 4);
       int rc = mi355asr_resample_streams_step(st, up, down, nstreams, max_packet, filt, &slot, &pos, &P, 1, flush, flush ? nullptr : pk, std::max(P, 1), y, oc, &n_out, ws, wsb, nullptr);
       if (rc) { fprintf(stderr, "rc %d %s\n", rc, g_err); return 2; }
       out.insert(out.end(), y, y + n_out); pos += P; free(pk);
     }
-    if (pos != total) return 3;
+    if (pos - start != total) return 3;
     wr(argv[8], out.data(), out.size() * 4);
     free(st); free(ws); free(y);
   }
