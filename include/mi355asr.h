@@ -14,8 +14,22 @@
  *     host pointers are marked `_host`
  *   - `stream` is a hipStream_t passed as void* (0 = default stream); all work is enqueued
  *     asynchronously on it; nothing synchronises the device
+ *   - nothing is enqueued on any stream but `stream` -- no launch, no copy, no memset -- so a call made on a stream that
+ *     does not synchronise with the null stream sees its inputs as that stream left them (an entry that names a
+ *     synchronisation below waits for `stream` alone)
+ *   - a workspace (`ws_dev`, `ws_bytes` from the matching *_workspace_bytes) may hold anything on entry: no call reads a
+ *     workspace word it has not written itself; on exit its contents are unspecified.  No byte outside
+ *     [ws_dev, ws_dev + ws_bytes), the output tensors and, for the stateful families, the state buffer is written
+ *   - an opaque state buffer (chunk streams, beam streams, resample streams) needs nothing but its `reset`, whatever it held
+ *     before: rings and arenas are never read past their counters
+ *   - an output is written in full, padding included (0, -1 or -FLT_MAX as its entry says), except where an entry says that
+ *     a region is not written: mi355asr_vad_forward / mi355asr_vad_enhance past a row's frame count, the capacity of the
+ *     mi355asr_chunk_outputs buffers behind their [B, Tp] blocks, and y_dev of mi355asr_resample_streams_step past
+ *     n_out_host[i]
+ *     (tests/test_gpu_caller_contract.py holds every entry point to these points on poisoned, fenced buffers)
  *   - a handle is not re-entrant: one in-flight call per handle (the reference's C++ Session has the
- *     same contract, asr_session.h keeps mutable buffers); distinct handles are independent
+ *     same contract, asr_session.h keeps mutable buffers); distinct handles are independent: they may be in flight at the
+ *     same time on different streams, from one thread or from several
  *   - values and accumulation are fp32 everywhere, matching the reference's dtype.  Products are formed by the fp32 matrix
  *     instruction (v_mfma_f32_16x16x4_f32, an exact fp32 FMA chain) or, in the large dmodel-144 kernels, on the 16-bit
  *     matrix pipe from SPLIT fp32 operands: three bf16 terms each, exact (six v_mfma_f32_16x16x32_bf16 per product group,
@@ -368,7 +382,8 @@ typedef struct {
 } mi355asr_chunk_config;
 
 /* optional DEVICE outputs of mi355asr_chunk_predict (NULL = not wanted).  Frame-major fp32 unless noted;
- * T = encoder frames of the utterances, Tp = max over the batch of picked frames (returned on the host). */
+ * T = encoder frames of the utterances, Tp = max over the batch of picked frames (returned on the host).  The four buffers
+ * with a capacity receive a dense [B, Tp, ...] block at their start; the rest of the capacity is not written. */
 typedef struct {
   float*   front_out;       /* [B, T, d]                    ChunkConformerFront.call                      */
   float*   enc_out;         /* [B, T, d]                    ChunkConformerEncoder.call                    */
@@ -613,7 +628,8 @@ int mi355asr_resample(const void* x_dev, int32_t dtype, const int32_t* in_len_de
  * taps - 1 + max_packet samples; a stream's position (samples taken so far, 64-bit) is the CALLER's: pos_host[i] for the
  * slot slots_host[i].  After N samples a stream has emitted E(N) = max(0, floor((N up - half - 1) / down) + 1) outputs,
  * those whose taps are all final, so a step over a packet of n_in_host[i] <= max_packet samples (x_dev f32 [n, Ppad])
- * writes E(N + n_in) - E(N) outputs to row i of y_dev f32 [n, out_cap] and that count to n_out_host[i]; with
+ * writes E(N + n_in) - E(N) outputs to row i of y_dev f32 [n, out_cap] (the rest of the row is not written) and that
+ * count to n_out_host[i]; with
  * flush != 0 (x_dev, n_in_host unused) it writes the rest up to ceil(N up / down), zero-extended, after which the slot
  * must be reset.  Concatenated, a stream's outputs equal mi355asr_resample of its concatenated input bit for bit.
  * reset: slots_host NULL = every slot.  A slot out of range or named twice, a packet above max_packet or Ppad, an

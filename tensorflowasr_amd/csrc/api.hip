@@ -62,6 +62,8 @@ Plan make_plan(const mi355asr_model* m, int Bp, int F, int T) {
   Layout lay;
   auto take = [&](size_t floats) { return lay.take(floats); };
   lay.scratch(p, M, d);
+  // (h4 = 0 aliases xa: safe only because every stack of this plan runs on exactly M rows, so the layer-at-a-time launches run
+  // for all of them or for none -- a stage on fewer rows must plan h4 itself, as make_chunk_plan does)
   p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;   // before logp: the block-only entry points size to p.logp
   p.enc = take(M * d);
   p.amax = take(M);

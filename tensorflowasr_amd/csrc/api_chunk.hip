@@ -36,7 +36,10 @@ ChunkPlan make_chunk_plan(const mi355asr_model* m, int B, int F, int T) {
   p.pmax = take((size_t)B * std::max(FT * m->dm.NCH_dft, F));
   p.mel = take((size_t)B * F * m->cfg.n_mels);
   p.sub = take(M * m->dm.F2 * d);
-  p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;
+  // the stacks behind feature_pick run on B * Tp <= M rows: with few picks they take the layer-at-a-time launches (up to
+  // MI355ASR_SMALL_M rows), which need the FFN hidden buffer, whatever M is -- without it h4 would alias xa
+  const size_t layer_rows = gemm16_for(m, M) ? M : std::min(M, (size_t)std::max(block_switches().small_m, 0L));
+  p.h4 = layer_rows ? take(layer_rows * 4 * d) : 0;
   p.total = lay.o;
   return p;
 }
@@ -432,7 +435,7 @@ int mi355asr_frame_argmax(const float* x, int32_t M, int32_t V, int32_t* out, vo
 // ---- feature_pick as its own entry point (the streaming path calls it between picker and decoder) --------------------
 int mi355asr_feature_pick_count(const float* ctc, int32_t B, int32_t T, int32_t V, int32_t* idx, int32_t* cnt,
                                 int32_t* counts_host, void* stream) {
-  if (!ctc || !idx || !cnt || !counts_host) return fail(MI355ASR_EINVAL, "null argument");
+  if ((!ctc && T != 0) || !idx || !cnt || !counts_host) return fail(MI355ASR_EINVAL, "null argument");   // (no frames: nothing to point at)
   if (B < 1 || T < 0 || V < 2) return fail(MI355ASR_EINVAL, "need B >= 1, T >= 0, V >= 2 (got %d, %d, %d)", B, T, V);
   hipStream_t s = (hipStream_t)stream;
   if (T == 0) {

@@ -17,7 +17,7 @@ TransPlan make_trans_plan(const mi355asr_model* m, int B, int U, int T) {
   auto take = [&](size_t floats) { return lay.take(floats); };
   lay.scratch(p, M, d);
   p.kv = take((size_t)B * T * 2 * d); p.amax = take(M);
-  p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;
+  p.h4 = gemm16_for(m, M) ? take(M * 4 * d) : 0;   // (every RBlock runs on exactly M = B * U rows: see make_plan in api.hip)
   p.hsplit = take(16 * M);          // per-range (maximum, class) pairs of the class head split over column ranges (up to 8)
   p.total = lay.o;
   return p;

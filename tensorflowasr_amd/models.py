@@ -536,11 +536,11 @@ class CTCDecoder(_ModelBase):
         B, T, _ = x.shape
         if not return_logits and not return_argmax:
             raise ValueError("nothing to return: return_logits=False needs return_argmax=True")
-        logits = torch.empty((B, T, self.num_classes), dtype=torch.float32, device=h.device) if return_logits else None
-        amax = torch.empty((B, T), dtype=torch.int32, device=h.device)
         if lengths is not None:
             logits, amax = _ctc_ragged(h, x, lengths, self.num_classes, return_logits)
             return (logits, amax) if return_argmax else logits
+        logits = torch.empty((B, T, self.num_classes), dtype=torch.float32, device=h.device) if return_logits else None
+        amax = torch.empty((B, T), dtype=torch.int32, device=h.device)
         ws, n = h.ws_for_frames(B, T)
         with torch.cuda.device(h.device):
             _lib.check(h.lib.mi355asr_ctc_forward(h.ptr, _p(x), B, T, _p(logits) if return_logits else None, _p(amax), _p(ws), n, h._stream()))

@@ -204,7 +204,7 @@ class StreamResampler(_Base):
         pos = np.ascontiguousarray([self.pos[s] for s in slots], np.int64)
         nin = np.ascontiguousarray(lens, np.int32)
         n_out = np.zeros(n, np.int32)
-        y = torch.empty((n, self.out_cap), dtype=torch.float32, device=self.device)
+        y = torch.zeros((n, self.out_cap), dtype=torch.float32, device=self.device)      # (a step writes n_out[i] samples of row i)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.mi355asr_resample_streams_step(
                 _ptr(self.state), self.up, self.down, self.n_streams, self.max_packet, _ptr(self.table),
@@ -215,7 +215,7 @@ class StreamResampler(_Base):
 
     def step_device(self, slots, packets, lengths=None):
         """-> (y [n, out_cap] float32 on the device, counts int32 [n] on the host); row i holds slot slots[i]'s counts[i] new
-        samples.  packets: one 1-D array or tensor per slot, or one float32 tensor [n, P] on the device with `lengths` samples
+        samples, zeros behind them.  packets: one 1-D array or tensor per slot, or one float32 tensor [n, P] on the device with `lengths` samples
         per row (None: P each), which is used as it is.  Nothing is waited for."""
         import torch
         slots = self._check(slots)
