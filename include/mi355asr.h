@@ -406,6 +406,19 @@ int mi355asr_chunk_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t L
 int mi355asr_chunk_predict(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L,
                            const mi355asr_chunk_outputs* outs, int32_t* n_picked_host, int32_t* t_pick_host,
                            void* ws_dev, size_t ws_bytes, void* stream);
+/* Ragged ChunkConformer batches: utterance b is wav_dev[b, :wav_len_dev[b]] (i32 [B] on the device,
+ * 2 hop + 1 <= wav_len[b] <= L; what lies behind it in the row is never read into a result -- it may hold anything).  Row b of
+ * every output equals the call on that utterance alone: the band attention of every stack takes the utterance's own length
+ * (T_b = chunk_out_frames(wav_len[b]) for encoder and picker, its pick count for helper and decoder), frames past T_b are never
+ * picked, and n_picked_host[b] is the valid length of its text logits.  Rows past T_b of front_out / enc_out / picker_logits /
+ * picker_hidden and rows past n_picked[b] of picked / helper_out / text_logits are 0, text_argmax is -1 there.  The lengths
+ * are read back at entry (one more synchronisation of `stream`).  EINVAL, before anything is launched: a length outside
+ * its range (the message names the row), a null wav_len_dev, a handle that is not a ChunkConformer, bf16 GEMM mode.
+ * Workspace: mi355asr_chunk_workspace_bytes_ragged(B, L). */
+int mi355asr_chunk_workspace_bytes_ragged(const mi355asr_model* m, int32_t B, int32_t L, size_t* bytes);
+int mi355asr_chunk_predict_ragged(mi355asr_model* m, const float* wav_dev, const int32_t* wav_len_dev, int32_t B, int32_t L,
+                                  const mi355asr_chunk_outputs* outs, int32_t* n_picked_host, int32_t* t_pick_host,
+                                  void* ws_dev, size_t ws_bytes, void* stream);
 
 /* per-frame argmax of given logits or probabilities, f32 [M, V] -> i32 [M], first maximum wins: the decision step of
  * tf.keras.backend.ctc_decode(greedy) when the logits come from outside a head kernel (the streaming ChunkConformer path

@@ -21,6 +21,85 @@ from .featurizers import SpeechFeaturizer, TextFeaturizer
 from .models import ConformerEncoder, CTCDecoder, StreamingConformerEncoder, Translator, ctc_forced_align, ctc_greedy_decode
 
 
+def batch_items(items, sample_rates, load_wav, model_rate):
+    """The items of an offline_stt_batch call (paths or 1-D waveforms) as 1-D arrays, and their rates: None (all at the model's
+    rate), or per item None / the rate it will be resampled from on the device.  A path with a rate is read at the file's
+    own rate, which has to be the stated one; an unsupported ratio is refused here, before anything runs."""
+    if sample_rates is None:
+        return [np.asarray(load_wav(w) if isinstance(w, (str, os.PathLike)) else w, np.float32).reshape(-1) for w in items], None
+    from .featurizers import read_wav_native
+    from .resample import ratio
+    if len(sample_rates) != len(items):
+        raise ValueError("%d items, %d sample rates" % (len(items), len(sample_rates)))
+    waves, rates = [], []
+    for w, r in zip(items, sample_rates):
+        r = None if r is None or int(r) == model_rate else int(r)
+        if isinstance(w, (str, os.PathLike)):
+            if r is None:
+                w = load_wav(w)
+            else:
+                path = w
+                w, file_rate = read_wav_native(path)
+                if file_rate != r:
+                    raise ValueError("%s is a %d Hz file, sample_rates says %d" % (path, file_rate, r))
+        w = np.asarray(w).reshape(-1)
+        if r is None or w.dtype != np.int16:
+            w = w.astype(np.float32, copy=False)
+        if r is not None:
+            ratio(r, model_rate)                       # an unsupported ratio: before anything runs
+        waves.append(w)
+        rates.append(r)
+    return waves, rates
+
+
+def cut_batches(waves, rates, model_rate, max_batch_samples, min_L=0):
+    """Ragged batches of a list of waveforms: sorted by length (similar lengths together: less padding) and cut so that no
+    batch holds more than max_batch_samples padded samples (B x its longest row, at least min_L; None: one batch).
+    -> (n16: every item's samples at the model's rate -- its length, or the length of its resampled output; the batches as
+    lists of item indices)"""
+    from .resample import out_length, ratio
+    n16 = [len(w) if rates is None or rates[i] is None else out_length(len(w), *ratio(rates[i], model_rate))
+           for i, w in enumerate(waves)]
+    order = sorted(range(len(waves)), key=lambda i: n16[i])
+    batches, cur = [], []
+    for i in order:
+        L = max(min_L, max([n16[j] for j in cur] + [n16[i]]))
+        if cur and max_batch_samples is not None and (len(cur) + 1) * L > max_batch_samples:
+            batches.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        batches.append(cur)
+    return n16, batches
+
+
+def batch_rows(waves, rates, idx, lens, W, resampler_for, device):
+    """The [len(idx), W] batch of the items idx, zero padded: a host array when every row is at the model's rate, else a device
+    tensor whose rows with a rate were resampled there -- one launch of resampler_for(rate) per distinct rate, the rows going
+    into the tensor without passing over the host."""
+    import torch
+    x = np.zeros((len(idx), W), np.float32)
+    groups = {}                                     # rate -> the rows of the batch to resample from it
+    for r, i in enumerate(idx):
+        if rates is None or rates[i] is None:
+            x[r, :lens[r]] = waves[i]
+        else:
+            groups.setdefault(rates[i], []).append(r)
+    if groups:
+        x = torch.from_numpy(x).to(device)
+        for rate, rows in sorted(groups.items()):
+            src = [waves[idx[r]] for r in rows]
+            n_in = np.array([len(w) for w in src], np.int32)
+            # int16 PCM goes up as it is (the kernel converts, x / 32768) unless the rate's rows are mixed
+            pcm = all(w.dtype == np.int16 for w in src)
+            xin = np.zeros((len(rows), max(1, int(n_in.max()))), np.int16 if pcm else np.float32)
+            for k, w in enumerate(src):
+                xin[k, :len(w)] = w if pcm or w.dtype != np.int16 else w.astype(np.float32) / 32768.0
+            y, _ = resampler_for(rate)(xin, n_in, out_pad=W)       # one launch per distinct rate
+            x[torch.as_tensor(rows, device=x.device)] = y
+    return x
+
+
 class ASR:
     def __init__(self, config, device="cuda:0", load_checkpoint=True, verbose=False):
         self.running_config = config["running_config"]
@@ -171,79 +250,21 @@ class ASR:
         read at the file's own rate (featurizers.read_wav_native), which has to be the stated one, and resampled on the
         device.  Items of one rate in one batch share one resampler launch (resample.Resampler), and the resampled rows go
         into the batch's device tensor without passing over the host."""
-        if sample_rates is None:
-            return self._stt_batch([np.asarray(self.speech_featurizer.load_wav(w) if isinstance(w, (str, os.PathLike)) else w,
-                                               np.float32).reshape(-1) for w in items], None, max_batch_samples)
-        from .featurizers import read_wav_native
-        from .resample import ratio
-        if len(sample_rates) != len(items):
-            raise ValueError("%d items, %d sample rates" % (len(items), len(sample_rates)))
-        model_rate = int(self.speech_config["sample_rate"])
-        waves, rates = [], []
-        for w, r in zip(items, sample_rates):
-            r = None if r is None or int(r) == model_rate else int(r)
-            if isinstance(w, (str, os.PathLike)):
-                if r is None:
-                    w = self.speech_featurizer.load_wav(w)
-                else:
-                    path = w
-                    w, file_rate = read_wav_native(path)
-                    if file_rate != r:
-                        raise ValueError("%s is a %d Hz file, sample_rates says %d" % (path, file_rate, r))
-            w = np.asarray(w).reshape(-1)
-            if r is None or w.dtype != np.int16:
-                w = w.astype(np.float32, copy=False)
-            if r is not None:
-                ratio(r, model_rate)                       # an unsupported ratio: before anything runs
-            waves.append(w)
-            rates.append(r)
+        waves, rates = batch_items(items, sample_rates, self.speech_featurizer.load_wav, int(self.speech_config["sample_rate"]))
         return self._stt_batch(waves, rates, max_batch_samples)
 
     def _stt_batch(self, waves, rates, max_batch_samples):
         """offline_stt_batch on 1-D arrays; rates: None, or per item None / the rate it is resampled from on the device"""
         import torch
-        from .resample import out_length, ratio
         mc, sc = self.model_config, self.speech_config
         # the length-aware attention kernels need more than 16 rows per utterance: pad the batch's L (and U) beyond that
         min_L = 16 * mc["reduction_factor"] * int(sc["stride_ms"] * sc["sample_rate"] // 1000) + 1
         out = [None] * len(waves)
-        model_rate = int(sc["sample_rate"])
-        # an item's samples at the model's rate: its length, or the length of its resampled output
-        n16 = [len(w) if rates is None or rates[i] is None else out_length(len(w), *ratio(rates[i], model_rate))
-               for i, w in enumerate(waves)]
-        order = sorted(range(len(waves)), key=lambda i: n16[i])     # similar lengths together: less padding
-        batches, cur = [], []
-        for i in order:
-            L = max(min_L, max([n16[j] for j in cur] + [n16[i]]))
-            if cur and max_batch_samples is not None and (len(cur) + 1) * L > max_batch_samples:
-                batches.append(cur)
-                cur = []
-            cur.append(i)
-        if cur:
-            batches.append(cur)
+        n16, batches = cut_batches(waves, rates, int(sc["sample_rate"]), max_batch_samples, min_L)
         blank = self.phone_featurizer.num_classes - 1
         for idx in batches:
             lens = np.array([n16[i] for i in idx], np.int32)
-            W = max(min_L, int(lens.max()))
-            x = np.zeros((len(idx), W), np.float32)
-            groups = {}                                     # rate -> the rows of the batch to resample from it
-            for r, i in enumerate(idx):
-                if rates is None or rates[i] is None:
-                    x[r, :lens[r]] = waves[i]
-                else:
-                    groups.setdefault(rates[i], []).append(r)
-            if groups:
-                x = torch.from_numpy(x).to(self.device)
-                for rate, rows in sorted(groups.items()):
-                    src = [waves[idx[r]] for r in rows]
-                    n_in = np.array([len(w) for w in src], np.int32)
-                    # int16 PCM goes up as it is (the kernel converts, x / 32768) unless the rate's rows are mixed
-                    pcm = all(w.dtype == np.int16 for w in src)
-                    xin = np.zeros((len(rows), max(1, int(n_in.max()))), np.int16 if pcm else np.float32)
-                    for k, w in enumerate(src):
-                        xin[k, :len(w)] = w if pcm or w.dtype != np.int16 else w.astype(np.float32) / 32768.0
-                    y, _ = self._resampler(rate)(xin, n_in, out_pad=W)       # one launch per distinct rate
-                    x[torch.as_tensor(rows, device=x.device)] = y
+            x = batch_rows(waves, rates, idx, lens, max(min_L, int(lens.max())), self._resampler, self.device)
             enc, enc_len = self.encoder(x, training=False, lengths=lens)
             _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False, lengths=enc_len)
             ids, tok = ctc_greedy_decode(frame_ids, enc_len, blank=blank)

@@ -81,6 +81,62 @@ class ChunkASR:
         ids, lens, _, _ = ctc_prefix_beam_decode(logits, None, beam, is_logits=True, ext_scorer=self.text_featurizer.scorer)
         return [int(n) for n in ids[0, 0, :int(lens[0, 0])] if n != 0]
 
+    def _resampler(self, rate):
+        """the device resampler from `rate` to the model's rate (one per rate, kept)"""
+        from .resample import Resampler
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if rate not in cache:
+            cache[rate] = Resampler(rate, self.speech_featurizer.sample_rate, device=self.device)
+        return cache[rate]
+
+    def _batch_ids(self, logits, counts):
+        """the text ids of every row of a ragged batch's text logits [B, Tp, V], row b over its first counts[b] frames:
+        greedy (frame_argmax + ctc_greedy_decode), or with `beam_width` > 1 in the text vocabulary's config the prefix beam
+        search with the vocabulary's scorer -> B id lists without zeros, as _ctc_text / _beam_text return for one row"""
+        B = logits.shape[0]
+        if logits.shape[1] == 0:
+            return [[] for _ in range(B)]
+        in_len = torch.as_tensor(np.asarray(counts, np.int32), device=logits.device)
+        beam = int(self.text_featurizer.decoder_config.get("beam_width", 1) or 1)
+        if beam > 1:
+            from .models import ctc_prefix_beam_decode
+            ids, lens, _, _ = ctc_prefix_beam_decode(logits, in_len, beam, is_logits=True, ext_scorer=self.text_featurizer.scorer)
+            return [[int(n) for n in ids[b, 0, :int(lens[b, 0])] if n != 0] for b in range(B)]
+        ids, lens = ctc_greedy_decode(frame_argmax(logits), in_len, blank=self.text_featurizer.num_classes - 1)
+        ids, lens = ids.clamp(min=0).cpu().numpy(), lens.cpu().numpy()
+        return [[int(n) for n in ids[b, :int(lens[b])] if n != 0] for b in range(B)]
+
+    def offline_stt_batch(self, items, max_batch_samples=None, sample_rates=None):
+        """offline_stt for every item of a list -- paths or 1-D waveforms -- in ragged batches: ONE ragged `predict` per batch
+        (mi355asr_chunk_predict_ragged), each row computed as if alone, then the greedy decode (or the prefix beam search) of
+        every row over its own counts[b] text frames.  Returns the texts in the order of `items`.  Every item is normalised as
+        `load_wav` does (data / abs(data.max())), the items are sorted by length and cut into batches of at most
+        max_batch_samples padded samples (None: one batch).  sample_rates: as ASR.offline_stt_batch -- an item with a rate is
+        resampled on the device (resample.Resampler) and normalised there, over its own samples."""
+        from .asr import batch_items, batch_rows, cut_batches
+        model_rate = int(self.speech_featurizer.sample_rate)
+        waves, rates = batch_items(items, sample_rates, self.speech_featurizer.load_wav, model_rate)
+        own = lambda i: rates is None or rates[i] is None
+        waves = [w / np.abs(w.max()) if own(i) and len(w) else w for i, w in enumerate(waves)]
+        n16, batches = cut_batches(waves, rates, model_rate, max_batch_samples)
+        hop = int(self.runner._stream_cfg()[1])
+        for i, n in enumerate(n16):
+            if n < 2 * hop + 1:
+                raise ValueError("item %d has %d samples at the model's rate: the chunk front end needs at least %d" % (i, n, 2 * hop + 1))
+        out = [None] * len(waves)
+        for idx in batches:
+            lens = np.array([n16[i] for i in idx], np.int32)
+            x = batch_rows(waves, rates, idx, lens, int(lens.max()), self._resampler, self.device)
+            if isinstance(x, torch.Tensor):                    # the resampled rows: normalised where they are
+                for r, i in enumerate(idx):
+                    if not own(i):
+                        row = x[r, :int(lens[r])]
+                        x[r, :int(lens[r])] = row / row.max().abs()
+            logits, counts = self.runner.predict(x, wav_lengths=lens)
+            for r, ids in enumerate(self._batch_ids(logits, counts)):
+                out[idx[r]] = "".join(self.text_featurizer.iextract(ids))
+        return out
+
     def stream_call(self, wav_path, verbose=False):
         """test_chunk_asr.py:47-139 -> {"streaming": [(seconds_heard, phones, text), ...], "offline": text}"""
         r = self.runner

@@ -48,11 +48,16 @@ ChunkPlan make_chunk_plan(const mi355asr_model* m, int B, int F, int T) {
 // On return the stack's hidden output is in sc.xa (sc is updated: the blocks ping-pong xa/xb).
 // `front` (round 4): a plain layer the caller left to this stack's first block (the chunk front's subsampling Dense: BlockOpts::pre_*
 // of the stack's options filled in; `in` is not read then).  A stack's own projection takes the same route when it can.
+// len / len_host (ragged batches): the rows of each utterance, on the device and on the host (BlockOpts::t_len of every block)
 int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int B, int T, Scratch& sc,
-              float* logits, int32_t* amax, hipStream_t s, const BlockOpts* front = nullptr) {
+              float* logits, int32_t* amax, hipStream_t s, const BlockOpts* front = nullptr, const int32_t* len = nullptr,
+              const int32_t* len_host = nullptr) {
   const int d = m->cfg.dmodel;
   const int M = B * T;
   BlockOpts first = front ? *front : st.opts;
+  BlockOpts rest = st.opts;
+  first.t_len = rest.t_len = len;
+  first.t_len_host = rest.t_len_host = len_host;
   if (!front && st.proj_wp && st.proj_pp && !st.blocks.empty() && block_takes_pre(m, st.blocks[0], (size_t)M)) {
     first.pre_x = in; first.pre_pp = st.proj_pp; first.pre_sw = st.proj_pp_sw; first.pre_chunks = 1;
   }
@@ -75,7 +80,7 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
   bool ff1_done = false;                    // the tail of block i also runs ff_module_1 + qkv of block i + 1 (model.h)
   for (size_t i = 0; i < st.blocks.size(); ++i) {
     const bool skip = ff1_done;
-    int rc = run_block(m, st.blocks[i], i == 0 ? first : st.opts, sc, B, T, nullptr, s, nullptr,
+    int rc = run_block(m, st.blocks[i], i == 0 ? first : rest, sc, B, T, nullptr, s, nullptr,
                        i + 1 < st.blocks.size() ? &st.blocks[i + 1] : nullptr, &ff1_done, skip);
     if (rc) return rc;
   }
@@ -94,7 +99,7 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
 // |mel| when the banded mel kernel runs; set to null when it did not (the dense kernel does not produce it).
 // pad_left: zeros in front of the first frame (default: the layer's n_dft - 1; the batched streams frame a window they cut themselves)
 int run_valid_mel(const mi355asr_model* m, const float* wav, int B, int L, int F, float* logp, float* pmax, float* mel,
-                  unsigned** absmax, hipStream_t s, int pad_left = -1) {
+                  unsigned** absmax, hipStream_t s, int pad_left = -1, const int32_t* f_len = nullptr) {
   const auto& c = m->cfg;
   if (pad_left < 0) pad_left = c.n_dft - 1;
   const int FT = ceil_div(F, 16);
@@ -117,6 +122,7 @@ int run_valid_mel(const mi355asr_model* m, const float* wav, int B, int L, int F
   me.logp = logp; me.umax = nullptr; me.mel = mel; me.wp = m->mel_wp;
   me.B = B; me.F = F; me.LP = m->dm.LP; me.nbins = m->dm.nbins; me.KBm = m->dm.KBm; me.NTm = m->dm.NTm;
   me.NM = c.n_mels; me.FT = FT; me.floor_db = 0.f;
+  me.f_len = f_len;                 // ragged batches: the utterance's largest |mel| over its own frames
   if (absmax && *absmax) { HIP_TRY(hipMemsetAsync(*absmax, 0, sizeof(unsigned) * (size_t)B, s)); me.absmax = *absmax; }
   { PROF(MI355ASR_K_MEL); LAUNCH_TRY(launch_mel_auto(m, me, s), "mel (valid)"); }
   if (absmax) *absmax = me.absmax;
@@ -256,6 +262,153 @@ const StackDev* chunk_stack_by_id(const mi355asr_model* m, int id) {
   return nullptr;
 }
 
+// the ragged call's workspace: the plan's, then the mel frames and the encoder frames of every utterance (B words each)
+size_t chunk_ragged_total(const ChunkPlan& p, int B) { return p.total + 2 * align256((size_t)B * 4); }
+
+// One body for mi355asr_chunk_predict and its ragged form.  ragged: wav_len [B] on the device, utterance b
+// being wav[b, :wav_len[b]]; every output row of it equals the call on that utterance alone.  The front, the causal conv and
+// every row-wise layer never read past a row's own frames, so the lengths reach four places only: the utterance maximum of the
+// mel kernel, the band attention (BlockOpts::t_len: T_b for encoder and picker, the pick counts for helper and decoder),
+// feature_pick, and the rows past a length in the outputs.
+int chunk_predict(mi355asr_model* m, const float* wav, bool ragged, const int32_t* wav_len, int32_t B, int32_t L,
+                  const mi355asr_chunk_outputs* outs, int32_t* n_picked, int32_t* t_pick, void* ws_, size_t ws_bytes, void* stream) {
+  if (!m || !m->is_chunk) return fail(MI355ASR_EINVAL, "not a ChunkConformer handle");
+  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
+  if (!wav || !outs || !n_picked || !t_pick || !ws_) return fail(MI355ASR_EINVAL, "null argument");
+  if (ragged && !wav_len) return fail(MI355ASR_EINVAL, "wav_len: null device pointer");
+  // (the block kernels that apply lengths: run_block refuses the others, but only once the front has been launched)
+  if (ragged && (m->cfg.gemm_dtype != 0 || use_gemm16(m) || !block_switches().fused))
+    return fail(MI355ASR_EINVAL, "ragged ChunkConformer batches: gemm_dtype bf16 / the layer-at-a-time GEMM mode (MI355ASR_GEMM16) / "
+                "MI355ASR_FUSED=0: only the fp32 dmodel-144 block kernels apply lengths");
+  ChunkGeom g;
+  int rc = chunk_geometry(m, B, L, &g);
+  if (rc) return rc;
+  const ChunkPlan p = make_chunk_plan(m, B, g.F, g.T);
+  const size_t need = ragged ? chunk_ragged_total(p, B) : p.total;
+  if (ws_bytes < need) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  char* ws = (char*)ws_;
+  hipStream_t s = (hipStream_t)stream;
+  // ragged: the lengths are device words: read once (this synchronises the stream), held to [2 hop + 1, L] -- at least one encoder frame
+  std::vector<int32_t> t_host;
+  int32_t *f_len = nullptr, *t_len = nullptr;
+  if (ragged) {
+    std::vector<int32_t> wl((size_t)B, 0);
+    HIP_TRY(hipMemcpyAsync(wl.data(), wav_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int lo = 2 * m->dm.hop + 1;
+    t_host.resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      if (wl[b] < lo || wl[b] > L) return fail(MI355ASR_EINVAL, "wav_len[%d] = %d lies outside [%d, %d]", b, wl[b], lo, L);
+      ChunkGeom gb;
+      if ((rc = chunk_geometry(m, 1, wl[b], &gb))) return rc;
+      t_host[b] = gb.T;
+    }
+    f_len = (int32_t*)(ws + p.total);
+    t_len = (int32_t*)(ws + p.total + align256((size_t)B * 4));
+    LAUNCH_TRY(launch_chunk_ragged_frames(wav_len, B, m->dm.hop, f_len, t_len, s), "ragged frame counts");
+  }
+  const int32_t* t_len_host = ragged ? t_host.data() : nullptr;
+  // rows past an utterance's length get defined values: 0, and -1 for ids
+  auto pad_rows = [&](const int32_t* len, int rows, float* x, int n, int32_t* ids) -> int {
+    if (len && (x || ids)) LAUNCH_TRY(launch_ragged_rows(len, B, rows, x, n, n, ids, s), "ragged ChunkConformer rows");
+    return 0;
+  };
+  const auto& c = m->cfg;
+  const int d = c.dmodel, T = g.T;
+  const size_t act = (size_t)B * T * d * 4;
+  Scratch sc = make_scratch(p, ws);
+  BlockOpts enc_front;
+  bool dense_deferred = false;
+  // ---- front: valid Melspectrogram + left-padded VALID ConvSubsampling
+  {
+    float* mel = (float*)(ws + p.mel);
+    // round 4: the valid frontend's log10 features have no static bound; the banded mel kernel leaves each utterance's largest
+    // |mel| in the first B words of the (by now consumed) per-frame maxima, and the two-term subsampling conv scales by it
+    // (round 5: per utterance, not per batch -- a quiet utterance next to a loud one keeps its own 2^-22, and B = 1 == B = N)
+    unsigned* melmax = (m->mel_band && m->c2_whalf && m->c1_l1 > 0.f) ? (unsigned*)(ws + p.pmax) : nullptr;
+    if ((rc = run_valid_mel(m, wav, B, L, g.F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, &melmax, s, -1, f_len))) return rc;
+    SubConvArgs sa{};
+    sa.mel = mel; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+    sa.w2s = m->c2_wsplit;
+    static const bool three = mi355_env("MI355ASR_SUBCONV_TERMS", -1) == 3;
+    if (melmax && !three) { sa.w2h = m->c2_whalf; sa.h_wscale = m->c2_wscale; sa.h_melmax = melmax; sa.h_l1 = m->c1_l1; sa.h_bmax = m->c1_bmax; sa.c1_wscale = m->c1_wscale; }
+    sa.B = B; sa.F = g.F; sa.NM = c.n_mels; sa.T1 = g.T1; sa.F1 = m->dm.F1; sa.T2 = T; sa.F2 = m->dm.F2;
+    sa.st1 = 2; sa.pt1 = 4; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
+    { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (valid)"); }
+    StreamGemmArgs lg{};
+    lg.x = sa.out; lg.y = sc.xa; lg.wp = m->lin_wp; lg.bias = m->lin_b;
+    lg.M = B * T; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+    // round 4: the Dense rides in the encoder's first ff_module_1 + qkv launch when both run on the two-term stream and
+    // nobody asked for the front's output (as encoder_impl in api.hip)
+    if (!outs->front_out && !m->c_enc.proj_wp && !m->c_enc.blocks.empty() && m->lin_wsplit && lg.M >= 4096 && m->lin_pp &&
+        pp_sublinear_ok(lg, m->lin_pp) && block_takes_pre(m, m->c_enc.blocks[0], (size_t)lg.M)) {
+      enc_front = m->c_enc.opts;
+      enc_front.pre_x = sa.out; enc_front.pre_pp = m->lin_pp; enc_front.pre_sw = m->lin_pp_sw; enc_front.pre_chunks = m->dm.F2;
+      dense_deferred = true;
+    } else {
+      PROF(MI355ASR_K_SUBLINEAR);
+      // the split-bf16 ring-DMA Dense from 4096 rows on (as run_subsampling in api.hip), else the fp32-MFMA stream kernel
+      // (round 4: the two-term stream with a scale per token and 144-wide chunk first, as run_subsampling in api.hip)
+      if (!(m->lin_wsplit && lg.M >= 4096 && ((m->lin_pp && launch_pp_sublinear(lg, m->lin_pp, m->lin_pp_sw, s) == 0) ||
+                                              launch_sublinear_split(lg, m->lin_wsplit, s) == 0)))
+        LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear");
+    }
+  }
+  if (outs->front_out) {
+    HIP_TRY(hipMemcpyAsync(outs->front_out, sc.xa, act, hipMemcpyDeviceToDevice, s));
+    if ((rc = pad_rows(t_len, T, outs->front_out, d, nullptr))) return rc;
+  }
+  // ---- encoder
+  rc = run_stack(m, m->c_enc, sc.xa, B, T, sc, nullptr, nullptr, s, dense_deferred ? &enc_front : nullptr, t_len, t_len_host);
+  if (rc) return rc;
+  if (outs->enc_out) {
+    HIP_TRY(hipMemcpyAsync(outs->enc_out, sc.xa, act, hipMemcpyDeviceToDevice, s));
+    if ((rc = pad_rows(t_len, T, outs->enc_out, d, nullptr))) return rc;
+  }
+  // ---- phone picker: logits (optional) + per-frame argmax, hidden = block output
+  int32_t* amax = (int32_t*)(ws + p.amax);
+  rc = run_stack(m, m->c_picker, sc.xa, B, T, sc, outs->picker_logits, amax, s, nullptr, t_len, t_len_host);
+  if (rc) return rc;
+  if ((rc = pad_rows(t_len, T, outs->picker_logits, m->ccfg.picker_num_classes, nullptr))) return rc;
+  float* hid = (float*)(ws + p.hid);
+  HIP_TRY(hipMemcpyAsync(hid, sc.xa, act, hipMemcpyDeviceToDevice, s));
+  if (outs->picker_hidden) {
+    HIP_TRY(hipMemcpyAsync(outs->picker_hidden, sc.xa, act, hipMemcpyDeviceToDevice, s));
+    if ((rc = pad_rows(t_len, T, outs->picker_hidden, d, nullptr))) return rc;
+  }
+  // ---- feature_pick
+  int32_t* idx = (int32_t*)(ws + p.idx);
+  int32_t* cnt = (int32_t*)(ws + p.cnt);
+  PickArgs pa{amax, idx, cnt, B, T, m->ccfg.picker_num_classes - 1};
+  pa.t_len = t_len;                    // ragged: frames past an utterance's own are never picked
+  LAUNCH_TRY(launch_pick(pa, s), "feature_pick compaction");
+  HIP_TRY(hipMemcpyAsync(n_picked, cnt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));    // the batch maximum sizes everything downstream (dynamic shape in the reference)
+  int Tp = 0;
+  for (int b = 0; b < B; ++b) Tp = std::max(Tp, n_picked[b]);
+  *t_pick = Tp;
+  if (Tp == 0) return 0;               // nothing picked: the reference would build [B, 0, V] logits
+  GatherArgs ga{hid, idx, cnt, sc.xa, B, T, Tp, d};
+  LAUNCH_TRY(launch_gather(ga, s), "feature_pick gather");
+  const size_t actp = (size_t)B * Tp * d * 4;
+  if (outs->picked) HIP_TRY(hipMemcpyAsync(outs->picked, sc.xa, actp, hipMemcpyDeviceToDevice, s));
+  // ---- context helper, text decoder (ragged: each utterance's pick count is its length; the counts are on the host by now)
+  const int32_t* p_len = ragged ? cnt : nullptr;
+  const int32_t* p_len_host = ragged ? n_picked : nullptr;
+  rc = run_stack(m, m->c_helper, sc.xa, B, Tp, sc, nullptr, nullptr, s, nullptr, p_len, p_len_host);
+  if (rc) return rc;
+  if (outs->helper_out) {
+    HIP_TRY(hipMemcpyAsync(outs->helper_out, sc.xa, actp, hipMemcpyDeviceToDevice, s));
+    if ((rc = pad_rows(p_len, Tp, outs->helper_out, d, nullptr))) return rc;
+  }
+  // (no arg-max unless asked for: the text logits go to top-n / the beam search, and a head without it needs no combine launch)
+  rc = run_stack(m, m->c_decoder, sc.xa, B, Tp, sc, outs->text_logits, outs->text_logits ? outs->text_argmax : (outs->text_argmax ? outs->text_argmax : amax), s,
+                 nullptr, p_len, p_len_host);
+  if (rc) return rc;
+  return pad_rows(p_len, Tp, outs->text_logits, m->ccfg.decoder_num_classes, outs->text_argmax);
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -338,91 +491,22 @@ int mi355asr_chunk_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t L
 
 int mi355asr_chunk_predict(mi355asr_model* m, const float* wav, int32_t B, int32_t L, const mi355asr_chunk_outputs* outs,
                            int32_t* n_picked, int32_t* t_pick, void* ws_, size_t ws_bytes, void* stream) {
-  if (!m || !m->is_chunk) return fail(MI355ASR_EINVAL, "not a ChunkConformer handle");
-  if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
-  if (!wav || !outs || !n_picked || !t_pick || !ws_) return fail(MI355ASR_EINVAL, "null argument");
+  return chunk_predict(m, wav, false, nullptr, B, L, outs, n_picked, t_pick, ws_, ws_bytes, stream);
+}
+
+int mi355asr_chunk_predict_ragged(mi355asr_model* m, const float* wav, const int32_t* wav_len, int32_t B, int32_t L,
+                                  const mi355asr_chunk_outputs* outs, int32_t* n_picked, int32_t* t_pick, void* ws_,
+                                  size_t ws_bytes, void* stream) {
+  return chunk_predict(m, wav, true, wav_len, B, L, outs, n_picked, t_pick, ws_, ws_bytes, stream);
+}
+
+int mi355asr_chunk_workspace_bytes_ragged(const mi355asr_model* m, int32_t B, int32_t L, size_t* bytes) {
+  if (!m || !m->is_chunk || !bytes) return fail(MI355ASR_EINVAL, "not a ChunkConformer handle / null argument");
   ChunkGeom g;
   int rc = chunk_geometry(m, B, L, &g);
   if (rc) return rc;
-  const ChunkPlan p = make_chunk_plan(m, B, g.F, g.T);
-  if (ws_bytes < p.total) return fail(MI355ASR_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
-  char* ws = (char*)ws_;
-  hipStream_t s = (hipStream_t)stream;
-  const auto& c = m->cfg;
-  const int d = c.dmodel, T = g.T;
-  const size_t act = (size_t)B * T * d * 4;
-  Scratch sc = make_scratch(p, ws);
-  BlockOpts enc_front;
-  bool dense_deferred = false;
-  // ---- front: valid Melspectrogram + left-padded VALID ConvSubsampling
-  {
-    float* mel = (float*)(ws + p.mel);
-    // round 4: the valid frontend's log10 features have no static bound; the banded mel kernel leaves each utterance's largest
-    // |mel| in the first B words of the (by now consumed) per-frame maxima, and the two-term subsampling conv scales by it
-    // (round 5: per utterance, not per batch -- a quiet utterance next to a loud one keeps its own 2^-22, and B = 1 == B = N)
-    unsigned* melmax = (m->mel_band && m->c2_whalf && m->c1_l1 > 0.f) ? (unsigned*)(ws + p.pmax) : nullptr;
-    if ((rc = run_valid_mel(m, wav, B, L, g.F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, &melmax, s))) return rc;
-    SubConvArgs sa{};
-    sa.mel = mel; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
-    sa.w2s = m->c2_wsplit;
-    static const bool three = mi355_env("MI355ASR_SUBCONV_TERMS", -1) == 3;
-    if (melmax && !three) { sa.w2h = m->c2_whalf; sa.h_wscale = m->c2_wscale; sa.h_melmax = melmax; sa.h_l1 = m->c1_l1; sa.h_bmax = m->c1_bmax; sa.c1_wscale = m->c1_wscale; }
-    sa.B = B; sa.F = g.F; sa.NM = c.n_mels; sa.T1 = g.T1; sa.F1 = m->dm.F1; sa.T2 = T; sa.F2 = m->dm.F2;
-    sa.st1 = 2; sa.pt1 = 4; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
-    { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (valid)"); }
-    StreamGemmArgs lg{};
-    lg.x = sa.out; lg.y = sc.xa; lg.wp = m->lin_wp; lg.bias = m->lin_b;
-    lg.M = B * T; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
-    // round 4: the Dense rides in the encoder's first ff_module_1 + qkv launch when both run on the two-term stream and
-    // nobody asked for the front's output (as encoder_impl in api.hip)
-    if (!outs->front_out && !m->c_enc.proj_wp && !m->c_enc.blocks.empty() && m->lin_wsplit && lg.M >= 4096 && m->lin_pp &&
-        pp_sublinear_ok(lg, m->lin_pp) && block_takes_pre(m, m->c_enc.blocks[0], (size_t)lg.M)) {
-      enc_front = m->c_enc.opts;
-      enc_front.pre_x = sa.out; enc_front.pre_pp = m->lin_pp; enc_front.pre_sw = m->lin_pp_sw; enc_front.pre_chunks = m->dm.F2;
-      dense_deferred = true;
-    } else {
-      PROF(MI355ASR_K_SUBLINEAR);
-      // the split-bf16 ring-DMA Dense from 4096 rows on (as run_subsampling in api.hip), else the fp32-MFMA stream kernel
-      // (round 4: the two-term stream with a scale per token and 144-wide chunk first, as run_subsampling in api.hip)
-      if (!(m->lin_wsplit && lg.M >= 4096 && ((m->lin_pp && launch_pp_sublinear(lg, m->lin_pp, m->lin_pp_sw, s) == 0) ||
-                                              launch_sublinear_split(lg, m->lin_wsplit, s) == 0)))
-        LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear");
-    }
-  }
-  if (outs->front_out) HIP_TRY(hipMemcpyAsync(outs->front_out, sc.xa, act, hipMemcpyDeviceToDevice, s));
-  // ---- encoder
-  rc = run_stack(m, m->c_enc, sc.xa, B, T, sc, nullptr, nullptr, s, dense_deferred ? &enc_front : nullptr);
-  if (rc) return rc;
-  if (outs->enc_out) HIP_TRY(hipMemcpyAsync(outs->enc_out, sc.xa, act, hipMemcpyDeviceToDevice, s));
-  // ---- phone picker: logits (optional) + per-frame argmax, hidden = block output
-  int32_t* amax = (int32_t*)(ws + p.amax);
-  rc = run_stack(m, m->c_picker, sc.xa, B, T, sc, outs->picker_logits, amax, s);
-  if (rc) return rc;
-  float* hid = (float*)(ws + p.hid);
-  HIP_TRY(hipMemcpyAsync(hid, sc.xa, act, hipMemcpyDeviceToDevice, s));
-  if (outs->picker_hidden) HIP_TRY(hipMemcpyAsync(outs->picker_hidden, sc.xa, act, hipMemcpyDeviceToDevice, s));
-  // ---- feature_pick
-  int32_t* idx = (int32_t*)(ws + p.idx);
-  int32_t* cnt = (int32_t*)(ws + p.cnt);
-  PickArgs pa{amax, idx, cnt, B, T, m->ccfg.picker_num_classes - 1};
-  LAUNCH_TRY(launch_pick(pa, s), "feature_pick compaction");
-  HIP_TRY(hipMemcpyAsync(n_picked, cnt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));    // the batch maximum sizes everything downstream (dynamic shape in the reference)
-  int Tp = 0;
-  for (int b = 0; b < B; ++b) Tp = std::max(Tp, n_picked[b]);
-  *t_pick = Tp;
-  if (Tp == 0) return 0;               // nothing picked: the reference would build [B, 0, V] logits
-  GatherArgs ga{hid, idx, cnt, sc.xa, B, T, Tp, d};
-  LAUNCH_TRY(launch_gather(ga, s), "feature_pick gather");
-  const size_t actp = (size_t)B * Tp * d * 4;
-  if (outs->picked) HIP_TRY(hipMemcpyAsync(outs->picked, sc.xa, actp, hipMemcpyDeviceToDevice, s));
-  // ---- context helper, text decoder
-  rc = run_stack(m, m->c_helper, sc.xa, B, Tp, sc, nullptr, nullptr, s);
-  if (rc) return rc;
-  if (outs->helper_out) HIP_TRY(hipMemcpyAsync(outs->helper_out, sc.xa, actp, hipMemcpyDeviceToDevice, s));
-  // (no arg-max unless asked for: the text logits go to top-n / the beam search, and a head without it needs no combine launch)
-  rc = run_stack(m, m->c_decoder, sc.xa, B, Tp, sc, outs->text_logits, outs->text_logits ? outs->text_argmax : (outs->text_argmax ? outs->text_argmax : amax), s);
-  return rc;
+  *bytes = chunk_ragged_total(make_chunk_plan(m, B, g.F, g.T), B);
+  return 0;
 }
 
 int mi355asr_frame_argmax(const float* x, int32_t M, int32_t V, int32_t* out, void* stream) {

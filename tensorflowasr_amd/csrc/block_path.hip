@@ -46,6 +46,8 @@ AttnChoice choose_attention(int HS, const AttnArgs& a) {
   if (a.k_len) {                                      // ragged batches: the split kernels apply key lengths, and at head size 64
     // (token-major rows, full attention) every kernel of the solo call does, each for the utterances it would take alone
     if (HS == 64 && a.win_front < 0 && !a.head_major && a.ldk % 4 == 0 && a.ldq % 4 == 0) c.kernel = ATTN_RAGGED64;
+    // band attention (token-major rows, any head size): the online-softmax kernel with the utterance's length as the band's T
+    else if (a.win_front >= 0 && !a.head_major && attention_head_size_ok(HS)) { c.kernel = ATTN_ONLINE; c.band_lengths = true; }
     return c;
   }
   if (split_on && w.attn64_split && attention_split64_applicable(HS, a)) {   // round 5: head size 64, bounds known, <= 288 keys

@@ -434,8 +434,15 @@ __global__ __launch_bounds__(BLOCK_THREADS, ((HS > 36 && KT >= 16) ? 1 : 2)) voi
   const int h = blockIdx.y, b = blockIdx.z;
   int T = TKA, TQ = TQA;               // keys / queries of this utterance
   if constexpr (HS == 64 && !LDSW) {   // ragged batches: the utterance's own lengths (attn64_class; uniform per workgroup)
-    if (a.k_len && !attn64_mine(a, b, KT == 1 ? ATTN64_ONLINE1 : KT == 4 ? ATTN64_ONLINE4 : ATTN64_ONLINE16, &TQ, &T)) return;
+    if (a.k_len && a.win_front < 0 && !attn64_mine(a, b, KT == 1 ? ATTN64_ONLINE1 : KT == 4 ? ATTN64_ONLINE4 : ATTN64_ONLINE16, &TQ, &T)) return;
   }
+  // ragged band attention (the ChunkConformer's stacks): the utterance's own length is the T of BOTH clamps of the band, keys at
+  // or past it are neither staged nor multiplied, and a query tile past it leaves at once (one scalar load, uniform per workgroup)
+  if (a.k_len && a.win_front >= 0) {
+    T = min(a.k_len[b], TKA);
+    TQ = min(TQA, T - a.q_off);
+  }
+  if (LDSW && (int)blockIdx.x * (16 * WAVES_PER_BLOCK) >= TQ) return;   // (never without lengths: the grid covers Tq)
   if (!LDSW && qt * 16 >= TQ) return;
   const int ld = a.ldk;  // row stride of the k / v buffers
   const int D = a.D;

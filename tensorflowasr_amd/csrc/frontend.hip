@@ -227,6 +227,7 @@ __global__ __launch_bounds__(256) void mel_band_kernel(MelArgs a) {
   if (threadIdx.x < 2 * NM) bl[threadIdx.x] = bnd;
   __syncthreads();
   float amax = 0.f;
+  const int fv = (a.f_len ? min(a.f_len[b], a.F) : a.F) - f0;      // frames of this tile that count for the utterance's maximum
   for (int o = threadIdx.x; o < nf * NM; o += 256) {
     const int fr = o / NM, m = o - fr * NM;
     const int lo = bl[2 * m], len4 = (bl[2 * m + 1] + 3) & ~3;     // weights are zero-padded to BW, rows to RS >= lo + BW
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(256) void mel_band_kernel(MelArgs a) {
       acc = __builtin_fmaf(x[j + 3], w4.w, acc);
     }
     a.mel[((size_t)b * a.F + f0 + fr) * NM + m] = acc;
-    amax = fmaxf(amax, fabsf(acc));
+    amax = fr < fv ? fmaxf(amax, fabsf(acc)) : amax;
   }
   if (a.absmax) {
     // |x| >= 0, so the float order is the order of the bit patterns.  One candidate per workgroup, and an atomic only when it
@@ -536,6 +537,22 @@ int launch_ragged_frames(const int32_t* wav_len, int B, int hop, int st1, int32_
   return 0;
 }
 
+// 'valid' chunk front (chunk_geometry in api_chunk.hip, per utterance): F = (L - 1) / hop + 1, T1 = (F + 1) / 2 + 1, T = (T1 - 3) / 2 + 1
+__global__ __launch_bounds__(64) void chunk_ragged_frames_kernel(const int32_t* __restrict__ wav_len, int B, int hop,
+                                                                 int32_t* __restrict__ f_len, int32_t* __restrict__ t_len) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int F = (wav_len[b] - 1) / hop + 1;
+  const int T1 = (F + 1) / 2 + 1;
+  f_len[b] = F;
+  t_len[b] = (T1 - 3) / 2 + 1;
+}
+int launch_chunk_ragged_frames(const int32_t* wav_len, int B, int hop, int32_t* f_len, int32_t* t_len, hipStream_t s) {
+  if (B <= 0 || !wav_len || !f_len || !t_len) return -1;
+  hipLaunchKernelGGL(chunk_ragged_frames_kernel, dim3((B + 63) / 64), dim3(64), 0, s, wav_len, B, hop, f_len, t_len);
+  return 0;
+}
+
 // one workgroup per row: rows of the utterance's own frames leave at once
 __global__ __launch_bounds__(256) void ragged_rows_kernel(const int32_t* __restrict__ t_len, int T, float* x, int ld, int n,
                                                           int32_t* ids) {
@@ -566,10 +583,11 @@ __global__ __launch_bounds__(64) void pick_kernel(PickArgs a) {
   // as the compiler may not assume the two pointers are distinct
   const int32_t* src = a.frame_ids + (size_t)b * a.T;
   int32_t* dst = a.idx + (size_t)b * a.T;
+  const int T = a.t_len ? min(a.t_len[b], a.T) : a.T;             // ragged batches: the utterance's own frames (uniform)
   int count = 0;
-  for (int t0 = 0; t0 < a.T; t0 += 64) {
+  for (int t0 = 0; t0 < T; t0 += 64) {
     const int t = t0 + lane;
-    const bool keep = t < a.T && src[t] != a.blank;
+    const bool keep = t < T && src[t] != a.blank;
     const unsigned long long mask = __ballot(keep);
     if (keep) dst[count + __popcll(mask & ((1ull << lane) - 1ull))] = t;
     count += __popcll(mask);

@@ -153,6 +153,8 @@ struct MelArgs {
   // on the bits of non-negative floats; the caller zeroes the words first).  The 'valid' chunk frontend has no dB normalisation, hence no static
   // bound on its features: the two-term subsampling conv takes its operand scale from this run-time maximum.
   unsigned* absmax = nullptr;
+  // ragged batches: utterance b has f_len[b] frames ([B] on the device); absmax is taken over those only (nullptr: all F)
+  const int32_t* f_len = nullptr;
 };
 struct SubConvArgs {
   const float* mel;   // [B, F, NM]
@@ -205,6 +207,7 @@ struct PickArgs {
   int32_t* idx;              // [B, T] indices of kept frames (first cnt[b] entries valid); may alias frame_ids (in place)
   int32_t* cnt;              // [B]
   int B, T, blank;
+  const int32_t* t_len = nullptr;   // ragged batches: utterance b has t_len[b] frames, later ones are never picked (nullptr: T)
 };
 struct GatherArgs {
   const float* src;          // [B, T, D]
@@ -429,7 +432,8 @@ struct AttnChoice {
   int terms = 0;   // ATTN_SPLIT / ATTN_SPLIT_LONG: two fp16 or three bf16 terms per operand
   bool split() const { return kernel == ATTN_SPLIT || kernel == ATTN_SPLIT_LONG; }
   bool head_major() const { return split() && terms == 2; }   // the one form that reads head-major q / k / v
-  bool applies_lengths() const { return split() || kernel == ATTN_RAGGED64; }   // ... and the kernels that read AttnArgs::k_len
+  bool band_lengths = false;   // ATTN_ONLINE on a band launch with AttnArgs::k_len: attention_kernel takes each utterance's own T
+  bool applies_lengths() const { return split() || kernel == ATTN_RAGGED64 || band_lengths; }   // ... and the kernels that read AttnArgs::k_len
 };
 // Ragged batches at head size 64 (full attention, token-major rows).  A ragged row is defined as the solo call's result, and the
 // solo call's attention kernel depends on its own tq queries and tk keys: attention_split64_kernel for 33 .. 288 keys where the
@@ -580,3 +584,5 @@ int launch_collapse(const CollapseArgs& a, hipStream_t s);
 int launch_ragged_frames(const int32_t* wav_len, int B, int hop, int st1, int32_t* t_len, int32_t* t_out, hipStream_t s);
 // rows t >= t_len[b] of [B, T] row-major outputs get defined values: x (ld floats per row, the first n written) 0, ids -1
 int launch_ragged_rows(const int32_t* t_len, int B, int T, float* x, int ld, int n, int32_t* ids, hipStream_t s);
+// ragged ChunkConformer batches: f_len[b] / t_len[b] = mel frames / encoder frames of a wav_len[b]-sample utterance ('valid' front)
+int launch_chunk_ragged_frames(const int32_t* wav_len, int B, int hop, int32_t* f_len, int32_t* t_len, hipStream_t s);

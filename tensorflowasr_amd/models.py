@@ -70,6 +70,18 @@ def ragged_geometry(L, hop=160, n_dft=1024, reduction_factor=4):
     return dict(F=F, pad_left=pad_left, T1=T1, pt1=pt1, T=T, pt2=pt2)
 
 
+def chunk_ragged_geometry(L, hop=160):
+    """The per-utterance shapes of a ragged ChunkConformer batch (mi355asr_chunk_predict_ragged): an utterance of L samples has
+    F = (L - 1) // hop + 1 'valid' mel frames, T1 = (F + 1) // 2 + 1 rows behind conv1 (four zero frames in front, VALID 3x3
+    stride 2) and T = (T1 - 3) // 2 + 1 encoder frames; T >= 1 needs L >= 2 hop + 1."""
+    L = int(L)
+    if L < 2 * hop + 1:
+        raise ValueError("L = %d is too short for the chunk front end: at least 2 * hop + 1 = %d samples" % (L, 2 * hop + 1))
+    F = (L - 1) // hop + 1
+    T1 = (F + 1) // 2 + 1
+    return dict(F=F, T1=T1, T=(T1 - 3) // 2 + 1)
+
+
 def _lengths(h, lengths, B, what):
     """[B] lengths of a ragged batch as a contiguous int32 device tensor"""
     t = h.to_device(lengths, torch.int32).reshape(-1).contiguous()
@@ -998,8 +1010,9 @@ class ChunkBeamPipeline:
             self.side.wait_event(ready)
             return ctc_prefix_beam_decode(logits, counts, is_logits=True, **self.kw)
 
-    def push(self, wav):
-        logits, counts = self.model.predict(wav)
+    def push(self, wav, wav_lengths=None):
+        """wav_lengths: a ragged batch (ChunkConformer.predict); the search takes the counts as every row's length either way"""
+        logits, counts = self.model.predict(wav) if wav_lengths is None else self.model.predict(wav, wav_lengths=wav_lengths)
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(self.device))
         logits.record_stream(self.side)                    # the caching allocator must not hand the logits out again early
@@ -1398,9 +1411,16 @@ class ChunkConformer(_ModelBase):
         _lib.check(self._h.lib.mi355asr_chunk_out_frames(self._h.ptr, L, ctypes.byref(f), ctypes.byref(t)))
         return f.value, t.value
 
-    def predict(self, x, stages=False):
+    def predict(self, x, stages=False, wav_lengths=None):
         """x [B, L(,1)] -> text logits torch [B, T_pick, txt_num_classes] (+ counts).  With stages=True returns a dict
-        with every intermediate the reference's predict() produces."""
+        with every intermediate the reference's predict() produces.
+
+        Without wav_lengths the batch has the reference's semantics: every row is L samples, and the picked rows of an
+        utterance are zero-padded to the batch maximum BEFORE the helper and the text decoder, whose band attention then reads
+        that padding -- a row's logits depend on what else is in the batch.  wav_lengths ([B] samples per utterance): a ragged
+        batch (mi355asr_chunk_predict_ragged) -- row b is what the call on x[b:b+1, :wav_lengths[b]] returns, whatever lies
+        behind it in the row; counts[b] is the valid length of its text logits, rows past it are 0 (text_argmax -1), and
+        stages=True adds "enc_lengths", the encoder frames of every utterance."""
         h = self._h
         if not h.built:
             self._build()
@@ -1409,7 +1429,12 @@ class ChunkConformer(_ModelBase):
         _, T = self.out_frames(L)
         d, V = self.dmodel, self.txt_num_classes
         n = ctypes.c_size_t()
-        _lib.check(h.lib.mi355asr_chunk_workspace_bytes(h.ptr, B, L, ctypes.byref(n)))
+        wl = None
+        if wav_lengths is not None:
+            wl = _lengths(h, wav_lengths, B, "wav_lengths")
+            _lib.check(h.lib.mi355asr_chunk_workspace_bytes_ragged(h.ptr, B, L, ctypes.byref(n)))
+        else:
+            _lib.check(h.lib.mi355asr_chunk_workspace_bytes(h.ptr, B, L, ctypes.byref(n)))
         ws = h.workspace(n.value)
         dev = h.device
         bufs = {"text_logits": torch.empty((B, T, V), dtype=torch.float32, device=dev)}
@@ -1422,9 +1447,14 @@ class ChunkConformer(_ModelBase):
         counts = np.zeros(B, np.int32)
         tp = ctypes.c_int32()
         with torch.cuda.device(dev):
-            _lib.check(h.lib.mi355asr_chunk_predict(h.ptr, _p(xd), B, L, ctypes.byref(outs),
-                                                   counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tp),
-                                                   _p(ws), n.value, h._stream()))
+            if wl is not None:
+                _lib.check(h.lib.mi355asr_chunk_predict_ragged(h.ptr, _p(xd), _p(wl), B, L, ctypes.byref(outs),
+                                                              counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tp),
+                                                              _p(ws), n.value, h._stream()))
+            else:
+                _lib.check(h.lib.mi355asr_chunk_predict(h.ptr, _p(xd), B, L, ctypes.byref(outs),
+                                                       counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tp),
+                                                       _p(ws), n.value, h._stream()))
         Tp = tp.value
         logits = bufs["text_logits"].view(-1)[:B * Tp * V].view(B, Tp, V)
         if not stages:
@@ -1435,6 +1465,9 @@ class ChunkConformer(_ModelBase):
              "picker_hidden": bufs["picker_hidden"],
              "picked": bufs["picked"].view(-1)[:B * Tp * d].view(B, Tp, d),
              "helper": bufs["helper_out"].view(-1)[:B * Tp * d].view(B, Tp, d)}
+        if wl is not None:
+            hop = int(self._stream_cfg()[1])
+            r["enc_lengths"] = np.array([chunk_ragged_geometry(int(k), hop)["T"] for k in wl.cpu().numpy()], np.int32)
         return r
 
     __call__ = predict
