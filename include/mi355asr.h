@@ -93,6 +93,10 @@ typedef struct {
 
 const char* mi355asr_last_error(void);
 const char* mi355asr_version(void);
+/* Test hook: the two-term fp16 operand split every two-term kernel applies (hi = fp16(x), lo = fp16(x - hi), both round to
+ * nearest even) on x_dev f32 [n], as bit patterns: hi_dev, lo_dev u16 [n].  Elements are split in pairs (2 i, 2 i + 1) as
+ * the kernels do, so even and odd positions take the two halves of the packed instructions.  Asynchronous on `stream`. */
+int mi355asr_test_split_f16(const float* x_dev, int64_t n, uint16_t* hi_dev, uint16_t* lo_dev, void* stream);
 
 /* replaces: ConformerEncoder(...)/CTCDecoder(...) construction, test_asr.py:28-75 */
 int mi355asr_create(const mi355asr_config* cfg, mi355asr_model** out);

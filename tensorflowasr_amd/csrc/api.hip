@@ -1,5 +1,6 @@
 // libmi355asr.so host side: model object, workspace planning and the launch sequences behind the ConformerCTC / CTCDecoder
 // entry points of the C ABI declared in include/mi355asr.h.  (Weights: weights.hip; which kernels run a block: block_path.hip.)
+#include "common.h"
 #include "model.h"
 
 namespace mi355 {
@@ -467,10 +468,34 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
 // =======================================================================================================
 thread_local int mi355asr_last_scheme = SCHEME_F32;   // launch.h: note_scheme
 
+// mi355asr_test_split_f16: the shared two-term operand split (common.h) on an array, pair by pair as the kernels apply it --
+// element 2 i goes through the low half (v_fma_mixlo_f16), element 2 i + 1 through the high half (v_fma_mixhi_f16)
+__global__ void split_f16_probe_kernel(const float* __restrict__ x, int64_t n, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
+  const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const bool two = i + 1 < n;
+  const float a = x[i], b = two ? x[i + 1] : 0.f;
+  const unsigned h = split_hi_f16(a, b), l = split_lo_f16(h, a, b);
+  hi[i] = (uint16_t)(h & 0xffffu);
+  lo[i] = (uint16_t)(l & 0xffffu);
+  if (two) {
+    hi[i + 1] = (uint16_t)(h >> 16);
+    lo[i + 1] = (uint16_t)(l >> 16);
+  }
+}
+
 extern "C" {
 
 const char* mi355asr_last_error(void) { return g_err; }
 const char* mi355asr_version(void) { return "mi355asr 0.1 (gfx950, fp32 operands as fp16 pairs / bf16 triples on the MFMA pipe)"; }
+
+int mi355asr_test_split_f16(const float* x_dev, int64_t n, uint16_t* hi_dev, uint16_t* lo_dev, void* stream) {
+  if (!x_dev || !hi_dev || !lo_dev) return fail(MI355ASR_EINVAL, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(MI355ASR_EINVAL, "test_split_f16: need 1 <= n <= 2^31 (got %lld)", (long long)n);
+  const int64_t pairs = (n + 1) / 2;
+  hipLaunchKernelGGL(split_f16_probe_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, n, hi_dev, lo_dev);
+  return hipGetLastError() == hipSuccess ? MI355ASR_OK : fail(MI355ASR_EHIP, "test_split_f16: launch failed");
+}
 
 int mi355asr_create(const mi355asr_config* cfg, mi355asr_model** out) {
   if (!cfg || !out) return fail(MI355ASR_EINVAL, "null argument");

@@ -22,6 +22,8 @@
 #include "env.h"
 #include "launch.h"
 
+MI355_SCALAR_F32_BEGIN     // common.h: no packed f32 VALU in this file (measured faster: profiles/valu_diet_mi355x.md)
+
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -64,18 +66,9 @@ DEV f32x4 mma_split(const u32x4_t (&a)[3], const Split8& b, f32x4 c) {
 // Two-term scheme (see subconv.hip / fused_pp.hip): hi + lo fp16 terms of values already multiplied by their power-of-two
 // scale, three products per fragment pair.  Split8::t[2] is unused then.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-DEV unsigned pk_f16(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, f16x2_t)); }
-DEV Split8 split8h(f32x4 lo, f32x4 hi) {
-  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+DEV Split8 split8h(f32x4 lo, f32x4 hi) {     // the shared three-instruction split (common.h: split8_f16)
   unsigned d0[4], d1[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    d0[k] = pk_f16(v[2 * k], v[2 * k + 1]);
-    const f16x2_t h = __builtin_bit_cast(f16x2_t, d0[k]);
-    d1[k] = pk_f16(v[2 * k] - (float)h.x, v[2 * k + 1] - (float)h.y);
-  }
+  split8_f16(lo, hi, d0, d1);
   Split8 f;
   f.t[0] = u32x4_t{d0[0], d0[1], d0[2], d0[3]};
   f.t[1] = u32x4_t{d1[0], d1[1], d1[2], d1[3]};
@@ -515,3 +508,5 @@ int launch_attention_split(int hs, const AttnArgs& a, int terms, hipStream_t s) 
     hipLaunchKernelGGL(attention_split_kernel<3>, grid, dim3(ATH), 0, s, a);
   return 0;
 }
+
+MI355_SCALAR_F32_END

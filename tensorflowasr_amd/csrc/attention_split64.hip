@@ -25,21 +25,12 @@
 namespace {
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 struct Split2 { u32x4_t hi, lo; };
 
-DEV unsigned pk_f16(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, f16x2_t)); }
 DEV Split2 split8h(f32x4 lo, f32x4 hi) {      // eight values -> hi + lo fp16 terms (the values already carry their power-of-two scale)
-  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
   unsigned d0[4], d1[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    d0[k] = pk_f16(v[2 * k], v[2 * k + 1]);
-    const f16x2_t h = __builtin_bit_cast(f16x2_t, d0[k]);
-    d1[k] = pk_f16(v[2 * k] - (float)h.x, v[2 * k + 1] - (float)h.y);
-  }
+  split8_f16(lo, hi, d0, d1);                 // the shared three-instruction split (common.h)
   return Split2{u32x4_t{d0[0], d0[1], d0[2], d0[3]}, u32x4_t{d1[0], d1[1], d1[2], d1[3]}};
 }
 DEV f32x4 mma32h(u32x4_t a, u32x4_t b, f32x4 c) {

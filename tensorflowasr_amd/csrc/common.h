@@ -24,6 +24,22 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define BLOCK_THREADS (WAVE * WAVES_PER_BLOCK)
 
 #define DEV __device__ __forceinline__
+
+// MI355_SCALAR_F32_BEGIN / _END around a kernel file's code (device pass only): f32 VALU arithmetic is emitted one lane value per
+// instruction -- no v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32, neither from the SLP vectoriser nor from f32x4 expressions.  A
+// packed f32 instruction occupies the VALU for two passes and, issued beside a stream of MFMAs, costs more than the two scalar
+// instructions it replaces; in kernels with ONE consumer wave per SIMD nothing else fills that time.  Kept per file where it
+// measured faster (profiles/valu_diet_mi355x.md); -DMI355ASR_PACKED_F32=1 builds every file with the compiler's packing (A / B).
+#ifndef MI355ASR_PACKED_F32
+#define MI355ASR_PACKED_F32 0
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !MI355ASR_PACKED_F32
+#define MI355_SCALAR_F32_BEGIN _Pragma("clang attribute push(__attribute__((target(\"no-packed-fp32-ops\"))), apply_to = function)")
+#define MI355_SCALAR_F32_END _Pragma("clang attribute pop")
+#else
+#define MI355_SCALAR_F32_BEGIN
+#define MI355_SCALAR_F32_END
+#endif
 // __launch_bounds__(BLOCK_THREADS, 2) on the MFMA kernels: asking for two waves per SIMD makes hipcc allocate
 // everything in <= 256 architectural VGPRs (no AGPR half, hence no v_accvgpr_read/write shuffling) and gives
 // every SIMD a second wave whose MFMAs cover the first one's address arithmetic and load issue.
@@ -102,6 +118,31 @@ DEV void mma_batch_rt(f32x4 (&acc)[RT][N], const f32x4 (&w)[N], const f32x4 (&x)
 DEV f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 DEV void stg4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 DEV f32x4 splat4(float v) { f32x4 r = {v, v, v, v}; return r; }
+
+// The two-term fp16 operand split of a value pair (a, b), the one copy every two-term kernel uses: hi = fp16(v), lo = fp16(v - hi),
+// both round-to-nearest-even, each result a packed pair (a in the low half).  Three instructions: v_cvt_pk_f16_f32 for hi, then
+// v_fma_mixlo_f16 / v_fma_mixhi_f16 for lo -- they read the fp16 hi in place (op_sel picks the half), form hi * -1 + v in fp32
+// (exact: v - hi has at most 13 significant bits) and round once into the destination half.  The same bits as v_cvt_f32_f16 +
+// v_sub_f32 + v_cvt_pk_f16_f32 (five to six instructions per pair; tests/test_split_f16.py compares the hardware with NumPy).
+DEV unsigned split_hi_f16(float a, float b) {
+  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, h2_t));
+}
+DEV unsigned split_lo_f16(unsigned hi, float a, float b) {
+  unsigned lo;
+  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a));
+  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(b));
+  return lo;
+}
+// eight values (two accumulator float4s = the k-slots of one 32-wide step) -> four hi pairs, four lo pairs
+DEV void split8_f16(f32x4 lo, f32x4 hi, unsigned (&d0)[4], unsigned (&d1)[4]) {
+  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    d0[k] = split_hi_f16(v[2 * k], v[2 * k + 1]);
+    d1[k] = split_lo_f16(d0[k], v[2 * k], v[2 * k + 1]);
+  }
+}
 
 // sum / max over the 4 lane groups that share a token (lanes t, t+16, t+32, t+48)
 // (Round 5 measured gfx950's v_permlane16_swap_b32 / v_permlane32_swap_b32 here -- handed the same value twice they return, in every

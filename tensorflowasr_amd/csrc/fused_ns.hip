@@ -110,7 +110,7 @@ DEV void ns1_allreduce(f32x4 (&y)[KB], Ns1Lds<NW>& L, int w, int lane) {
 // One phase of a chain for ONE token tile (operands in registers):
 //   B part (HB): y[tile] += W2[pair b][tile] fB        27 MFMAs, tiles in groups of three so that an accumulator rests two MFMAs
 //   A part (HA): hA[0..1] += W1[:, pair a] x            30 MFMAs
-//   prep   (HP): fP = split(swish(hP[0..1]))             40 slots behind the MFMAs (all of them in a row when the phase has none)
+//   prep   (HP): fP = split(swish(hP[0..1]))             PREP2_SLOTS (32) slots behind the MFMAs (all of them in a row when the phase has none)
 // positions: B = per group (lo of three tiles, hi of three tiles), 18 + 2 idle; A = per step (b0 lo, b1 lo, b0 hi, b1 hi)
 DEV u32x4_t ns1_frag_b(const NsPtr& p, int q) {        // q < 18
   const int g = q / 6, j = q % 6;
@@ -136,10 +136,10 @@ DEV void ns1_phase(f32x4 (&y)[KB], f32x4 (&hA)[2], f32x4 (&hP)[2], const Split8&
     }
   };
   auto release = [&](auto Q) { load_pos(std::integral_constant<int, decltype(Q)::value + NP1>()); };
-  Prep2Ctx pc{hP[0], hP[1], fP, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+  Prep2Ctx pc{hP[0], hP[1], fP, k1, ik2, 0.f, 0.f, 0u};
   auto slot = [&](auto S) {
     prep2_slot<decltype(S)::value>(pc);
-    asm volatile("" : "+v"(pc.ta), "+v"(pc.tb), "+v"(pc.m0), "+v"(pc.m1), "+v"(pc.hp), "+v"(pc.lo), "+v"(pc.hi), "+v"(pc.out.t[0]), "+v"(pc.out.t[1]));
+    asm volatile("" : "+v"(pc.ta), "+v"(pc.tb), "+v"(pc.hp), "+v"(pc.lo), "+v"(pc.hi), "+v"(pc.out.t[0]), "+v"(pc.out.t[1]));
   };
   auto prep_after = [&](auto Mi) {
     constexpr int m = decltype(Mi)::value;

@@ -4,10 +4,10 @@
 //
 //     unit p:   y      += W2[pair p]^T  hf(p)                 B(p)      27 MFMAs, 18 fragments
 //               h(p+2)  = W1[:, pair p + 2]^T xf              A(p + 2)  30 MFMAs, 20 fragments
-//               hf(p+1) = split(swish(h(p + 1)))              prep      40 slots of <= 2 VALU instructions behind the MFMAs
+//               hf(p+1) = split(swish(h(p + 1)))              prep      32 slots of <= 2 VALU instructions behind the MFMAs
 //
 // (counts of the two-term operand scheme below; the first version of this file ran three bf16 terms: 54 / 60 MFMAs, 27 / 30
-// fragments, 48 slots.)  What the pairing buys over the round-2 kernels (profiles/r02_ring_experiments.md: 17 of tail_ff1's
+// fragments, 48 slots; 40 slots before the operand split took three instructions per value pair.)  What the pairing buys over the round-2 kernels (profiles/r02_ring_experiments.md: 17 of tail_ff1's
 // 85 us were activation / split VALU work that only the five W2 slabs of a chunk could carry):
 //   * the VALU work of a pair is spread over the MFMAs of a unit, uniformly;
 //   * 32 hidden features are exactly one 32-wide k-step of W2: no ninth tile paired with zeros;
@@ -307,7 +307,7 @@ DEV void pp_chain(f32x4 (&y)[KB], const Split8 (&xf)[KS32X], PpPool& pl, ST& st,
   pp_unit_A<DG>(h0, xf, pl, st);                                   // h(0)
   h1[0] = zero; h1[1] = zero;
   {
-    PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+    PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0u};
     pp_unit_AP<DG>(h1, xf, pc, pl, st);                            // h(1) ; hf(0)
   }
   constexpr int NF = P - 2;
@@ -315,29 +315,29 @@ DEV void pp_chain(f32x4 (&y)[KB], const Split8 (&xf)[KS32X], PpPool& pl, ST& st,
   for (int i = 0; i < NF / 2; ++i) {
     h0[0] = zero; h0[1] = zero;
     {
-      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0u};
       pp_unit_F<DG>(y, h0, xf, f0, pc, pl, st);                    // p even: B(p) with f0, A(p + 2) -> h0, h1 -> f1
     }
     h1[0] = zero; h1[1] = zero;
     {
-      PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+      PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0u};
       pp_unit_F<DG>(y, h1, xf, f1, pc, pl, st);                    // p odd: B(p) with f1, A(p + 2) -> h1, h0 -> f0
     }
   }
   if constexpr (NF & 1) {
     h0[0] = zero; h0[1] = zero;
     {
-      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0u};
       pp_unit_F<DG>(y, h0, xf, f0, pc, pl, st);
     }
     {
-      PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+      PpPrep pc{h0[0], h0[1], f0, k1, ik2, 0.f, 0.f, 0u};
       pp_unit_BP<DG>(y, f1, pc, pl, st);                           // B(P - 2) with f1 ; h(P - 1) -> f0
     }
     pp_unit_B<DG>(y, f0, pl, st);
   } else {
     {
-      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0.f, 0.f, 0u};
+      PpPrep pc{h1[0], h1[1], f1, k1, ik2, 0.f, 0.f, 0u};
       pp_unit_BP<DG>(y, f0, pc, pl, st);                           // B(P - 2) with f0 ; h(P - 1) -> f1
     }
     pp_unit_B<DG>(y, f1, pl, st);

@@ -7,24 +7,12 @@
 namespace {
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 struct Split8 { u32x4_t t[2]; };             // 8 k-slots x (hi, lo) fp16 terms
 
-DEV unsigned pp_pk_f16(float a, float b) {   // v_cvt_pk_f16_f32: both halves round to nearest
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, f16x2_t));
-}
-DEV float pp_f16_lo(unsigned p) { return (float)__builtin_bit_cast(f16x2_t, p).x; }
-DEV float pp_f16_hi(unsigned p) { return (float)__builtin_bit_cast(f16x2_t, p).y; }
-DEV Split8 split8(f32x4 lo, f32x4 hi) {      // the values are already in the operand's unit (x * sx)
-  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+DEV Split8 split8(f32x4 lo, f32x4 hi) {      // the values are already in the operand's unit (x * sx); common.h: split8_f16
   unsigned d0[4], d1[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    d0[k] = pp_pk_f16(v[2 * k], v[2 * k + 1]);
-    d1[k] = pp_pk_f16(v[2 * k] - pp_f16_lo(d0[k]), v[2 * k + 1] - pp_f16_hi(d0[k]));
-  }
+  split8_f16(lo, hi, d0, d1);
   Split8 f;
   f.t[0] = u32x4_t{d0[0], d0[1], d0[2], d0[3]};
   f.t[1] = u32x4_t{d1[0], d1[1], d1[2], d1[3]};
@@ -46,7 +34,7 @@ struct Prep2Ctx {
   f32x4 &lo, &hi;
   Split8& out;
   float k1, ik2;
-  float ta, tb, m0, m1;
+  float ta, tb;
   unsigned hp;
 };
 using PpPrep = Prep2Ctx;

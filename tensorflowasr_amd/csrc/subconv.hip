@@ -18,6 +18,8 @@
 #include "launch.h"
 #include "wstream.h"
 
+MI355_SCALAR_F32_BEGIN     // common.h: no packed f32 VALU in this file (measured faster: profiles/valu_diet_mi355x.md)
+
 namespace {
 
 constexpr int D = 144;
@@ -296,31 +298,11 @@ DEV SplitFrag split8(f32x4 lo, f32x4 hi) {
 // of six, the dropped a_lo b_lo and the representation errors are of the size of the terms the six-product bf16 scheme
 // drops (measured: the same distance from the fp64 oracle; Ootomo & Yokota's error-corrected fp16 GEMM without its
 // second accumulator, which the power-of-two scales make unnecessary here).
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-DEV unsigned pk_f16(float a, float b) {      // v_cvt_pk_f16_f32: both halves round to nearest
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, f16x2));
-}
-DEV SplitFrag split8h(f32x4 lo, f32x4 hi) {
-  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+DEV SplitFrag split8h(f32x4 lo, f32x4 hi) {     // the shared three-instruction split (common.h: split8_f16)
   SplitFrag f;
   unsigned d0[4], d1[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    d0[k] = pk_f16(v[2 * k], v[2 * k + 1]);
-    [[maybe_unused]] const f16x2 h = __builtin_bit_cast(f16x2, d0[k]);
-#if MI355ASR_CONV1_PK
-    // lo = fp16(v - hi) as v_fma_mixlo / mixhi_f16: the fp16 hi is read in place (op_sel picks the half), v - hi is formed in
-    // fp32 (exact) and rounded once into the destination half -- the same value as v_cvt_f32_f16 + v_sub_f32 + v_cvt_pk_f16_f32,
-    // two instructions per pair instead of five
-    unsigned lo2;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo2) : "v"(d0[k]), "v"(v[2 * k]));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo2) : "v"(d0[k]), "v"(v[2 * k + 1]));
-    d1[k] = lo2;
-#else
-    d1[k] = pk_f16(v[2 * k] - (float)h.x, v[2 * k + 1] - (float)h.y);
-#endif
-  }
+  split8_f16(lo, hi, d0, d1);
   f.t[0] = u32x4{d0[0], d0[1], d0[2], d0[3]};
   f.t[1] = u32x4{d1[0], d1[1], d1[2], d1[3]};
   f.t[2] = u32x4{0u, 0u, 0u, 0u};
@@ -671,10 +653,9 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
       const bool okr = tm >= 0 && tm < F;
       const float v0 = (okr && fm >= 0 && fm < a.NM) ? mbp[(size_t)tm * a.NM + fm] * sm : 0.f;
       const float v1 = (okr && fm + 1 >= 0 && fm + 1 < a.NM) ? mbp[(size_t)tm * a.NM + fm + 1] * sm : 0.f;
-      const unsigned h = pk_f16(v0, v1);
-      const f16x2 hh = __builtin_bit_cast(f16x2, h);
+      const unsigned h = split_hi_f16(v0, v1);
       mph[i] = h;
-      mph[rows * RD + i] = pk_f16(v0 - (float)hh.x, v1 - (float)hh.y);
+      mph[rows * RD + i] = split_lo_f16(h, v0, v1);
     }
     for (int i = threadIdx.x; i < C1_ZERO_ROWS * RD; i += SCT) mph[2 * rows * RD + i] = 0u;
   } else {
@@ -737,11 +718,10 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
       const int g = lane >> 4;
       const float* wp = p_w1 + 3 * min(g, 2) * D + 16 * cb + c;
       const float w0 = g < 3 ? wp[0] : 0.f, w1 = g < 3 ? wp[D] : 0.f, w2 = g < 3 ? wp[2 * D] : 0.f;
-      c1t.ph = pk_f16(w0, w1);
-      c1t.qh = pk_f16(w2, 0.f);
-      const f16x2 hp = __builtin_bit_cast(f16x2, c1t.ph), hq = __builtin_bit_cast(f16x2, c1t.qh);
-      c1t.pl = pk_f16(w0 - (float)hp.x, w1 - (float)hp.y);
-      c1t.ql = pk_f16(w2 - (float)hq.x, 0.f);
+      c1t.ph = split_hi_f16(w0, w1);
+      c1t.qh = split_hi_f16(w2, 0.f);
+      c1t.pl = split_lo_f16(c1t.ph, w0, w1);
+      c1t.ql = split_lo_f16(c1t.qh, w2, 0.f);
     } else {
 #pragma unroll
       for (int tp = 0; tp < 9; ++tp) w1r[tp] = *reinterpret_cast<const f32x4*>(p_w1 + tp * D + 16 * cb + g4);
@@ -1140,3 +1120,5 @@ int launch_subconv_split(int d, const SubConvArgs& a, hipStream_t s) {
 #endif
   return launch_split_d<0>(d, grid, a, RS, rows, s, rtn);
 }
+
+MI355_SCALAR_F32_END

@@ -34,7 +34,7 @@ import sys
 TERMS = int(os.environ.get("PP_TERMS", "2"))
 NPOOL = int(os.environ.get("PP_NPOOL", "10" if TERMS == 2 else "9"))     # fragment registers of a wave (the pool)
 SLOT = 10 * TERMS  # fragments (KB) per ring slot
-NPREP = 40 if TERMS == 2 else 48    # slots of the activation + split schedule (prep2_sched.inc / prep_sched.inc)
+NPREP = 32 if TERMS == 2 else 48    # slots of the activation + split schedule (prep2_sched.inc / prep_sched.inc)
 TOP = TERMS - 1    # highest term index
 # products of a fragment pair, by weight term: x terms it meets, smallest product first
 XT = {t: list(range(TOP - t, -1, -1)) for t in range(TERMS)}      # weight term t meets x terms TOP - t .. 0
