@@ -172,7 +172,8 @@ int run_subsampling(const mi355asr_model* m, const float* mel, int Bp, int F, fl
   same_pad(F, 3, m->dm.st1, &T1, &pt1);
   same_pad(T1, 3, 2, &T2, &pt2);
   SubConvArgs sa{};
-  sa.mel = mel; sa.out = sub; sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b; sa.w2s = m->c2_wsplit;
+  sa.mel = mel; sa.out = sub;
+  subconv_weights(m, sa, true);
   static const bool force_half = mi355_env("MI355ASR_SUBCONV_TERMS", -1) == 22;   // 22: also for caller-supplied features (tests)
   if (m->c2_whalf && (mel_bounded || force_half)) { sa.w2h = m->c2_whalf; sa.h_scale = m->c2_hscale; sa.h_wscale = m->c2_wscale; }
   // conv1 on the matrix pipe needs the frontend's own bound on |mel| for its fp16 planes: not for caller-supplied features
@@ -188,9 +189,7 @@ int run_subsampling(const mi355asr_model* m, const float* mel, int Bp, int F, fl
     { PROF(MI355ASR_K_SUBLINEAR); LAUNCH_TRY(launch_gemm16(m, E16_BIAS, false, lg, m->lin_wp, s), "subsampling linear"); }
     return 0;
   }
-  StreamGemmArgs lg{};
-  lg.x = sub; lg.y = out; lg.wp = m->lin_wp; lg.bias = m->lin_b;
-  lg.M = Bp * T2; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+  const StreamGemmArgs lg = sublinear_args(m, sub, out, Bp * T2);
   // MI355ASR_SUBLINEAR_SPLIT: 1 (default) = split-bf16 ring-DMA kernel (fused.hip) from 4096 rows, 2 = for any row
   // count, 0 = the fp32-MFMA stream_gemm_kernel
   static const int lin_split = (int)mi355_env("MI355ASR_SUBLINEAR_SPLIT", 1);
@@ -423,15 +422,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
     { PROF(MI355ASR_K_CTC_PROJECT); LAUNCH_TRY(launch_gemm16(m, E16_BIAS, false, pr, st.proj_wp, s), "ctc project"); }
   } else {
     // on its own: the same two-term stream through pp_sublinear_kernel (one chunk) -- bit-identical to the folded form --, else fp32 MFMA
-    StreamGemmArgs sp{};
-    sp.x = enc; sp.y = sc.xa; sp.M = M; sp.K = d; sp.NT = d / 16; sp.ldy = d; sp.n_valid = d;
-    PROF(MI355ASR_K_CTC_PROJECT);
-    if (!(st.proj_pp && m->cfg.gemm_dtype == 0 && launch_pp_sublinear(sp, st.proj_pp, st.proj_pp_sw, s) == 0)) {
-      GemmArgs pr{};
-      pr.x = enc; pr.y = sc.xa; pr.wp = st.proj_wp; pr.bias = st.proj_b;
-      pr.M = M; pr.NT = d / 16; pr.ldy = d; pr.n_valid = d; pr.eps = kLnEps;
-      LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "ctc project");
-    }
+    if (int rc = run_rows_project(m, st, enc, sc.xa, M, s, st.proj_pp && m->cfg.gemm_dtype == 0)) return rc;
   }
   // round 4: the class head rides in the last block's tail launch where pp_head_kernel would have run (run_class_head's conditions);
   // the launch does not read hd.x: the block's output never leaves the chip

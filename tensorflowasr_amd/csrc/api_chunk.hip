@@ -65,15 +65,7 @@ int run_stack(const mi355asr_model* m, const StackDev& st, const float* in, int 
     // (nothing here: the first block below computes the layer in front of it)
   } else if (st.proj_wp) {
     // on its own: the same two-term stream through pp_sublinear_kernel (bit-identical to the folded form), else fp32 MFMA
-    StreamGemmArgs sp{};
-    sp.x = in; sp.y = sc.xa; sp.M = M; sp.K = d; sp.NT = d / 16; sp.ldy = d; sp.n_valid = d;
-    PROF(MI355ASR_K_CTC_PROJECT);
-    if (!(st.proj_pp && m->cfg.gemm_dtype == 0 && !gemm16_for(m, (size_t)M) && launch_pp_sublinear(sp, st.proj_pp, st.proj_pp_sw, s) == 0)) {
-      GemmArgs pr{};
-      pr.x = in; pr.y = sc.xa; pr.wp = st.proj_wp; pr.bias = st.proj_b;
-      pr.M = M; pr.NT = d / 16; pr.ldy = d; pr.n_valid = d; pr.eps = kLnEps;
-      LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "project");
-    }
+    if (int rc = run_rows_project(m, st, in, sc.xa, M, s, st.proj_pp && m->cfg.gemm_dtype == 0 && !gemm16_for(m, (size_t)M))) return rc;
   } else if (in != sc.xa) {
     HIP_TRY(hipMemcpyAsync(sc.xa, in, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
   }
@@ -184,62 +176,34 @@ StreamPlan make_stream_plan(const mi355asr_model* m, int N, int F, int Fs) {
   return p;
 }
 
-// ChunkConformerBlock.stream_call (:381-388) for one stream: x (T rows) in sc.xa -> result in sc.xa.
+// ChunkConformerBlock.stream_call (:381-388) for one stream: x (T rows) in sc.xa -> result in sc.xa, on walk_block_rows (model.h).
 // new_mha [Cm+T, d] / new_cnn [Cc+T, d] receive [cache ; module input] (untrimmed).
 int run_block_stream(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int T,
                      const float* mha_cache, int Cm, const float* cnn_cache, int Cc, float* new_mha, float* new_cnn,
                      hipStream_t s) {
-  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size;
-  const int N = Cm + T, Nc = Cc + T;
+  const int d = m->cfg.dmodel;
   const size_t row = (size_t)d * 4;
-  // ff_module_1: xb = xa + fc * FFN(LN(xa))
-  Chain2Args f1{};
-  f1.x = sc.xa; f1.res = sc.xa; f1.y = sc.xb;
-  f1.ln_g = w.ff_ln_g[0]; f1.ln_b = w.ff_ln_b[0];
-  f1.w1p = w.ff_w1p[0]; f1.b1 = w.ff_b1[0]; f1.w2p = w.ff_w2p[0]; f1.b2 = w.ff_b2[0];
-  f1.scale = bo.fc; f1.eps = kLnEps; f1.M = T;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f1, s), "ff_module_1"); }
+  // [cache ; rows]: what the two layers in front of the token-mixing steps read
+  auto concat = [&](float* cat, const float* cache, int C, const float* rows) -> int {
+    if (C > 0) HIP_TRY(hipMemcpyAsync(cat, cache, C * row, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(cat + (size_t)C * d, rows, T * row, hipMemcpyDeviceToDevice, s));
+    return 0;
+  };
   // new_mha = [cache ; xb]; q/k/v of every row of it (the queries are its last T rows, :209-214)
-  if (Cm > 0) HIP_TRY(hipMemcpyAsync(new_mha, mha_cache, Cm * row, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(new_mha + (size_t)Cm * d, sc.xb, T * row, hipMemcpyDeviceToDevice, s));
-  GemmArgs q{};
-  q.x = new_mha; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.qkv_wp; q.bias = w.qkv_b;
-  q.M = N; q.NT = 3 * d / 16; q.ldy = 3 * d; q.n_valid = 3 * d; q.eps = kLnEps;
-  q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-  { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "qkv projection"); }
-  AttnArgs at{};
-  at.q = sc.qkv + (size_t)Cm * 3 * d; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ctx = sc.ctx;
-  at.B = 1; at.Tq = T; at.Tk = N; at.H = H; at.D = d; at.ldq = 3 * d; at.ldk = 3 * d;
-  at.win_front = bo.win_front; at.win_back = bo.win_back; at.q_off = Cm;
-  { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
-  GemmArgs op{};
-  op.x = sc.ctx; op.y = sc.xa; op.res = sc.xb; op.wp = w.out_wp; op.bias = w.out_b;
-  op.M = T; op.NT = d / 16; op.ldy = d; op.n_valid = d; op.eps = kLnEps;
-  { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, op, s), "attention out-projection"); }
+  auto qkv_rows = [&](RowsOf& r) -> int { r = RowsOf{new_mha, Cm + T}; return concat(new_mha, mha_cache, Cm, sc.xb); };
+  auto attend = [&]() -> int {
+    AttnArgs at = self_attn_args(m, bo, sc.qkv, sc.ctx, 1, T);
+    at.q = sc.qkv + (size_t)Cm * 3 * d; at.Tk = Cm + T; at.q_off = Cm;
+    PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(m->cfg.head_size, at, s), "attention");
+    return 0;
+  };
   // new_cnn = [cache ; xa]; the conv module runs over all of it, its last T rows are kept (:297-306)
-  if (Cc > 0) HIP_TRY(hipMemcpyAsync(new_cnn, cnn_cache, Cc * row, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(new_cnn + (size_t)Cc * d, sc.xa, T * row, hipMemcpyDeviceToDevice, s));
-  GemmArgs g{};
-  g.x = new_cnn; g.y = sc.u; g.ln_g = w.cv_ln_g; g.ln_b = w.cv_ln_b; g.wp = w.pw1_wp; g.bias = w.pw1_b;
-  g.M = Nc; g.NT = 2 * d / 16; g.ldy = d; g.n_valid = d; g.eps = kLnEps;
-  { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, g, s), "pw_conv_1 + GLU"); }
-  DwArgs dwa{};
-  dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = 1; dwa.T = Nc; dwa.D = d;
-  dwa.pad_left = bo.causal ? bo.ksz - 1 : (bo.ksz - 1) / 2;
-  { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(bo.ksz, dwa, s), "depthwise conv"); }
-  Chain2Args cv{};
-  cv.x = sc.dw + (size_t)Cc * d; cv.res = sc.xa; cv.y = sc.xb;
-  cv.w1p = w.pc_w1p; cv.b1 = w.pc_b1; cv.aff_s = w.bn_s; cv.aff_t = w.bn_t; cv.w2p = w.pw2_wp; cv.b2 = w.pw2_b;
-  cv.scale = 1.0f; cv.eps = kLnEps; cv.M = T;
-  { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, cv, s), "conv module tail"); }
-  Chain2Args f2{};
-  f2.x = sc.xb; f2.res = sc.xb; f2.y = sc.xa;
-  f2.ln_g = w.ff_ln_g[1]; f2.ln_b = w.ff_ln_b[1];
-  f2.w1p = w.ff_w1p[1]; f2.b1 = w.ff_b1[1]; f2.w2p = w.ff_w2p[1]; f2.b2 = w.ff_b2[1];
-  f2.fln_g = w.ln_g; f2.fln_b = w.ln_b;
-  f2.scale = bo.fc; f2.eps = kLnEps; f2.M = T;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f2, s), "ff_module_2 + LayerNorm"); }
-  return 0;
+  auto glu_rows = [&](RowsOf& r) -> int { r = RowsOf{new_cnn, Cc + T}; return concat(new_cnn, cnn_cache, Cc, sc.xa); };
+  auto depthwise = [&]() -> int {
+    PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(bo.ksz, dw_args(m, w, bo, sc.u, sc.dw, 1, Cc + T), s), "depthwise conv");
+    return 0;
+  };
+  return walk_block_rows(m, w, bo, sc, T, nullptr, s, qkv_rows, attend, glu_rows, depthwise, (size_t)Cc);
 }
 
 // mel frames of a wav buffer / rows after the two VALID stride-2 convs over [sub cache ; last chunk_num mel frames]
@@ -328,16 +292,14 @@ int chunk_predict(mi355asr_model* m, const float* wav, bool ragged, const int32_
     unsigned* melmax = (m->mel_band && m->c2_whalf && m->c1_l1 > 0.f) ? (unsigned*)(ws + p.pmax) : nullptr;
     if ((rc = run_valid_mel(m, wav, B, L, g.F, (float*)(ws + p.logp), (float*)(ws + p.pmax), mel, &melmax, s, -1, f_len))) return rc;
     SubConvArgs sa{};
-    sa.mel = mel; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
-    sa.w2s = m->c2_wsplit;
+    sa.mel = mel; sa.out = (float*)(ws + p.sub);
+    subconv_weights(m, sa, true);
     static const bool three = mi355_env("MI355ASR_SUBCONV_TERMS", -1) == 3;
     if (melmax && !three) { sa.w2h = m->c2_whalf; sa.h_wscale = m->c2_wscale; sa.h_melmax = melmax; sa.h_l1 = m->c1_l1; sa.h_bmax = m->c1_bmax; sa.c1_wscale = m->c1_wscale; }
     sa.B = B; sa.F = g.F; sa.NM = c.n_mels; sa.T1 = g.T1; sa.F1 = m->dm.F1; sa.T2 = T; sa.F2 = m->dm.F2;
     sa.st1 = 2; sa.pt1 = 4; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
     { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (valid)"); }
-    StreamGemmArgs lg{};
-    lg.x = sa.out; lg.y = sc.xa; lg.wp = m->lin_wp; lg.bias = m->lin_b;
-    lg.M = B * T; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+    const StreamGemmArgs lg = sublinear_args(m, sa.out, sc.xa, B * T);
     // round 4: the Dense rides in the encoder's first ff_module_1 + qkv launch when both run on the two-term stream and
     // nobody asked for the front's output (as encoder_impl in api.hip)
     if (!outs->front_out && !m->c_enc.proj_wp && !m->c_enc.blocks.empty() && m->lin_wsplit && lg.M >= 4096 && m->lin_pp &&
@@ -347,8 +309,8 @@ int chunk_predict(mi355asr_model* m, const float* wav, bool ragged, const int32_
       dense_deferred = true;
     } else {
       PROF(MI355ASR_K_SUBLINEAR);
-      // the split-bf16 ring-DMA Dense from 4096 rows on (as run_subsampling in api.hip), else the fp32-MFMA stream kernel
-      // (round 4: the two-term stream with a scale per token and 144-wide chunk first, as run_subsampling in api.hip)
+      // the two-term stream (a scale per token and 144-wide chunk), then the split-bf16 ring-DMA Dense, from 4096 rows on,
+      // else the fp32-MFMA stream kernel
       if (!(m->lin_wsplit && lg.M >= 4096 && ((m->lin_pp && launch_pp_sublinear(lg, m->lin_pp, m->lin_pp_sw, s) == 0) ||
                                               launch_sublinear_split(lg, m->lin_wsplit, s) == 0)))
         LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear");
@@ -599,13 +561,12 @@ int mi355asr_chunk_front_stream(mi355asr_model* m, const float* wav, int32_t Lw,
   if (Tout < 1) return 0;
   // pad 2/2 on the mel axis only, two VALID 3x3 stride-2 convs, last Tout frames, Dense (:77-89)
   SubConvArgs sa{};
-  sa.mel = new_sub; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+  sa.mel = new_sub; sa.out = (float*)(ws + p.sub);
+  subconv_weights(m, sa, false);
   sa.B = 1; sa.F = S + nf; sa.NM = c.n_mels; sa.T1 = T1; sa.F1 = m->dm.F1; sa.T2 = T2; sa.F2 = m->dm.F2;
   sa.st1 = 2; sa.pt1 = 0; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
   { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (stream)"); }
-  StreamGemmArgs lg{};
-  lg.x = sa.out + (size_t)(T2 - Tout) * m->dm.F2 * d; lg.y = front_out; lg.wp = m->lin_wp; lg.bias = m->lin_b;
-  lg.M = Tout; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+  const StreamGemmArgs lg = sublinear_args(m, sa.out + (size_t)(T2 - Tout) * m->dm.F2 * d, front_out, Tout);
   { PROF(MI355ASR_K_SUBLINEAR); LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear"); }
   return 0;
 }
@@ -630,10 +591,7 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
   hipStream_t s = (hipStream_t)stream;
   Scratch sc = make_scratch(p, ws);
   if (st->proj_wp) {
-    GemmArgs pr{};
-    pr.x = x; pr.y = sc.xa; pr.wp = st->proj_wp; pr.bias = st->proj_b;
-    pr.M = T; pr.NT = d / 16; pr.ldy = d; pr.n_valid = d; pr.eps = kLnEps;
-    { PROF(MI355ASR_K_CTC_PROJECT); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "project"); }
+    if (int rc = run_rows_project(m, *st, x, sc.xa, T, s)) return rc;
   } else {
     HIP_TRY(hipMemcpyAsync(sc.xa, x, (size_t)T * d * 4, hipMemcpyDeviceToDevice, s));
   }
@@ -646,8 +604,7 @@ int mi355asr_chunk_stack_stream(mi355asr_model* m, int32_t stack, const float* x
   }
   HIP_TRY(hipMemcpyAsync(hidden, sc.xa, (size_t)T * d * 4, hipMemcpyDeviceToDevice, s));
   if (st->fc_wp && (logits || amax)) {
-    GemmArgs hd = head_args(*st, sc.xa, T, logits, amax ? amax : (int32_t*)(ws + p.amax));
-    { PROF(MI355ASR_K_CTC_HEAD); LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "fully_connected"); }
+    if (int rc = run_rows_head(m, *st, sc.xa, T, logits, amax ? amax : (int32_t*)(ws + p.amax), s)) return rc;
   }
   return 0;
 }
@@ -743,69 +700,33 @@ CsPlan cs_plan(const mi355asr_model* m, const CsLayout& L, int n) {
 
 size_t cs_state_bytes(const CsLayout& L, int n_streams) { return ((size_t)n_streams * L.slot_words + (size_t)n_streams) * 4; }
 
-// One stack over the n TP padded rows in sc.xa (result there too): the row-wise layers on every row, attention and depthwise conv
-// per stream on its T[i] real rows against its caches.  blk0 = index of the stack's first block in the state layout.
+// One stack over the n TP padded rows in sc.xa (result there too): walk_block_rows (model.h) on every row, attention and depthwise
+// conv per stream on its T[i] real rows against its caches.  blk0 = index of the stack's first block in the state layout.
 int cs_run_stack(const mi355asr_model* m, const StackDev& st, const CsLayout& L, int blk0, float* state, const int32_t* slots,
                  int n, int TP, const int32_t* T, const int32_t* A, Scratch& sc, hipStream_t s) {
-  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size;
-  const int M = n * TP;
+  const int d = m->cfg.dmodel;
   const BlockOpts& bo = st.opts;
   for (size_t i = 0; i < st.blocks.size(); ++i) {
     const BlockDev& w = st.blocks[i];
-    const size_t koff = L.blk[blk0 + i], ring = (size_t)bo.win_front * d;
-    Chain2Args f1{};
-    f1.x = sc.xa; f1.res = sc.xa; f1.y = sc.xb;
-    f1.ln_g = w.ff_ln_g[0]; f1.ln_b = w.ff_ln_b[0];
-    f1.w1p = w.ff_w1p[0]; f1.b1 = w.ff_b1[0]; f1.w2p = w.ff_w2p[0]; f1.b2 = w.ff_b2[0];
-    f1.scale = bo.fc; f1.eps = kLnEps; f1.M = M;
-    { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f1, s), "ff_module_1"); }
-    GemmArgs q{};
-    q.x = sc.xb; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.qkv_wp; q.bias = w.qkv_b;
-    q.M = M; q.NT = 3 * d / 16; q.ldy = 3 * d; q.n_valid = 3 * d; q.eps = kLnEps;
-    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "qkv projection"); }
-    CsAttnArgs at{};
-    at.qkv = sc.qkv; at.ctx = sc.ctx; at.state = state; at.slot_words = L.slot_words; at.meta_off = L.meta(blk0 + (int)i);
-    at.k_off = koff; at.v_off = koff + ring; at.slots = slots; at.T = T; at.A = A;
-    at.n = n; at.TP = TP; at.H = H; at.wf = bo.win_front; at.wb = bo.win_back;
-    { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_cs_attn(hs, at, s), "stream attention"); }
-    GemmArgs op{};
-    op.x = sc.ctx; op.y = sc.xa; op.res = sc.xb; op.wp = w.out_wp; op.bias = w.out_b;
-    op.M = M; op.NT = d / 16; op.ldy = d; op.n_valid = d; op.eps = kLnEps;
-    { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, op, s), "attention out-projection"); }
-    GemmArgs g{};
-    g.x = sc.xa; g.y = sc.u; g.ln_g = w.cv_ln_g; g.ln_b = w.cv_ln_b; g.wp = w.pw1_wp; g.bias = w.pw1_b;
-    g.M = M; g.NT = 2 * d / 16; g.ldy = d; g.n_valid = d; g.eps = kLnEps;
-    { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, g, s), "pw_conv_1 + GLU"); }
-    CsDwArgs dwa{};
-    dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.state = state; dwa.slot_words = L.slot_words;
-    dwa.meta_off = at.meta_off; dwa.g_off = koff + 2 * ring; dwa.slots = slots; dwa.T = T; dwa.A = A;
-    dwa.n = n; dwa.TP = TP; dwa.D = d; dwa.K = bo.ksz; dwa.wf = bo.win_front;
-    { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_cs_dwconv(dwa, s), "stream depthwise conv"); }
-    Chain2Args cv{};
-    cv.x = sc.dw; cv.res = sc.xa; cv.y = sc.xb;
-    cv.w1p = w.pc_w1p; cv.b1 = w.pc_b1; cv.aff_s = w.bn_s; cv.aff_t = w.bn_t; cv.w2p = w.pw2_wp; cv.b2 = w.pw2_b;
-    cv.scale = 1.0f; cv.eps = kLnEps; cv.M = M;
-    { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, cv, s), "conv module tail"); }
-    Chain2Args f2{};
-    f2.x = sc.xb; f2.res = sc.xb; f2.y = sc.xa;
-    f2.ln_g = w.ff_ln_g[1]; f2.ln_b = w.ff_ln_b[1];
-    f2.w1p = w.ff_w1p[1]; f2.b1 = w.ff_b1[1]; f2.w2p = w.ff_w2p[1]; f2.b2 = w.ff_b2[1];
-    f2.fln_g = w.ln_g; f2.fln_b = w.ln_b;
-    f2.scale = bo.fc; f2.eps = kLnEps; f2.M = M;
-    { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f2, s), "ff_module_2 + LayerNorm"); }
+    const size_t koff = L.blk[blk0 + i], ring = (size_t)bo.win_front * d, meta = L.meta(blk0 + (int)i);
+    auto attend = [&]() -> int {
+      CsAttnArgs at{};
+      at.qkv = sc.qkv; at.ctx = sc.ctx; at.state = state; at.slot_words = L.slot_words; at.meta_off = meta;
+      at.k_off = koff; at.v_off = koff + ring; at.slots = slots; at.T = T; at.A = A;
+      at.n = n; at.TP = TP; at.H = m->cfg.num_heads; at.wf = bo.win_front; at.wb = bo.win_back;
+      PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_cs_attn(m->cfg.head_size, at, s), "stream attention");
+      return 0;
+    };
+    auto depthwise = [&]() -> int {
+      CsDwArgs dwa{};
+      dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.state = state; dwa.slot_words = L.slot_words;
+      dwa.meta_off = meta; dwa.g_off = koff + 2 * ring; dwa.slots = slots; dwa.T = T; dwa.A = A;
+      dwa.n = n; dwa.TP = TP; dwa.D = d; dwa.K = bo.ksz; dwa.wf = bo.win_front;
+      PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_cs_dwconv(dwa, s), "stream depthwise conv");
+      return 0;
+    };
+    if (int rc = walk_block_rows(m, w, bo, sc, n * TP, nullptr, s, own_rows, attend, own_rows, depthwise)) return rc;
   }
-  return 0;
-}
-
-// Dense(d -> d) of a stack with a projection: x -> sc.xa
-int cs_project(const mi355asr_model* m, const StackDev& st, const float* x, int M, Scratch& sc, hipStream_t s) {
-  const int d = m->cfg.dmodel;
-  GemmArgs pr{};
-  pr.x = x; pr.y = sc.xa; pr.wp = st.proj_wp; pr.bias = st.proj_b;
-  pr.M = M; pr.NT = d / 16; pr.ldy = d; pr.n_valid = d; pr.eps = kLnEps;
-  PROF(MI355ASR_K_CTC_PROJECT);
-  LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, pr, s), "project");
   return 0;
 }
 
@@ -905,28 +826,23 @@ int mi355asr_chunk_streams_step(mi355asr_model* m, void* state_dev, int32_t n_st
   const int rows = L.S + F, T1 = (rows - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1;
   if (T2 != TP) return fail(MI355ASR_EINVAL, "batched streams: the front yields %d rows per packet, expected %d", T2, TP);
   SubConvArgs sa{};
-  sa.mel = su.new_sub; sa.out = (float*)(ws + p.sub); sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+  sa.mel = su.new_sub; sa.out = (float*)(ws + p.sub);
+  subconv_weights(m, sa, false);
   sa.B = n; sa.F = rows; sa.NM = c.n_mels; sa.T1 = T1; sa.F1 = m->dm.F1; sa.T2 = T2; sa.F2 = m->dm.F2;
   sa.st1 = 2; sa.pt1 = 0; sa.pf1 = 2; sa.pt2 = 0; sa.pf2 = 0;
   { PROF(MI355ASR_K_SUBCONV); LAUNCH_TRY(launch_subconv(d, sa, s), "conv subsampling (streams)"); }
-  StreamGemmArgs lg{};
-  lg.x = sa.out; lg.y = sc.xa; lg.wp = m->lin_wp; lg.bias = m->lin_b;
-  lg.M = n * TP; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+  const StreamGemmArgs lg = sublinear_args(m, sa.out, sc.xa, n * TP);
   { PROF(MI355ASR_K_SUBLINEAR); LAUNCH_TRY(launch_stream_gemm(d, lg, s), "subsampling linear"); }
   // ---- encoder, phone picker (win_back 0: every row is valid, nothing waits)
   const auto& cc = m->ccfg;
   int blk = 0;
   if (int rc = cs_run_stack(m, m->c_enc, L, blk, state, slots, n, TP, nullptr, nullptr, sc, s)) return rc;
   blk += cc.enc_num_blocks;
-  if (int rc = cs_project(m, m->c_picker, sc.xa, n * TP, sc, s)) return rc;
+  if (int rc = run_rows_project(m, m->c_picker, sc.xa, sc.xa, n * TP, s)) return rc;
   if (int rc = cs_run_stack(m, m->c_picker, L, blk, state, slots, n, TP, nullptr, nullptr, sc, s)) return rc;
   blk += cc.picker_num_blocks;
   int32_t* amax_p = outs->phone_argmax ? outs->phone_argmax : (int32_t*)(ws + p.amax_p);
-  {
-    GemmArgs hd = head_args(m->c_picker, sc.xa, n * TP, outs->phone_logits, amax_p);
-    PROF(MI355ASR_K_CTC_HEAD);
-    LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "phone fully_connected");
-  }
+  if (int rc = run_rows_head(m, m->c_picker, sc.xa, n * TP, outs->phone_logits, amax_p, s)) return rc;
   float* hid = (float*)(ws + p.hid);
   HIP_TRY(hipMemcpyAsync(hid, sc.xa, (size_t)n * TP * d * 4, hipMemcpyDeviceToDevice, s));
   if (outs->picker_hidden) HIP_TRY(hipMemcpyAsync(outs->picker_hidden, sc.xa, (size_t)n * TP * d * 4, hipMemcpyDeviceToDevice, s));
@@ -946,15 +862,10 @@ int mi355asr_chunk_streams_step(mi355asr_model* m, void* state_dev, int32_t n_st
   ca.helped = sc.xa; ca.dec_in = dec_in; ca.state = state; ca.slot_words = L.slot_words; ca.hdr_off = L.hdr; ca.carry_off = L.carry;
   ca.slots = slots; ca.Td = Td; ca.Vd = Vd; ca.n = n; ca.TP = TP; ca.TPd = TPd; ca.D = d;
   LAUNCH_TRY(launch_cs_carry(ca, s), "stream decoder input");
-  if (int rc = cs_project(m, m->c_decoder, dec_in, n * TPd, sc, s)) return rc;
+  if (int rc = run_rows_project(m, m->c_decoder, dec_in, sc.xa, n * TPd, s)) return rc;
   if (int rc = cs_run_stack(m, m->c_decoder, L, blk, state, slots, n, TPd, Td, Vd, sc, s)) return rc;
   int32_t* amax_t = outs->text_argmax ? outs->text_argmax : (int32_t*)(ws + p.amax_t);
-  {
-    GemmArgs hd = head_args(m->c_decoder, sc.xa, n * TPd, outs->text_logits, amax_t);
-    PROF(MI355ASR_K_CTC_HEAD);
-    LAUNCH_TRY(launch_gemm_rows(d, EPI_HEAD, false, hd, s), "text fully_connected");
-  }
-  return 0;
+  return run_rows_head(m, m->c_decoder, sc.xa, n * TPd, outs->text_logits, amax_t, s);
 }
 
 }  // extern "C"

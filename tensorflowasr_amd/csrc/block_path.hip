@@ -100,10 +100,115 @@ bool block_takes_pre(const mi355asr_model* m, const BlockDev& w, size_t M) {
   return m->cfg.dmodel == 144 && sw.fused && !gemm16_for(m, M) && w.pp_ff1 && w.ff1_slabs && sw.pp && sw.pp_pre;
 }
 
+// ---- the arguments of a block's layers and token-mixing steps: every walker below, and those of api_chunk.hip, fill them here
+// FFModule i: y = x + fc * FFN(LN(x)), behind ff_module_2 also the block's final LayerNorm
+Chain2Args ff_module_args(const BlockDev& w, const BlockOpts& bo, int i, const float* x, float* y, int M, bool block_ln) {
+  Chain2Args a{};
+  a.x = x; a.res = x; a.y = y;
+  a.ln_g = w.ff_ln_g[i]; a.ln_b = w.ff_ln_b[i];
+  a.w1p = w.ff_w1p[i]; a.b1 = w.ff_b1[i]; a.w2p = w.ff_w2p[i]; a.b2 = w.ff_b2[i];
+  if (block_ln) { a.fln_g = w.ln_g; a.fln_b = w.ln_b; }
+  a.scale = bo.fc; a.eps = kLnEps; a.M = M;
+  return a;
+}
+// y = res + pw2( swish( BN( dw Wpc + bpc ) ) ) + b2
+Chain2Args conv_tail_args(const BlockDev& w, const float* dw, const float* res, float* y, int M) {
+  Chain2Args a{};
+  a.x = dw; a.res = res; a.y = y;
+  a.w1p = w.pc_w1p; a.b1 = w.pc_b1; a.aff_s = w.bn_s; a.aff_t = w.bn_t; a.w2p = w.pw2_wp; a.b2 = w.pw2_b;
+  a.scale = 1.0f; a.eps = kLnEps; a.M = M;
+  return a;
+}
+// a gemm_rows layer of `wide` x dmodel columns of which the first `kept` x dmodel are stored, densely; ln_g: LayerNorm in front
+static GemmArgs rows_layer_args(const mi355asr_model* m, const float* x, float* y, const float* wp, const float* bias, int M, int wide,
+                                int kept, const float* ln_g = nullptr, const float* ln_b = nullptr, bool qscale = false) {
+  const int d = m->cfg.dmodel;
+  GemmArgs g{};
+  g.x = x; g.y = y; g.ln_g = ln_g; g.ln_b = ln_b; g.wp = wp; g.bias = bias;
+  g.M = M; g.NT = wide * d / 16; g.ldy = kept * d; g.n_valid = kept * d; g.eps = kLnEps;
+  if (qscale) { g.qscale = 1.0f / std::sqrt((float)m->cfg.head_size); g.qtiles = d / 16; }   // q pre-scaled by 1 / sqrt(hs)
+  return g;
+}
+// qkv = LN(x) Wqkv
+GemmArgs qkv_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* qkv, int M) {
+  return rows_layer_args(m, x, qkv, w.qkv_wp, w.qkv_b, M, 3, 3, w.att_ln_g, w.att_ln_b, true);
+}
+// the Translator's RBlock: q = LN(x) Wq  [M, d] ; [k | v] = enc [Wk | Wv]  [B * T_enc, 2 d]  (qkv_b: 3 d zeros, no bias)
+GemmArgs cross_q_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* q, int M) {
+  return rows_layer_args(m, x, q, w.xq_wp, w.qkv_b, M, 1, 1, w.att_ln_g, w.att_ln_b, true);
+}
+GemmArgs cross_kv_args(const mi355asr_model* m, const BlockDev& w, const CrossAttn& c, int B) {
+  return rows_layer_args(m, c.enc, c.kv, w.xkv_wp, w.qkv_b, B * c.T_enc, 2, 2);
+}
+// y = res + ctx Wo + bo
+GemmArgs attn_out_args(const mi355asr_model* m, const BlockDev& w, const float* ctx, const float* res, float* y, int M) {
+  GemmArgs g = rows_layer_args(m, ctx, y, w.out_wp, w.out_b, M, 1, 1);
+  g.res = res;
+  return g;
+}
+// u = GLU(LN(x) Wpw1 + b)
+GemmArgs glu_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* u, int M) {
+  return rows_layer_args(m, x, u, w.pw1_wp, w.pw1_b, M, 2, 1, w.cv_ln_g, w.cv_ln_b);
+}
+DwArgs dw_args(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, const float* u, float* y, int B, int T) {
+  DwArgs a{};
+  a.u = u; a.y = y; a.wd = w.dw_w; a.B = B; a.T = T; a.D = m->cfg.dmodel;
+  // Keras 'same', stride 1: total k-1, before = (k-1)//2 ; 'causal': all k-1 on the left
+  a.pad_left = bo.causal ? bo.ksz - 1 : (bo.ksz - 1) / 2;
+  return a;
+}
+static AttnArgs attn_args_base(const mi355asr_model* m, const BlockOpts& bo, float* ctx, int B, int T) {
+  AttnArgs at{};
+  at.ctx = ctx; at.B = B; at.Tq = T; at.H = m->cfg.num_heads; at.D = m->cfg.dmodel;
+  at.win_front = bo.win_front; at.win_back = bo.win_back;
+  return at;
+}
+AttnArgs self_attn_args(const mi355asr_model* m, const BlockOpts& bo, const float* qkv, float* ctx, int B, int T) {
+  const int d = m->cfg.dmodel;
+  AttnArgs at = attn_args_base(m, bo, ctx, B, T);
+  at.q = qkv; at.k = qkv + d; at.v = qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
+  return at;
+}
+AttnArgs cross_attn_args(const mi355asr_model* m, const BlockOpts& bo, const float* q, int ldq, const CrossAttn& c, float* ctx, int B, int T) {
+  const int d = m->cfg.dmodel;
+  AttnArgs at = attn_args_base(m, bo, ctx, B, T);
+  at.q = q; at.ldq = ldq; at.k = c.kv; at.v = c.kv + d; at.ldk = 2 * d; at.Tk = c.T_enc;
+  return at;
+}
+
+// ---- stack-level launches on the rows kernels
+int run_rows_project(const mi355asr_model* m, const StackDev& st, const float* x, float* y, int M, hipStream_t s, bool try_pp) {
+  const int d = m->cfg.dmodel;
+  PROF(MI355ASR_K_CTC_PROJECT);
+  if (try_pp) {
+    StreamGemmArgs sp{};
+    sp.x = x; sp.y = y; sp.M = M; sp.K = d; sp.NT = d / 16; sp.ldy = d; sp.n_valid = d;
+    if (launch_pp_sublinear(sp, st.proj_pp, st.proj_pp_sw, s) == 0) return 0;
+  }
+  LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, rows_layer_args(m, x, y, st.proj_wp, st.proj_b, M, 1, 1), s), "project");
+  return 0;
+}
+int run_rows_head(const mi355asr_model* m, const StackDev& st, const float* x, int M, float* logits, int32_t* argmax, hipStream_t s) {
+  PROF(MI355ASR_K_CTC_HEAD);
+  LAUNCH_TRY(launch_gemm_rows(m->cfg.dmodel, EPI_HEAD, false, head_args(st, x, M, logits, argmax), s), "fully_connected");
+  return 0;
+}
+void subconv_weights(const mi355asr_model* m, SubConvArgs& sa, bool split) {
+  sa.w1 = m->c1_w; sa.b1 = m->c1_b; sa.w2p = m->c2_wp; sa.b2 = m->c2_b;
+  if (split) sa.w2s = m->c2_wsplit;
+}
+StreamGemmArgs sublinear_args(const mi355asr_model* m, const float* x, float* y, int M) {
+  const int d = m->cfg.dmodel;
+  StreamGemmArgs lg{};
+  lg.x = x; lg.y = y; lg.wp = m->lin_wp; lg.bias = m->lin_b;
+  lg.M = M; lg.K = m->dm.F2 * d; lg.NT = d / 16; lg.ldy = d; lg.n_valid = d;
+  return lg;
+}
+
 // one launch per dense layer (bf16.hip: bf16 or fp32 operands); LayerNorm / softmax / activations / depthwise conv in fp32
 static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int B, int T,
                             float* out, hipStream_t s, const CrossAttn* cross) {
-  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size, ksz = bo.ksz, M = B * T;
+  const int d = m->cfg.dmodel, hs = m->cfg.head_size, ksz = bo.ksz, M = B * T;
   const float fc = bo.fc;
   auto g16 = [&](const float* x, int ldx, int K, const float* wp, const float* bias, int NT, float* y, int ldy) {
     Gemm16Args g{};
@@ -118,10 +223,8 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
   const bool chain256 = m->cfg.gemm_dtype == 1 && d == 256 && block_switches().chain256 && !cross && cr[0] && cr[1] && cr[2] && cr[3] && cr[4] && cr[5];
   auto ffn = [&](int i, const float* x, float* y, const float* fg, const float* fb) -> int {
     if (chain256) {
-      Chain2Args ca{};
-      ca.x = x; ca.res = x; ca.y = y; ca.ln_g = w.ff_ln_g[i]; ca.ln_b = w.ff_ln_b[i];
-      ca.w1p = cr[2 * i]; ca.b1 = w.ff_b1[i]; ca.w2p = cr[2 * i + 1]; ca.b2 = w.ff_b2[i];
-      ca.fln_g = fg; ca.fln_b = fb; ca.scale = fc; ca.eps = kLnEps; ca.M = M;
+      Chain2Args ca = ff_module_args(w, bo, i, x, y, M, fg != nullptr);
+      ca.w1p = cr[2 * i]; ca.w2p = cr[2 * i + 1];
       PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain256_bf16(0, ca, s), "ff module");
       return 0;
     }
@@ -135,9 +238,7 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
   };
   int rc = ffn(0, sc.xa, sc.xb, nullptr, nullptr);
   if (rc) return rc;
-  AttnArgs at{};
-  at.ctx = sc.ctx; at.B = B; at.Tq = T; at.H = H; at.D = d;
-  at.win_front = bo.win_front; at.win_back = bo.win_back;
+  AttnArgs at = cross ? cross_attn_args(m, bo, sc.qkv, d, *cross, sc.ctx, B, T) : self_attn_args(m, bo, sc.qkv, sc.ctx, B, T);
   if (cross) {
     // RBlock: q = (LN(xb + PE) Wq) / sqrt(hs) ; [k | v] = enc [Wk | Wv]
     AddPeArgs pa{sc.xb, cross->pe, sc.u, B, T, d};
@@ -148,12 +249,10 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
     Gemm16Args kv = g16(cross->enc, d, d, w.xkv_wp, w.qkv_b, 2 * d / 16, cross->kv, 2 * d);
     kv.M = B * cross->T_enc;
     { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm16(m, E16_BIAS, false, kv, w.xkv_wp, s), "cross-attention key/value projection"); }
-    at.q = sc.qkv; at.ldq = d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc;
   } else {
     Gemm16Args q = g16(sc.xb, d, d, w.qkv_wp, w.qkv_b, 3 * d / 16, sc.qkv, 3 * d);
     q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
     { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm16(m, E16_QKV, true, q, w.qkv_wp, s), "qkv"); }
-    at.q = sc.qkv; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
     at.h2_sq = w.att_h2[0]; at.h2_sk = w.att_h2[1]; at.h2_sv = w.att_h2[2];      // q / k / v are the block's own projections (0: no bound known)
   }
   if (bo.t_len) {
@@ -171,15 +270,12 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
   Gemm16Args gl = g16(sc.xa, d, d, w.pw1_wp, w.pw1_b, 2 * d / 16, sc.u, d);
   gl.ln_g = w.cv_ln_g; gl.ln_b = w.cv_ln_b; gl.n_valid = d;
   { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm16(m, E16_GLU, true, gl, w.pw1_wp, s), "pw_conv_1 + GLU"); }
-  DwArgs dwa{};
-  dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-  dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
+  DwArgs dwa = dw_args(m, w, bo, sc.u, sc.dw, B, T);
   dwa.t_len = bo.t_len;
   { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
   if (chain256) {
-    Chain2Args ca{};
-    ca.x = sc.dw; ca.res = sc.xa; ca.y = sc.xb; ca.w1p = cr[4]; ca.b1 = w.pc_b1; ca.aff_s = w.bn_s; ca.aff_t = w.bn_t;
-    ca.w2p = cr[5]; ca.b2 = w.pw2_b; ca.scale = 1.0f; ca.eps = kLnEps; ca.M = M;
+    Chain2Args ca = conv_tail_args(w, sc.dw, sc.xa, sc.xb, M);
+    ca.w1p = cr[4]; ca.w2p = cr[5];
     { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain256_bf16(1, ca, s), "conv module tail"); }
     return ffn(1, sc.xb, out ? out : sc.xa, w.ln_g, w.ln_b);
   }
@@ -192,75 +288,32 @@ static int run_block_layers(const mi355asr_model* m, const BlockDev& w, const Bl
   return ffn(1, sc.xb, out ? out : sc.xa, w.ln_g, w.ln_b);
 }
 
-// MI355ASR_FUSED=0 (and the Translator's RBlock under MI355ASR_PP=0): one fp32-MFMA launch per layer or pair of layers
+// MI355ASR_FUSED=0 (and the Translator's RBlock under MI355ASR_PP=0): walk_block_rows (model.h) with attention and depthwise
+// conv over the B x T rows
 static int run_block_rows(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int B, int T,
                           float* out, hipStream_t s, const CrossAttn* cross) {
-  const int d = m->cfg.dmodel, H = m->cfg.num_heads, hs = m->cfg.head_size, ksz = bo.ksz, M = B * T;
-  const float fc = bo.fc;
-  // ff_module_1: xb = xa + fc * FFN(LN(xa))
-  Chain2Args f1{};
-  f1.x = sc.xa; f1.res = sc.xa; f1.y = sc.xb;
-  f1.ln_g = w.ff_ln_g[0]; f1.ln_b = w.ff_ln_b[0];
-  f1.w1p = w.ff_w1p[0]; f1.b1 = w.ff_b1[0]; f1.w2p = w.ff_w2p[0]; f1.b2 = w.ff_b2[0];
-  f1.scale = fc; f1.eps = kLnEps; f1.M = M;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f1, s), "ff_module_1"); }
-  AttnArgs at{};
-  at.ctx = sc.ctx; at.B = B; at.Tq = T; at.H = H; at.D = d;
-  at.win_front = bo.win_front; at.win_back = bo.win_back;
-  if (cross) {
-    // q = (LN(xb + PE) Wq) / sqrt(hs)  [M, d] ; [k | v] = enc [Wk | Wv]  [B*T_enc, 2d]
+  const int d = m->cfg.dmodel, hs = m->cfg.head_size, M = B * T;
+  auto qkv_rows = [&](RowsOf& r) -> int {
+    if (!cross) return 0;
+    // q of LN(xb + PE), k / v of the encoder output: made here, the walker's own qkv launch is left out
     AddPeArgs pa{sc.xb, cross->pe, sc.u, B, T, d};
     { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_add_pe(pa, s), "positional encoding"); }
-    GemmArgs q{};
-    q.x = sc.u; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.xq_wp; q.bias = w.qkv_b;
-    q.M = M; q.NT = d / 16; q.ldy = d; q.n_valid = d; q.eps = kLnEps;
-    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "cross-attention query projection"); }
-    GemmArgs kv{};
-    kv.x = cross->enc; kv.y = cross->kv; kv.wp = w.xkv_wp; kv.bias = w.qkv_b;   // qkv_b: 3d zeros (no bias)
-    kv.M = B * cross->T_enc; kv.NT = 2 * d / 16; kv.ldy = 2 * d; kv.n_valid = 2 * d; kv.eps = kLnEps;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, kv, s), "cross-attention key/value projection"); }
-    at.q = sc.qkv; at.ldq = d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc;
-  } else {
-    // mhsa: qkv = LN(xb) Wqkv (q pre-scaled)
-    GemmArgs q{};
-    q.x = sc.xb; q.y = sc.qkv; q.ln_g = w.att_ln_g; q.ln_b = w.att_ln_b; q.wp = w.qkv_wp; q.bias = w.qkv_b;
-    q.M = M; q.NT = 3 * d / 16; q.ldy = 3 * d; q.n_valid = 3 * d; q.eps = kLnEps;
-    q.qscale = 1.0f / std::sqrt((float)hs); q.qtiles = d / 16;
-    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, q, s), "qkv projection"); }
-    at.q = sc.qkv; at.k = sc.qkv + d; at.v = sc.qkv + 2 * d; at.ldq = 3 * d; at.ldk = 3 * d; at.Tk = T;
-  }
-  { PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention"); }
-  // xa = xb + ctx Wo + bo
-  GemmArgs op{};
-  op.x = sc.ctx; op.y = sc.xa; op.res = sc.xb; op.wp = w.out_wp; op.bias = w.out_b;
-  op.M = M; op.NT = d / 16; op.ldy = d; op.n_valid = d; op.eps = kLnEps;
-  { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, op, s), "attention out-projection"); }
-  // conv module: u = GLU(LN(xa) Wpw1 + b)
-  GemmArgs g{};
-  g.x = sc.xa; g.y = sc.u; g.ln_g = w.cv_ln_g; g.ln_b = w.cv_ln_b; g.wp = w.pw1_wp; g.bias = w.pw1_b;
-  g.M = M; g.NT = 2 * d / 16; g.ldy = d; g.n_valid = d; g.eps = kLnEps;
-  { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, g, s), "pw_conv_1 + GLU"); }
-  DwArgs dwa{};
-  dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-  // Keras 'same', stride 1: total k-1, before = (k-1)//2 ; 'causal': all k-1 on the left
-  dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
-  { PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(ksz, dwa, s), "depthwise conv"); }
-  // xb = xa + pw2( swish( BN( dw Wpc + bpc ) ) ) + b2
-  Chain2Args cv{};
-  cv.x = sc.dw; cv.res = sc.xa; cv.y = sc.xb;
-  cv.w1p = w.pc_w1p; cv.b1 = w.pc_b1; cv.aff_s = w.bn_s; cv.aff_t = w.bn_t; cv.w2p = w.pw2_wp; cv.b2 = w.pw2_b;
-  cv.scale = 1.0f; cv.eps = kLnEps; cv.M = M;
-  { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, cv, s), "conv module tail"); }
-  // ff_module_2 + block LayerNorm
-  Chain2Args f2{};
-  f2.x = sc.xb; f2.res = sc.xb; f2.y = out ? out : sc.xa;
-  f2.ln_g = w.ff_ln_g[1]; f2.ln_b = w.ff_ln_b[1];
-  f2.w1p = w.ff_w1p[1]; f2.b1 = w.ff_b1[1]; f2.w2p = w.ff_w2p[1]; f2.b2 = w.ff_b2[1];
-  f2.fln_g = w.ln_g; f2.fln_b = w.ln_b;
-  f2.scale = fc; f2.eps = kLnEps; f2.M = M;
-  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, f2, s), "ff_module_2 + LayerNorm"); }
-  return 0;
+    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, cross_q_args(m, w, sc.u, sc.qkv, M), s), "cross-attention query projection"); }
+    { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_BIAS, false, cross_kv_args(m, w, *cross, B), s), "cross-attention key/value projection"); }
+    r.x = nullptr;
+    return 0;
+  };
+  auto attend = [&]() -> int {
+    const AttnArgs at = cross ? cross_attn_args(m, bo, sc.qkv, d, *cross, sc.ctx, B, T) : self_attn_args(m, bo, sc.qkv, sc.ctx, B, T);
+    PROF(MI355ASR_K_ATTN); LAUNCH_TRY(launch_attention(hs, at, s), "attention");
+    return 0;
+  };
+  auto depthwise = [&]() -> int {
+    // (no t_len: run_block never sends a ragged batch to this walker)
+    PROF(MI355ASR_K_DWCONV); LAUNCH_TRY(launch_dwconv(bo.ksz, dw_args(m, w, bo, sc.u, sc.dw, B, T), s), "depthwise conv");
+    return 0;
+  };
+  return walk_block_rows(m, w, bo, sc, M, out, s, qkv_rows, attend, own_rows, depthwise);
 }
 
 // What run_block_fused launches for one block, decided before anything is launched.
@@ -289,12 +342,9 @@ static int run_block_fused(const mi355asr_model* m, const BlockDev& w, const Blo
   // the producer (this block's own ff_module_1 launch, or the previous block's tail) and the consumer agree without a flag
   // being passed between launches.  MI355ASR_QKV_HEAD_MAJOR=0: token-major rows as before.
   auto attn_args = [&](const BlockDev& bw, bool hm) {
-    AttnArgs at{};
-    at.q = sc.qkv; at.k = sc.qkv + (hm ? (size_t)M * d : (size_t)d); at.v = sc.qkv + (hm ? 2 * (size_t)M * d : 2 * (size_t)d); at.ctx = sc.ctx;
-    at.B = B; at.Tq = T; at.Tk = T; at.H = H; at.D = d; at.ldq = hm ? hs : 3 * d; at.ldk = hm ? hs : 3 * d;
-    at.win_front = bo.win_front; at.win_back = bo.win_back;
+    AttnArgs at = self_attn_args(m, bo, sc.qkv, sc.ctx, B, T);
+    if (hm) { at.k = sc.qkv + (size_t)M * d; at.v = sc.qkv + 2 * (size_t)M * d; at.ldq = hs; at.ldk = hs; at.head_major = 1; }
     at.h2_sq = bw.att_h2[0]; at.h2_sk = bw.att_h2[1]; at.h2_sv = bw.att_h2[2];      // q / k / v are the block's own projections
-    at.head_major = hm ? 1 : 0;
     at.k_len = bo.t_len;
     return at;
   };
@@ -321,10 +371,8 @@ static int run_block_fused(const mi355asr_model* m, const BlockDev& w, const Blo
   GemmArgs kv{};
   if (cross) {
     // [k | v] = enc [Wk | Wv]  [B * T_enc, 2 d]; q sits at columns 0..143 of the [M, 3 d] rows the ff_module_1 launch wrote
-    kv.x = cross->enc; kv.y = cross->kv; kv.wp = w.xkv_wp; kv.bias = w.qkv_b;   // qkv_b: 3d zeros (no bias)
-    kv.M = B * cross->T_enc; kv.NT = 2 * d / 16; kv.ldy = 2 * d; kv.n_valid = 2 * d; kv.eps = kLnEps;
-    at.q = sc.qkv; at.ldq = 3 * d; at.k = cross->kv; at.v = cross->kv + d; at.ldk = 2 * d; at.Tk = cross->T_enc; at.head_major = 0;
-    at.h2_sq = 0.f; at.h2_sk = 0.f; at.h2_sv = 0.f;          // no operand bounds for the encoder's rows: three exact terms
+    kv = cross_kv_args(m, w, *cross, B);
+    at = cross_attn_args(m, bo, sc.qkv, 3 * d, *cross, sc.ctx, B, T);   // no operand bounds for the encoder's rows: three exact terms
     at.k_len = bo.t_len ? cross->k_len : nullptr;             // ragged batches: the keys are the utterance's encoder frames
   }
   OutGluArgs k2{};
@@ -333,9 +381,7 @@ static int run_block_fused(const mi355asr_model* m, const BlockDev& w, const Blo
   k2.pw1_wp = w.pw1_wp; k2.pw1_b = w.pw1_b; k2.eps = kLnEps; k2.M = M;
   k2.og_slabs = w.og_slabs; k2.pp_slabs = w.pp_og; k2.pp_sw_out = w.pp_sw_out; k2.pp_sw_pw1 = w.pp_sw_pw1;
   k2.ns_out = w.ns_out; k2.ns_pw1 = w.ns_pw1;
-  DwArgs dwa{};
-  dwa.u = sc.u; dwa.y = sc.dw; dwa.wd = w.dw_w; dwa.B = B; dwa.T = T; dwa.D = d;
-  dwa.pad_left = bo.causal ? ksz - 1 : (ksz - 1) / 2;
+  DwArgs dwa = dw_args(m, w, bo, sc.u, sc.dw, B, T);
   dwa.t_len = bo.t_len;
   TailFf2Args k4{};
   k4.dw = sc.dw; k4.x2 = sc.xa; k4.y = out ? out : sc.xb;

@@ -411,6 +411,64 @@ inline GemmArgs head_args(const StackDev& st, const float* x, int M, float* logi
   hd.argmax_out = argmax;
   return hd;
 }
+// ... that head on gemm_rows<EPI_HEAD>, and a stack's Dense(d -> d) in front of its blocks on gemm_rows<EPI_BIAS> (x -> y;
+// try_pp: first as the stack's two-term stream through pp_sublinear_kernel, one chunk, where that launcher takes the shape)
+int run_rows_head(const mi355asr_model* m, const StackDev& st, const float* x, int M, float* logits, int32_t* argmax, hipStream_t s);
+int run_rows_project(const mi355asr_model* m, const StackDev& st, const float* x, float* y, int M, hipStream_t s, bool try_pp = false);
+// The subsampling front: the conv weights of the handle (split: with conv2's split-bf16 fragments, which select the
+// split-operand kernel) and the Dense behind the convs.  Which Dense kernel runs is the caller's policy: run_subsampling
+// (api.hip) reads MI355ASR_SUBLINEAR_SPLIT and has the small-batch and the layer-at-a-time kernels; chunk_predict
+// (api_chunk.hip) takes the two-term / split-bf16 streams from 4096 rows and never the small-batch kernel; the two
+// streaming fronts (api_chunk.hip) always take launch_stream_gemm.
+void subconv_weights(const mi355asr_model* m, SubConvArgs& sa, bool split);
+StreamGemmArgs sublinear_args(const mi355asr_model* m, const float* x, float* y, int M);
+
+// The arguments of the block's layers and token-mixing steps, for every walker of a block (block_path.hip)
+Chain2Args ff_module_args(const BlockDev& w, const BlockOpts& bo, int i, const float* x, float* y, int M, bool block_ln = false);
+Chain2Args conv_tail_args(const BlockDev& w, const float* dw, const float* res, float* y, int M);
+GemmArgs qkv_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* qkv, int M);
+GemmArgs cross_q_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* q, int M);
+GemmArgs cross_kv_args(const mi355asr_model* m, const BlockDev& w, const CrossAttn& c, int B);
+GemmArgs attn_out_args(const mi355asr_model* m, const BlockDev& w, const float* ctx, const float* res, float* y, int M);
+GemmArgs glu_args(const mi355asr_model* m, const BlockDev& w, const float* x, float* u, int M);
+DwArgs dw_args(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, const float* u, float* y, int B, int T);   // no t_len
+AttnArgs self_attn_args(const mi355asr_model* m, const BlockOpts& bo, const float* qkv, float* ctx, int B, int T);      // token-major rows, no operand bounds
+AttnArgs cross_attn_args(const mi355asr_model* m, const BlockOpts& bo, const float* q, int ldq, const CrossAttn& c, float* ctx, int B, int T);
+
+// The unfused fp32 block, one fp32-MFMA launch per layer or pair of layers over the M rows in sc.xa (result in `out`, or in
+// sc.xa), for its three callers: run_block_rows (block_path.hip: B x T rows, the Translator's cross block), run_block_stream
+// (api_chunk.hip: one stream against [cache ; new] rows) and cs_run_stack (api_chunk.hip: many streams against their rings).
+// Theirs are the two token-mixing steps and the rows the layer in front of each reads:
+//   qkv_rows(r) / glu_rows(r): r is preset to the block's own rows (sc.xb / sc.xa, M); a caller with caches stages
+//     [cache ; new] and names it, a caller that makes q / k / v itself clears r.x
+//   attend(): sc.qkv -> sc.ctx under MI355ASR_K_ATTN;  depthwise(): sc.u -> sc.dw under MI355ASR_K_DWCONV, the conv tail
+//     reading sc.dw from row tail_row on.  (Callables, not std::function: nothing is allocated per block.)
+struct RowsOf { const float* x; int M; };
+inline int own_rows(RowsOf&) { return 0; }
+template <class QkvRows, class Attend, class GluRows, class Depthwise>
+int walk_block_rows(const mi355asr_model* m, const BlockDev& w, const BlockOpts& bo, Scratch& sc, int M, float* out, hipStream_t s,
+                    QkvRows&& qkv_rows, Attend&& attend, GluRows&& glu_rows, Depthwise&& depthwise, size_t tail_row = 0) {
+  const int d = m->cfg.dmodel;
+  // ff_module_1: xb = xa + fc * FFN(LN(xa))
+  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, ff_module_args(w, bo, 0, sc.xa, sc.xb, M), s), "ff_module_1"); }
+  // mhsa: qkv = LN(rows) Wqkv (q pre-scaled)
+  RowsOf r{sc.xb, M};
+  if (int rc = qkv_rows(r)) return rc;
+  if (r.x) { PROF(MI355ASR_K_QKV); LAUNCH_TRY(launch_gemm_rows(d, EPI_QKV, true, qkv_args(m, w, r.x, sc.qkv, r.M), s), "qkv projection"); }
+  if (int rc = attend()) return rc;
+  // xa = xb + ctx Wo + bo
+  { PROF(MI355ASR_K_ATTN_OUT); LAUNCH_TRY(launch_gemm_rows(d, EPI_RESIDUAL, false, attn_out_args(m, w, sc.ctx, sc.xb, sc.xa, M), s), "attention out-projection"); }
+  // conv module: u = GLU(LN(rows) Wpw1 + b)
+  r = RowsOf{sc.xa, M};
+  if (int rc = glu_rows(r)) return rc;
+  { PROF(MI355ASR_K_PW1_GLU); LAUNCH_TRY(launch_gemm_rows(d, EPI_GLU, true, glu_args(m, w, r.x, sc.u, r.M), s), "pw_conv_1 + GLU"); }
+  if (int rc = depthwise()) return rc;
+  // xb = xa + pw2( swish( BN( dw Wpc + bpc ) ) ) + b2
+  { PROF(MI355ASR_K_CONV_TAIL); LAUNCH_TRY(launch_chain2(d, 1, conv_tail_args(w, sc.dw + tail_row * d, sc.xa, sc.xb, M), s), "conv module tail"); }
+  // ff_module_2 + block LayerNorm
+  { PROF(MI355ASR_K_FFN); LAUNCH_TRY(launch_chain2(d, 0, ff_module_args(w, bo, 1, sc.xb, out ? out : sc.xa, M, true), s), "ff_module_2 + LayerNorm"); }
+  return 0;
+}
 
 // ---- the other handle kinds' weight packing ----------------------------------------------------------------------------------
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
