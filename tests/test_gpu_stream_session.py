@@ -3,6 +3,8 @@ per-stream histories), the device-side histories (mi355asr_stream_append / mi355
 streaming server, on the MI355X.
 
 Every comparison but one (named below) is exact (np.array_equal / ==): a ragged row is defined as the solo call's result.
+That definition compares GPU calls with GPU calls; the same two entry points meet the float64 oracle (and in the bf16 mode the
+rounding oracle), row by row and with a length on every boundary of attn64_class, in tests/test_gpu_ragged256_edges.py.
 
 Which batches can be compared with solo calls bit for bit.  Attention and the depthwise conv are the stages that look across
 rows, and in a ragged launch every utterance runs on the attention kernel its solo call takes (attn64_class), so they never
