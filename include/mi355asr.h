@@ -97,6 +97,10 @@ const char* mi355asr_version(void);
  * nearest even) on x_dev f32 [n], as bit patterns: hi_dev, lo_dev u16 [n].  Elements are split in pairs (2 i, 2 i + 1) as
  * the kernels do, so even and odd positions take the two halves of the packed instructions.  Asynchronous on `stream`. */
 int mi355asr_test_split_f16(const float* x_dev, int64_t n, uint16_t* hi_dev, uint16_t* lo_dev, void* stream);
+/* Test hook: the exact three-term bf16 operand split every three-term kernel applies (each term the truncated high half of what
+ * the terms before it left: x = t0 + t1 + t2) on x_dev f32 [n], as bit patterns: t0_dev, t1_dev, t2_dev u16 [n].  Elements are
+ * split in pairs (2 i, 2 i + 1) as the kernels pack them; an odd n splits the last element alone.  Asynchronous on `stream`. */
+int mi355asr_test_split_bf16(const float* x_dev, int64_t n, uint16_t* t0_dev, uint16_t* t1_dev, uint16_t* t2_dev, void* stream);
 
 /* replaces: ConformerEncoder(...)/CTCDecoder(...) construction, test_asr.py:28-75 */
 int mi355asr_create(const mi355asr_config* cfg, mi355asr_model** out);

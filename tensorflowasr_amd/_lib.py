@@ -74,6 +74,7 @@ SIGNATURES = {
     "mi355asr_last_error": (ctypes.c_char_p, []),
     "mi355asr_version": (ctypes.c_char_p, []),
     "mi355asr_test_split_f16": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P]),
+    "mi355asr_test_split_bf16": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, _P]),
     "mi355asr_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(_P)]),
     "mi355asr_destroy": (ctypes.c_int, [_P]),
     "mi355asr_load_weight": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _I, ctypes.POINTER(ctypes.c_int64)]),

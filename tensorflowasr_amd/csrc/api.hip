@@ -1,6 +1,7 @@
 // libmi355asr.so host side: model object, workspace planning and the launch sequences behind the ConformerCTC / CTCDecoder
 // entry points of the C ABI declared in include/mi355asr.h.  (Weights: weights.hip; which kernels run a block: block_path.hip.)
 #include "common.h"
+#include "mfma_ops.h"
 #include "model.h"
 
 namespace mi355 {
@@ -459,7 +460,7 @@ int ctc_impl(mi355asr_model* m, const float* enc, int B, int T, const Plan& p, c
 // =======================================================================================================
 thread_local int mi355asr_last_scheme = SCHEME_F32;   // launch.h: note_scheme
 
-// mi355asr_test_split_f16: the shared two-term operand split (common.h) on an array, pair by pair as the kernels apply it --
+// mi355asr_test_split_f16: the shared two-term operand split (common.h: split_hi_f16 / split_lo_f16) on an array, pair by pair as the kernels apply it --
 // element 2 i goes through the low half (v_fma_mixlo_f16), element 2 i + 1 through the high half (v_fma_mixhi_f16)
 __global__ void split_f16_probe_kernel(const float* __restrict__ x, int64_t n, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
   const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
@@ -474,6 +475,21 @@ __global__ void split_f16_probe_kernel(const float* __restrict__ x, int64_t n, u
     lo[i + 1] = (uint16_t)(l >> 16);
   }
 }
+// mi355asr_test_split_bf16: the shared exact three-term operand split (mfma_ops.h: split8) on an array, pair by pair -- elements
+// 2 i and 2 i + 1 are k-slots 0 and 1 of a fragment (the low and the high half of dword 0 of every term)
+__global__ void split_bf16_probe_kernel(const float* __restrict__ x, int64_t n, uint16_t* __restrict__ t0, uint16_t* __restrict__ t1,
+                                        uint16_t* __restrict__ t2) {
+  const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const bool two = i + 1 < n;
+  const Split8x3 f = split8(f32x4{x[i], two ? x[i + 1] : 0.f, 0.f, 0.f}, splat4(0.f));
+  uint16_t* const out[3] = {t0, t1, t2};
+#pragma unroll
+  for (int term = 0; term < 3; ++term) {
+    out[term][i] = (uint16_t)(f.t[term].x & 0xffffu);
+    if (two) out[term][i + 1] = (uint16_t)(f.t[term].x >> 16);
+  }
+}
 
 extern "C" {
 
@@ -486,6 +502,15 @@ int mi355asr_test_split_f16(const float* x_dev, int64_t n, uint16_t* hi_dev, uin
   const int64_t pairs = (n + 1) / 2;
   hipLaunchKernelGGL(split_f16_probe_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, n, hi_dev, lo_dev);
   return hipGetLastError() == hipSuccess ? MI355ASR_OK : fail(MI355ASR_EHIP, "test_split_f16: launch failed");
+}
+
+int mi355asr_test_split_bf16(const float* x_dev, int64_t n, uint16_t* t0_dev, uint16_t* t1_dev, uint16_t* t2_dev, void* stream) {
+  if (!x_dev || !t0_dev || !t1_dev || !t2_dev) return fail(MI355ASR_EINVAL, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(MI355ASR_EINVAL, "test_split_bf16: need 1 <= n <= 2^31 (got %lld)", (long long)n);
+  const int64_t pairs = (n + 1) / 2;
+  hipLaunchKernelGGL(split_bf16_probe_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, n, t0_dev, t1_dev,
+                     t2_dev);
+  return hipGetLastError() == hipSuccess ? MI355ASR_OK : fail(MI355ASR_EHIP, "test_split_bf16: launch failed");
 }
 
 int mi355asr_create(const mi355asr_config* cfg, mi355asr_model** out) {

@@ -21,79 +21,11 @@
 #include "common.h"
 #include "env.h"
 #include "launch.h"
+#include "mfma_ops.h"
 
 MI355_SCALAR_F32_BEGIN     // common.h: no packed f32 VALU in this file (measured faster: profiles/valu_diet_mi355x.md)
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-struct Split8 { u32x4_t t[3]; };
-
-DEV Split8 split8(f32x4 lo, f32x4 hi) {      // exact: x = t0 + t1 + t2 (truncation; the remainders are exact)
-  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  Split8 f;
-#pragma unroll
-  for (int term = 0; term < 3; ++term) {
-    unsigned d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * k]), a1 = __builtin_bit_cast(unsigned, v[2 * k + 1]);
-      d[k] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-      if (term < 2) {
-        v[2 * k] -= __builtin_bit_cast(float, a0 & 0xffff0000u);
-        v[2 * k + 1] -= __builtin_bit_cast(float, a1 & 0xffff0000u);
-      }
-    }
-    f.t[term] = u32x4_t{d[0], d[1], d[2], d[3]};
-  }
-  return f;
-}
-DEV f32x4 mma32(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-// c += A B with both operands split: the six term pairs with i + j <= 2, smallest first
-DEV f32x4 mma_split(const u32x4_t (&a)[3], const Split8& b, f32x4 c) {
-  c = mma32(a[2], b.t[0], c);
-  c = mma32(a[1], b.t[1], c);
-  c = mma32(a[0], b.t[2], c);
-  c = mma32(a[1], b.t[0], c);
-  c = mma32(a[0], b.t[1], c);
-  c = mma32(a[0], b.t[0], c);
-  return c;
-}
-
-// Two-term scheme (see subconv.hip / fused_pp.hip): hi + lo fp16 terms of values already multiplied by their power-of-two
-// scale, three products per fragment pair.  Split8::t[2] is unused then.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-DEV Split8 split8h(f32x4 lo, f32x4 hi) {     // the shared three-instruction split (common.h: split8_f16)
-  unsigned d0[4], d1[4];
-  split8_f16(lo, hi, d0, d1);
-  Split8 f;
-  f.t[0] = u32x4_t{d0[0], d0[1], d0[2], d0[3]};
-  f.t[1] = u32x4_t{d1[0], d1[1], d1[2], d1[3]};
-  f.t[2] = u32x4_t{0u, 0u, 0u, 0u};
-  return f;
-}
-DEV f32x4 mma32h(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-template <int TM>
-DEV Split8 split_tm(f32x4 lo, f32x4 hi) {
-  if constexpr (TM == 2) return split8h(lo, hi); else return split8(lo, hi);
-}
-// c += A B: TM = 3 the six bf16 term pairs, TM = 2 the three fp16 ones (lo x hi, hi x lo, hi x hi)
-template <int TM>
-DEV f32x4 mma_tm(const u32x4_t (&a)[3], const Split8& b, f32x4 c) {
-  if constexpr (TM == 2) {
-    c = mma32h(a[1], b.t[0], c);
-    c = mma32h(a[0], b.t[1], c);
-    c = mma32h(a[0], b.t[0], c);
-    return c;
-  } else {
-    return mma_split(a, b, c);
-  }
-}
 
 #ifndef MI355ASR_ATTN_DIAG
 #define MI355ASR_ATTN_DIAG 0
@@ -165,7 +97,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(AttnArgs a) {
   }
   if (skey >= T) { klo = splat4(0.f); khi = splat4(0.f); ktl = 0.f; }
   {
-    const Split8 kf = split_tm<TM>(klo * splat4(sk), khi * splat4(sk));
+    const Split8x3 kf = split_tm<TM>(klo * splat4(sk), khi * splat4(sk));
     Kf[0][wv][lane] = kf.t[0];
     Kf[1][wv][lane] = kf.t[1];
     if constexpr (TM == 3) Kf[2][wv][lane] = kf.t[2];
@@ -174,7 +106,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(AttnArgs a) {
   __syncthreads();                     // K fragments staged; the V rows are still in flight / in registers
   const bool active = qt * 16 < TQ;    // (waves without queries still stage their share of V)
   const int nkt = (T + 15) / 16;       // key tiles that hold at least one real key (uniform)
-  const Split8 qf = split_tm<TM>(qlo * splat4(LOG2E * sq), qhi * splat4(LOG2E * sq));
+  const Split8x3 qf = split_tm<TM>(qlo * splat4(LOG2E * sq), qhi * splat4(LOG2E * sq));
   const f32x4 inv_qk = splat4(1.0f / (sq * sk));                        // powers of two
 
   // ---- S^T = K Q^T: lane holds S^T[key = 16 kt + 4 g + j][query c] in log2 units
@@ -207,7 +139,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(AttnArgs a) {
     const int en = tid + it * ATH;
     if (en < NVE && !(ADG & 8)) {
       const f32x4 lo = {ve[it][0], ve[it][1], ve[it][2], ve[it][3]}, hi = {ve[it][4], ve[it][5], ve[it][6], ve[it][7]};
-      const Split8 vf = split_tm<TM>(lo * splat4(sv), hi * splat4(sv));
+      const Split8x3 vf = split_tm<TM>(lo * splat4(sv), hi * splat4(sv));
       u32x4_t* dst = &Vf[0][0][0][0] + en;                         // [t][s][ot][lane]: en = (s * OT + ot) * 64 + lane
       dst[0] = vf.t[0];
       dst[NVE] = vf.t[1];
@@ -252,7 +184,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(AttnArgs a) {
   for (int s = 0; s < NST; ++s) {
     if constexpr (ADG & 4) { o[0] += sc[2 * s]; o[1] += sc[2 * s + 1]; }
     else if (s < nst) {
-      const Split8 pf = split_tm<TM>(sc[2 * s] * splat4(SP), sc[2 * s + 1] * splat4(SP));
+      const Split8x3 pf = split_tm<TM>(sc[2 * s] * splat4(SP), sc[2 * s + 1] * splat4(SP));
 #pragma unroll
       for (int i = 0; i < OT; ++i) {
         const u32x4_t vf[3] = {Vf[0][s][i][lane], Vf[1][s][i][lane], Vf[TM - 1][s][i][lane]};
@@ -312,7 +244,7 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
   constexpr float LOG2E = 1.4426950408889634f;
   const f32x4 qlo = ldg4(qrow + 8 * g), qhi = ldg4(qrow + 8 * g + 4);
   const float qtl = qrow[32 + g] * (LOG2E * sq);
-  const Split8 qf = split_tm<TM>(qlo * splat4(LOG2E * sq), qhi * splat4(LOG2E * sq));
+  const Split8x3 qf = split_tm<TM>(qlo * splat4(LOG2E * sq), qhi * splat4(LOG2E * sq));
   const f32x4 inv_qk = splat4(1.0f / (sq * sk));
   const bool active = qt * 16 < TQ;
 
@@ -355,7 +287,7 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
     for (int it = 0; it < NKR; ++it) {
       const int en = tid + it * LTH;
       if (en < NKE) {
-        const Split8 kf = split_tm<TM>(klo[it] * splat4(sk), khi[it] * splat4(sk));
+        const Split8x3 kf = split_tm<TM>(klo[it] * splat4(sk), khi[it] * splat4(sk));
         (&Kf[0][0][0])[en] = kf.t[0];
         (&Kf[1][0][0])[en] = kf.t[1];
         if constexpr (TM == 3) (&Kf[2][0][0])[en] = kf.t[2];
@@ -367,7 +299,7 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
       const int en = tid + it * LTH;
       if (en < NVE) {
         const f32x4 lo = {ve[it][0], ve[it][1], ve[it][2], ve[it][3]}, hi = {ve[it][4], ve[it][5], ve[it][6], ve[it][7]};
-        const Split8 vf = split_tm<TM>(lo * splat4(sv), hi * splat4(sv));
+        const Split8x3 vf = split_tm<TM>(lo * splat4(sv), hi * splat4(sv));
         u32x4_t* dst = &Vf[0][0][0][0] + en;
         dst[0] = vf.t[0];
         dst[NVE] = vf.t[1];
@@ -443,7 +375,7 @@ __global__ __launch_bounds__(LW * 64) void attention_split_long_kernel(AttnArgs 
           for (int s4 = 0; s4 < HS2; ++s4) {
             const int s = hb * HS2 + s4;
             if (s < nst) {
-              const Split8 pf = split_tm<TM>(sc[2 * s4] * splat4(SP), sc[2 * s4 + 1] * splat4(SP));
+              const Split8x3 pf = split_tm<TM>(sc[2 * s4] * splat4(SP), sc[2 * s4 + 1] * splat4(SP));
 #pragma unroll
               for (int i = 0; i < OT; ++i) {
                 const u32x4_t vf[3] = {Vf[0][s][i][lane], Vf[1][s][i][lane], Vf[TM - 1][s][i][lane]};

@@ -21,26 +21,15 @@
 #include "common.h"
 #include "env.h"
 #include "launch.h"
+#include "mfma_ops.h"
 
 namespace {
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-struct Split2 { u32x4_t hi, lo; };
-
-DEV Split2 split8h(f32x4 lo, f32x4 hi) {      // eight values -> hi + lo fp16 terms (the values already carry their power-of-two scale)
-  unsigned d0[4], d1[4];
-  split8_f16(lo, hi, d0, d1);                 // the shared three-instruction split (common.h)
-  return Split2{u32x4_t{d0[0], d0[1], d0[2], d0[3]}, u32x4_t{d1[0], d1[1], d1[2], d1[3]}};
-}
-DEV f32x4 mma32h(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
 // c += A B with both operands split: lo x hi, hi x lo, hi x hi (smallest first)
-DEV f32x4 mma2(u32x4_t ah, u32x4_t al, const Split2& b, f32x4 c) {
-  c = mma32h(al, b.hi, c);
-  c = mma32h(ah, b.lo, c);
-  return mma32h(ah, b.hi, c);
+DEV f32x4 mma2(u32x4_t ah, u32x4_t al, const Split8x2& b, f32x4 c) {
+  c = mma32h(al, b.t[0], c);
+  c = mma32h(ah, b.t[1], c);
+  return mma32h(ah, b.t[0], c);
 }
 
 constexpr int HS = 64;
@@ -106,18 +95,18 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
   for (int it = 0; it < NKI; ++it) {
     const int en = tid + it * ATH;
     if (en < NKE) {
-      const Split2 f = split8h(kr[it][0] * splat4(sk), kr[it][1] * splat4(sk));
-      (&Kf[0][0][0][0])[en] = f.hi;                                      // [term][ks][kt][lane]: en = (ks NKT + kt) 64 + lane
-      (&Kf[1][0][0][0])[en] = f.lo;
+      const Split8x2 f = split8h(kr[it][0] * splat4(sk), kr[it][1] * splat4(sk));
+      (&Kf[0][0][0][0])[en] = f.t[0];                                      // [term][ks][kt][lane]: en = (ks NKT + kt) 64 + lane
+      (&Kf[1][0][0][0])[en] = f.t[1];
     }
   }
 #pragma unroll
   for (int it = 0; it < NVI; ++it) {
     const int en = tid + it * ATH;
     if (en < NVE) {
-      const Split2 f2 = split8h(f32x4{vr[it][0], vr[it][1], vr[it][2], vr[it][3]} * splat4(sv), f32x4{vr[it][4], vr[it][5], vr[it][6], vr[it][7]} * splat4(sv));
-      (&Vf[0][0][0][0])[en] = f2.hi;                                     // [term][s][ot][lane]: en = (s OT + ot) 64 + lane
-      (&Vf[1][0][0][0])[en] = f2.lo;
+      const Split8x2 f2 = split8h(f32x4{vr[it][0], vr[it][1], vr[it][2], vr[it][3]} * splat4(sv), f32x4{vr[it][4], vr[it][5], vr[it][6], vr[it][7]} * splat4(sv));
+      (&Vf[0][0][0][0])[en] = f2.t[0];                                     // [term][s][ot][lane]: en = (s OT + ot) 64 + lane
+      (&Vf[1][0][0][0])[en] = f2.t[1];
     }
   }
   __syncthreads();
@@ -128,7 +117,7 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
   for (int qt = blockIdx.x * MAXQT + wv; qt < min(nqt, (int)(blockIdx.x + 1) * MAXQT); qt += AW) {
     const int tq = qt * 16 + c;
     const float* qrow = a.q + ((size_t)b * TQA + min(tq, TQ - 1)) * a.ldq + h * HS;
-    Split2 qf[KS];
+    Split8x2 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
       qf[ks] = split8h(ldg4(qrow + 32 * ks + 8 * g) * splat4(LOG2E * sq), ldg4(qrow + 32 * ks + 8 * g + 4) * splat4(LOG2E * sq));
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(ATH) void attention_split64_kernel(AttnArgs a) {
 #pragma unroll
     for (int s = 0; s < NST; ++s) {
       if (s < nst) {
-        const Split2 pf = split8h(sc[2 * s] * splat4(SP), sc[2 * s + 1] * splat4(SP));
+        const Split8x2 pf = split8h(sc[2 * s] * splat4(SP), sc[2 * s + 1] * splat4(SP));
 #pragma unroll
         for (int i = 0; i < OT; ++i) o[i] = mma2(Vf[0][s][i][lane], Vf[1][s][i][lane], pf, o[i]);
       }

@@ -14,11 +14,11 @@
 #include "common.h"
 #include "env.h"
 #include "launch.h"
+#include "mfma_ops.h"
 
 namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 DEV s16x4 to_bf16x4(f32x4 v) {      // 2 x v_cvt_pk_bf16_f32 (round to nearest even)
@@ -389,11 +389,6 @@ void launch_layernorm_rows(float* y, const float* g, const float* b, int M, int 
 constexpr int C_NW = 8;         // waves per workgroup, two 16-column tiles of dmodel 256 each
 constexpr int C_KB = 16;        // 16-wide k-blocks of a row
 constexpr int C_BF = 8;         // weight fragments (1 KB: 16 bytes per lane) per batch
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-DEV f32x4 mfma32_bf16(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // Weights: the one-term slab-ring packs of gemm_ring.hip (api.hip: put_ring with ring_terms = 1) -- [N / 128 chunks][K / 32
 // steps][8 tiles][64 lanes][8 bf16], a lane's eight values of a 32-wide k-step being the two 16-blocks side by side, which is
 // how two accumulator-layout tiles (or two operand k-blocks) sit next to each other -- read straight from L2 with 16-byte
@@ -519,7 +514,7 @@ __global__ __launch_bounds__(C_NW * 64) void chain256_bf16_kernel(Chain2Args a) 
 #pragma unroll
         for (int i = 0; i < HWP; ++i)
 #pragma unroll
-          for (int rt = 0; rt < RT; ++rt) acc1[rt][i] = mfma32_bf16(wa[t % NBUF][u * HWP + i], xv[rt], acc1[rt][i]);
+          for (int rt = 0; rt < RT; ++rt) acc1[rt][i] = mma32(wa[t % NBUF][u * HWP + i], xv[rt], acc1[rt][i]);
       }
       if (r == NB1 - 1) {
         // the phase's hidden tiles -> LDS (a later phase: once every wave has read the previous one's), tile 2 p and 2 p + 1
@@ -542,7 +537,7 @@ __global__ __launch_bounds__(C_NW * 64) void chain256_bf16_kernel(Chain2Args a) 
         for (int rt = 0; rt < RT; ++rt) {
           const u32x4_t hv = hid[rt][(r - NB1) * 4 + u][lane];
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc2[rt][j] = mfma32_bf16(wa[t % NBUF][u * 2 + j], hv, acc2[rt][j]);
+          for (int j = 0; j < 2; ++j) acc2[rt][j] = mma32(wa[t % NBUF][u * 2 + j], hv, acc2[rt][j]);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -688,8 +683,8 @@ __global__ __launch_bounds__(C_NW * 64) void gemm256_bf16_kernel(Gemm16Args a, c
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
           const u32x4_t xv = xl[rt][st][lane];
-          acc[rt] = mfma32_bf16(wa[h][st], xv, acc[rt]);
-          if constexpr (GLU) accg[rt] = mfma32_bf16(wa[h][KS + st], xv, accg[rt]);
+          acc[rt] = mma32(wa[h][st], xv, acc[rt]);
+          if constexpr (GLU) accg[rt] = mma32(wa[h][KS + st], xv, accg[rt]);
         }
       }
       const int unit = (int)wave + C_NW * (i + h);

@@ -18,6 +18,12 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+// a 16-byte MFMA operand fragment (eight bf16 / fp16 k-slots) as the four dwords it is loaded, stored and packed as, and the views
+// the 16x16x32 builtins take
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 #define WAVE 64
 #define WAVES_PER_BLOCK 4

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "env.h"
 #include "launch.h"
+#include "mfma_ops.h"
 
 namespace {
 
@@ -180,64 +181,18 @@ __global__ __launch_bounds__(BLOCK_THREADS, 2) void fft_stft_kernel(FftStftArgs 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same factorisation on the bf16 matrix pipe (round 3): both DFT-32 stages as v_mfma_f32_16x16x32_bf16 over operands
 // split exactly into three bf16 terms (the six term pairs with i + j <= 2, smallest first: as accurate as the fp32 FMA chain,
-// see subconv.hip / leaf.hip).  Stage 1 is ONE 32-wide step (K = n1), stage 2 two (K = re | im of n2): 96 MFMAs of 16 cycles
+// mfma_ops.h).  Stage 1 is ONE 32-wide step (K = n1), stage 2 two (K = re | im of n2): 96 MFMAs of 16 cycles
 // per frame instead of 128 of 32 -- 1536 matrix-pipe cycles instead of 4096.  The k-slot order of a step (pack_split32:
 // slot j of lane group g <-> k = 16 (j >> 2) + 4 g + (j & 3)) is exactly the pair of float4 fragments the fp32 kernel feeds
 // to its two 16-wide k-blocks, so loads, window, twiddles, the LDS transpose and the epilogue are unchanged; the stage
 // matrices are split on the host (cos / sin of multiples of 2 pi / 32 in fp32, three terms hold every bit).
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-struct Split8 { u32x4_t t[3]; };
-DEV Split8 split8(f32x4 lo, f32x4 hi) {      // exact: x = t0 + t1 + t2 (truncation; the remainders are exact)
-  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  Split8 f;
-#pragma unroll
-  for (int term = 0; term < 3; ++term) {
-    unsigned d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * k]), a1 = __builtin_bit_cast(unsigned, v[2 * k + 1]);
-      d[k] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-      if (term < 2) {
-        v[2 * k] -= __builtin_bit_cast(float, a0 & 0xffff0000u);
-        v[2 * k + 1] -= __builtin_bit_cast(float, a1 & 0xffff0000u);
-      }
-    }
-    f.t[term] = u32x4_t{d[0], d[1], d[2], d[3]};
-  }
-  return f;
-}
-DEV f32x4 mma32(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 // Two-term scheme (TM = 2 below): the stage matrices (cos / sin: |w| <= 1) as hi + lo fp16 of w * 2^14,
 // an operand column (one n2 of stage 1, one k1 of stage 2: this lane's token, spread over the four lanes c, c + 16, c + 32,
 // c + 48) as hi + lo fp16 of the column times the power of two of its largest magnitude; three products per fragment pair.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 constexpr float kStageScale = 16384.f;
-DEV Split8 split8h(f32x4 lo, f32x4 hi) {     // the shared three-instruction split (common.h: split8_f16)
-  unsigned d0[4], d1[4];
-  split8_f16(lo, hi, d0, d1);
-  Split8 f;
-  f.t[0] = u32x4_t{d0[0], d0[1], d0[2], d0[3]};
-  f.t[1] = u32x4_t{d1[0], d1[1], d1[2], d1[3]};
-  f.t[2] = u32x4_t{0u, 0u, 0u, 0u};
-  return f;
-}
-DEV f32x4 mma32h(u32x4_t a, u32x4_t b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-// 2^k with m * 2^k in [2^13, 2^14), k in [-14, 100], and its reciprocal.  The scale only ever multiplies fp32 values
-// (operands before the split, accumulators after the MFMAs), so nothing ties it to fp16's range: columns of a quiet signal
-// (peak 1e-8) are normalised like any other and keep both fp16 terms normal.  Below 2^-87 (and for m = 0) k stays at 100.
-DEV float pow2_scale(float m) {
-  const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u);
-  return __builtin_bit_cast(float, (unsigned)(127 + min(100, max(-14, 140 - e))) << 23);
-}
-DEV float recip_pow2(float s) { return __builtin_bit_cast(float, 0x7f000000u - __builtin_bit_cast(unsigned, s)); }
-DEV float max8(f32x4 a, f32x4 b) {
-  return fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))), fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
-}
+// The column scale is mfma_ops.h: pow2_scale<100> -- it only ever multiplies fp32 values (operands before the split, accumulators
+// after the MFMAs), so columns of a quiet signal (peak 1e-8) are normalised like any other and keep both fp16 terms normal.  Below
+// 2^-87 (and for a zero column) k stays at 100.
 // reductions over the sixteen lanes of a row on the VALU (DPP row_ror): a __shfl_xor is a ds_bpermute, an LDS round trip in a
 // dependent chain -- eighteen of them per frame were ~2000 of the ~8800 cycles a wave spends on a frame
 template <int N> DEV float dpp_ror(float v) {
@@ -321,7 +276,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
   };
   const int L = a.L;
   // acc += W^T x over the six term pairs, smallest first, for NT tiles and two row tiles: MFMAs on one accumulator 2 NT apart
-  auto mma6 = [&](auto& acc, const auto& w, const Split8 (&x)[2], auto NT_T) {
+  auto mma6 = [&](auto& acc, const auto& w, const Split8x3 (&x)[2], auto NT_T) {
     constexpr int NT = decltype(NT_T)::value;
 #pragma unroll
     for (int ord = TM - 1; ord >= 0; --ord)
@@ -374,7 +329,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
           raw[rt][kb] = v;
         }
     }
-    Split8 xs[2];
+    Split8x3 xs[2];
     float un1[2];                              // two-term: 1 / (stage scale x column scale) of the stage-1 accumulators
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
@@ -382,9 +337,9 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) xf[kb] = raw[rt][kb] * tab(rt, kb, 0);
       if constexpr (TM == 2) {
-        const float sx = pow2_scale(col_max(max8(xf[0], xf[1])));
+        const float sx = pow2_scale<100>(col_max(max8(xf[0], xf[1])));
         un1[rt] = recip_pow2(sx * kStageScale);
-        xs[rt] = split8h(xf[0] * splat4(sx), xf[1] * splat4(sx));
+        xs[rt] = split_tm<2>(xf[0] * splat4(sx), xf[1] * splat4(sx));
       } else {
         un1[rt] = 1.f;
         xs[rt] = split8(xf[0], xf[1]);
@@ -443,14 +398,14 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
         const float* si = Lim + (16 * rt + c) * LDW + g4;
         yr[rt][0] = *reinterpret_cast<const f32x4*>(sr); yr[rt][1] = *reinterpret_cast<const f32x4*>(sr + 16);
         yi[rt][0] = *reinterpret_cast<const f32x4*>(si); yi[rt][1] = *reinterpret_cast<const f32x4*>(si + 16);
-        sy[rt] = pow2_scale(col_max(fmaxf(max8(yr[rt][0], yr[rt][1]), max8(yi[rt][0], yi[rt][1]))));
+        sy[rt] = pow2_scale<100>(col_max(fmaxf(max8(yr[rt][0], yr[rt][1]), max8(yi[rt][0], yi[rt][1]))));
       }
-      Split8 ys[2];
+      Split8x3 ys[2];
 #pragma unroll
-      for (int rt = 0; rt < 2; ++rt) ys[rt] = split8h(yr[rt][0] * splat4(sy[rt]), yr[rt][1] * splat4(sy[rt]));
+      for (int rt = 0; rt < 2; ++rt) ys[rt] = split_tm<2>(yr[rt][0] * splat4(sy[rt]), yr[rt][1] * splat4(sy[rt]));
       mma6(acc2, w2[0], ys, std::integral_constant<int, 2>{});
 #pragma unroll
-      for (int rt = 0; rt < 2; ++rt) ys[rt] = split8h(yi[rt][0] * splat4(sy[rt]), yi[rt][1] * splat4(sy[rt]));
+      for (int rt = 0; rt < 2; ++rt) ys[rt] = split_tm<2>(yi[rt][0] * splat4(sy[rt]), yi[rt][1] * splat4(sy[rt]));
       mma6(acc2, w2[1], ys, std::integral_constant<int, 2>{});
 #pragma unroll
       for (int rt = 0; rt < 2; ++rt) {
@@ -461,7 +416,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, (TM == 2 && MI355ASR_STFT_TABS_LDS) 
     } else {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        Split8 ys[2];
+        Split8x3 ys[2];
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
           const float* src = (st == 0 ? Lre : Lim) + (16 * rt + c) * LDW + g4;

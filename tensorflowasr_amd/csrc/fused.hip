@@ -17,55 +17,13 @@
 #include "env.h"
 #include "launch.h"
 #include "wstream.h"
+#include "block144.h"
+#include "mfma_ops.h"
 
 namespace {
 
-constexpr int D = 144;
-constexpr int KB = D / 16;   // 9
-
-struct WaveCtx {
-  int lane, g4, t, tok;
-  size_t row;
-  bool live;
-};
-DEV WaveCtx wave_ctx(int M) {
-  WaveCtx c;
-  c.lane = threadIdx.x & 63;
-  c.g4 = (c.lane >> 4) * 4;
-  c.t = c.lane & 15;
-  const int wid = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-  c.tok = wid * 16 + c.t;
-  c.live = c.tok < M;
-  c.row = (size_t)min(c.tok, M - 1) * D;     // waves past the end recompute the last token and store nothing
-  return c;
-}
-
-// the same, recomputed from an opaque copy of the thread index: long kernels call this again before their stores instead of
-// keeping the 64-bit row offset alive across the whole stream (it was the value the register allocator spilled)
-DEV WaveCtx wave_ctx_fresh(int M) {
-  unsigned tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  WaveCtx c;
-  c.lane = tid & 63;
-  c.g4 = (c.lane >> 4) * 4;
-  c.t = c.lane & 15;
-  const int wid = blockIdx.x * WAVES_PER_BLOCK + (int)(tid >> 6);
-  c.tok = wid * 16 + c.t;
-  c.live = c.tok < M;
-  c.row = (size_t)min(c.tok, M - 1) * D;
-  return c;
-}
-
-// LayerNorm with gamma / beta in LDS
-DEV void ln_lds(f32x4 (&xs)[KB], const float* ga, const float* be, int g4, float eps) {
-  float mean, rstd;
-  ln_stats<KB>(xs, eps, mean, rstd);
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) xs[kb] = (xs[kb] - splat4(mean)) * splat4(rstd) * lds4(ga, kb, g4) + lds4(be, kb, g4);
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// out_glu on the bf16 matrix pipe (fp32 operands as three bf16 terms, see subconv.hip / leaf.hip) with the weights
+// out_glu on the bf16 matrix pipe (fp32 operands as three bf16 terms, mfma_ops.h) with the weights
 // shared through LDS.  At 16 000 tokens there is one 16-token row tile per wave and one wave per SIMD, so the fp32
 // kernel above is bound by each wave's own MFMA chain (4 x 32 cycles per fragment); six bf16 MFMAs per 32 k-slots are
 // 2.7x faster, which a per-wave weight stream from L2 cannot feed -- the four waves of a workgroup read the fragments
@@ -75,33 +33,7 @@ DEV void ln_lds(f32x4 (&xs)[KB], const float* ga, const float* be, int g4, float
 // A lane's B operand for step t is the split of its two accumulator-layout float4 (blocks 2 t, 2 t + 1): the transposed
 // chain property of the fp32 kernels carries over.  Column tiles are processed in groups of three (fragments of the
 // next group are read from LDS during the 18 MFMAs of the current one; MFMAs on one accumulator are three apart).
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-struct Split8 { u32x4_t t[3]; };
-
-DEV Split8 split8(f32x4 lo, f32x4 hi) {      // exact: x = t0 + t1 + t2 (truncation, remainders are exact)
-  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  Split8 f;
-#pragma unroll
-  for (int term = 0; term < 3; ++term) {
-    unsigned d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * k]), a1 = __builtin_bit_cast(unsigned, v[2 * k + 1]);
-      d[k] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-      if (term < 2) {
-        v[2 * k] -= __builtin_bit_cast(float, a0 & 0xffff0000u);
-        v[2 * k + 1] -= __builtin_bit_cast(float, a1 & 0xffff0000u);
-      }
-    }
-    f.t[term] = u32x4_t{d[0], d[1], d[2], d[3]};
-  }
-  return f;
-}
-DEV void dma16(const u32x4_t* gsrc, u32x4_t* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
+using Split8 = Split8x3;                      // mfma_ops.h; the name prep_sched.inc uses
 
 constexpr int KS32X = 5;                      // 32-wide steps over K = 144
 
@@ -109,18 +41,7 @@ constexpr int KS32X = 5;                      // 32-wide steps over K = 144
 // fragments so that every thread issues exactly 7 DMAs per slab), fetched three slabs ahead into a ring of four LDS
 // slots by global_load_lds_dwordx4.  "Slab s + 1 has landed" is the counted wait vmcnt(14) -- valid as long as the
 // slab DMAs are the only vector-memory operations in flight (inputs are loaded before the stream starts, outputs are
-// stored after it ends).  The fragment reads are inline asm: the compiler would otherwise put vmcnt(0) in front of
-// every LDS read that may alias a pending DMA (it tracks LDS-DMA per LDS object; a ring indexed at run time is one
-// object), and the fence of __syncthreads() waits for all DMAs too -- hence also the bare s_barrier.
-// s_waitcnt vmcnt(PER * ahead) lgkmcnt(0) for a wave-uniform run-time `ahead` in [0, MAXA] (the count is an immediate)
-template <int PER, int MAXA>
-DEV void wait_dma_ahead(int ahead) {
-  static_for<0, MAXA + 1>([&](auto K) {
-    constexpr int k = decltype(K)::value, n = PER * k;
-    if (ahead == k) __builtin_amdgcn_s_waitcnt(0x0070 | (n & 15) | ((n >> 4) << 14));
-  });
-}
-
+// stored after it ends).  Reads and barriers: wstream.h (dma16, lds_read16, wait_dma_ahead).
 constexpr int SLB = 7 * BLOCK_THREADS;
 template <int RING>
 struct SlabStream {
@@ -161,36 +82,6 @@ struct SlabStream {
     rd = rd + 1 == RING ? 0 : rd + 1;
   }
 };
-
-// parameter stash in two phases: all global loads of a kernel first, then the LDS writes (stash() per array makes one
-// L2 round trip per array: load, wait, write)
-template <int N>
-struct StashRegs { float r[(N + BLOCK_THREADS - 1) / BLOCK_THREADS]; };
-template <int N>
-DEV StashRegs<N> stash_load(const float* __restrict__ src) {
-  StashRegs<N> s;
-#pragma unroll
-  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
-    const int idx = threadIdx.x + BLOCK_THREADS * k;
-    s.r[k] = idx < N ? src[idx] : 0.f;
-  }
-  return s;
-}
-template <int N>
-DEV void stash_store(float* dst, const StashRegs<N>& s) {
-#pragma unroll
-  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
-    const int idx = threadIdx.x + BLOCK_THREADS * k;
-    if (idx < N) dst[idx] = s.r[k];
-  }
-}
-
-template <int OFF>
-DEV u32x4_t lds_read16(unsigned addr) {
-  u32x4_t v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
 
 // acc[0..9) += W(slab)^T x: column tiles in groups of three, the fragments of the next group are requested before the
 // 18 MFMAs of the current one (LDS returns in order: lgkmcnt(9) = "everything but the nine newest reads")
@@ -765,7 +656,7 @@ __global__ __launch_bounds__(LD_THREADS) void head_ld_kernel(GemmArgs a, const u
 #pragma unroll
       for (int i = 0; i < KB; ++i) nb[i] = bias_of(g + 1, i);
     }
-    const WaveCtx e = wave_ctx_fresh(a.M);
+    const WaveCtx e = wave_ctx_fresh<false>(a.M);
     float* yrow = a.y ? a.y + (size_t)e.tok * a.ldy : nullptr;
 #pragma unroll
     for (int i = 0; i < KB; ++i) {
@@ -795,7 +686,7 @@ __global__ __launch_bounds__(LD_THREADS) void head_ld_kernel(GemmArgs a, const u
     const int oi = __shfl_xor(best_i, off);
     if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
   }
-  const WaveCtx e = wave_ctx_fresh(a.M);
+  const WaveCtx e = wave_ctx_fresh<false>(a.M);
   if (a.argmax_out && e.live && c.lane < 16) a.argmax_out[e.tok] = best_i;
   if (a.maxval_out && e.live && c.lane < 16) a.maxval_out[e.tok] = best_v;
 }

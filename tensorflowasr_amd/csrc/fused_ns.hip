@@ -32,8 +32,6 @@
 
 namespace {
 
-constexpr int D = 144;
-constexpr int KB = D / 16;      // 9
 constexpr int KS = 5;           // 32-wide steps over K = 144 (+ the bias row 144)
 
 #define NS_FENCE __builtin_amdgcn_sched_barrier(0)
@@ -45,28 +43,6 @@ constexpr int KS = 5;           // 32-wide steps over K = 144 (+ the bias row 14
 #endif
 #define NS1_STAMP(i) do { if constexpr ((NS_DIAG & 32) != 0) { if (blockIdx.x == 3 && blockIdx.y == 0) st1[i] = __builtin_readcyclecounter(); } } while (0)
 
-DEV f32x4 ns_mfma(u32x4_t w, u32x4_t x, f32x4 acc) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), acc, 0, 0, 0);
-}
-DEV float ns_row_max(const f32x4 (&xs)[KB]) {
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < KB; ++i)
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(xs[i].x), fabsf(xs[i].y))), fmaxf(fabsf(xs[i].z), fabsf(xs[i].w)));
-  return group_max(m);
-}
-struct NsTok { float sx, k1, ik2, s2, inv2; };
-DEV NsTok ns_chain_scales(const PpChainSc& c, float xmax) {      // fused_pp.hip: pp_chain_scales
-  NsTok t;
-  t.sx = pp_pow2_scale(xmax);
-  const float sh = pp_pow2_scale(fmaf(c.l1, xmax, c.bmax));
-  const float u1 = c.sw1 * t.sx;
-  t.k1 = -1.4426950408889634f * pp_recip_pow2(u1);
-  t.ik2 = u1 * pp_recip_pow2(sh);
-  t.s2 = c.sw2 * sh;
-  t.inv2 = pp_recip_pow2(t.s2);
-  return t;
-}
 // fragment pointers of a hidden pair, WAVE-UNIFORM (the lane is added as a 32-bit index at the load: scalar base + vector offset
 // instead of 64-bit address arithmetic per fragment): b = its W2 fragments [9][2][64], a = its W1 fragments [KS][NT1][2][64] at tile
 // 2 pair; lane = this lane's index
@@ -161,7 +137,7 @@ DEV void ns1_phase(f32x4 (&y)[KB], f32x4 (&hA)[2], f32x4 (&hP)[2], const Split8&
           constexpr int i = decltype(Ti)::value, tile = 3 * g + i;
           constexpr int m = (g * 3 + pr) * 3 + i;
           constexpr int q = 6 * g + (pr == 0 ? 0 : 3) + i;
-          y[tile] = ns_mfma(pool[q % NP1], pr == 1 ? fB.t[1] : fB.t[0], y[tile]);
+          y[tile] = mma32h(pool[q % NP1], pr == 1 ? fB.t[1] : fB.t[0], y[tile]);
           prep_after(std::integral_constant<int, m>());
           if constexpr (i == 2 && pr == 0) { release(std::integral_constant<int, 6 * g>()); release(std::integral_constant<int, 6 * g + 1>()); release(std::integral_constant<int, 6 * g + 2>()); }
           if constexpr (i == 2 && pr == 2) {
@@ -182,7 +158,7 @@ DEV void ns1_phase(f32x4 (&y)[KB], f32x4 (&hA)[2], f32x4 (&hP)[2], const Split8&
           constexpr int b = decltype(Bi)::value;
           constexpr int m = MB + (st * 3 + pr) * 2 + b;
           constexpr int q = NB + 4 * st + (pr == 0 ? 0 : 2) + b;
-          hA[b] = ns_mfma(pool[q % NP1], pr == 1 ? xf[st].t[1] : xf[st].t[0], hA[b]);
+          hA[b] = mma32h(pool[q % NP1], pr == 1 ? xf[st].t[1] : xf[st].t[0], hA[b]);
           prep_after(std::integral_constant<int, m>());
           if constexpr (b == 1 && pr == 0) { release(std::integral_constant<int, NB + 4 * st>()); release(std::integral_constant<int, NB + 4 * st + 1>()); }
           if constexpr (b == 1 && pr == 2) { release(std::integral_constant<int, NB + 4 * st + 2>()); release(std::integral_constant<int, NB + 4 * st + 3>()); }
@@ -258,7 +234,7 @@ DEV void ns1_plain3(f32x4 (&acc)[3], const u32x4_t* const (&wt)[3], int NT, cons
       constexpr int pr = decltype(Pi)::value;
       static_for<0, 3>([&](auto J) {
         constexpr int j = decltype(J)::value;
-        acc[j] = ns_mfma(pl[st % DP][(pr == 0 ? 0 : 3) + j], pr == 1 ? xf[st].t[1] : xf[st].t[0], acc[j]);
+        acc[j] = mma32h(pl[st % DP][(pr == 0 ? 0 : 3) + j], pr == 1 ? xf[st].t[1] : xf[st].t[0], acc[j]);
         if constexpr (st + DP < KS && j == 2) {
           if constexpr (pr == 0) { pl[st % DP][0] = frag(0, st + DP, 1); pl[st % DP][1] = frag(1, st + DP, 1); pl[st % DP][2] = frag(2, st + DP, 1); }
           if constexpr (pr == 2) { pl[st % DP][3] = frag(0, st + DP, 0); pl[st % DP][4] = frag(1, st + DP, 0); pl[st % DP][5] = frag(2, st + DP, 0); }
@@ -285,20 +261,6 @@ DEV Ns1Tile ns1_tile(int M, int T, int t) {
   r.row = (size_t)r.tok * D;
   return r;
 }
-DEV void ns1_split_rows(Split8 (&xf)[KS], const f32x4 (&xs)[KB], int g4, float sx) {       // fused_pp.hip: split_operand
-  const f32x4 s4 = splat4(sx);
-#pragma unroll
-  for (int s = 0; s < KS - 1; ++s) xf[s] = split8(xs[2 * s] * s4, xs[2 * s + 1] * s4);
-  f32x4 oh = splat4(0.f);
-  oh.x = g4 == 0 ? sx : 0.0f;
-  xf[KS - 1] = split8(xs[KB - 1] * s4, oh);
-}
-DEV void ns1_ln(f32x4 (&xs)[KB], const float* ga, const float* be, int g4, float eps) {      // parameters from the LDS stash
-  float mean, rstd;
-  ln_stats<KB>(xs, eps, mean, rstd);
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) xs[kb] = (xs[kb] - splat4(mean)) * splat4(rstd) * lds4(ga, kb, g4) + lds4(be, kb, g4);
-}
 // up to twelve 144-float vectors into L.par (null pointers are skipped); the caller's next __syncthreads() publishes them
 template <int NW, int N>
 DEV void ns1_stash(Ns1Lds<NW>& L, const float* const (&src)[N]) {
@@ -319,11 +281,11 @@ DEV void ns1_ff1_qkv(const Ff1QkvArgs& a, Ns1Lds<NW>& L, f32x4 (&xs)[KB], const 
     f32x4 r[KB];
 #pragma unroll
     for (int i = 0; i < KB; ++i) r[i] = lds4(L.par[2], i, g4) + splat4(inv_fc) * xs[i];
-    ns1_ln(xs, L.par[0], L.par[1], g4, a.eps);
-    const NsTok tk = ns_chain_scales(a.pp_sc, ns_row_max(xs));
+    ln_lds(xs, L.par[0], L.par[1], g4, a.eps);
+    const PpTok tk = pp_chain_scales(a.pp_sc, row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = w == 0 ? r[i] * splat4(tk.s2) : splat4(0.f);       // residual + bias ride in wave 0's partial
-    ns1_split_rows(xf, xs, g4, tk.sx);
+    split_operand(xf, xs, g4, tk.sx);
     ns1_chain<18, NW>(y, xf, pool, reinterpret_cast<const u32x4_t*>(a.ns_w1), reinterpret_cast<const u32x4_t*>(a.ns_w2), w, lane, tk.k1, tk.ik2);
     ns1_allreduce<NW>(y, L, w, lane);
 #pragma unroll
@@ -333,10 +295,10 @@ DEV void ns1_ff1_qkv(const Ff1QkvArgs& a, Ns1Lds<NW>& L, f32x4 (&xs)[KB], const 
 #pragma unroll
     for (int i = 0; i < KB; ++i) stg4(a.x1 + tl.row + 16 * i + g4, y[i]);
   }
-  ns1_ln(xs, L.par[3], L.par[4], g4, a.eps);
-  const float sx = pp_pow2_scale(ns_row_max(xs));
-  ns1_split_rows(xf, xs, g4, sx);
-  const float invq = pp_recip_pow2(a.pp_sw_qkv * sx);
+  ln_lds(xs, L.par[3], L.par[4], g4, a.eps);
+  const float sx = pow2_scale<15>(row_max(xs));
+  split_operand(xf, xs, g4, sx);
+  const float invq = recip_pow2(a.pp_sw_qkv * sx);
   const u32x4_t* wq = reinterpret_cast<const u32x4_t*>(a.ns_qkv);
 #pragma unroll 1
   for (int t0 = w; t0 < 27; t0 += 3 * NW) {           // column tiles t0, t0 + NW, t0 + 2 NW (past the end: tile 26 again, not stored)
@@ -446,18 +408,18 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
       f32x4 sc[2], o[A_OT] = {splat4(0.f), splat4(0.f), splat4(0.f)};
       float mw = -INFINITY, lw = 0.f;
       if (have) {
-        const Split8 qf = split8(qlo[hh] * splat4(LOG2E * sq), qhi[hh] * splat4(LOG2E * sq));
+        const Split8 qf = split8h(qlo[hh] * splat4(LOG2E * sq), qhi[hh] * splat4(LOG2E * sq));
         const float qt = qtl[hh] * (LOG2E * sq);
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
           const int kt = 2 * w + k2;
           Split8 kf;
           if constexpr ((NS_DIAG & 64) != 0) { kf.t[0] = __builtin_bit_cast(u32x4_t, klo[hh][k2]); kf.t[1] = __builtin_bit_cast(u32x4_t, khi[hh][k2]); }   // timing only
-          else kf = split8(klo[hh][k2] * splat4(sk), khi[hh][k2] * splat4(sk));
+          else kf = split8h(klo[hh][k2] * splat4(sk), khi[hh][k2] * splat4(sk));
           f32x4 acc = splat4(0.f);
-          acc = ns_mfma(kf.t[1], qf.t[0], acc);
-          acc = ns_mfma(kf.t[0], qf.t[1], acc);
-          acc = ns_mfma(kf.t[0], qf.t[0], acc);
+          acc = mma32h(kf.t[1], qf.t[0], acc);
+          acc = mma32h(kf.t[0], qf.t[1], acc);
+          acc = mma32h(kf.t[0], qf.t[0], acc);
           sc[k2] = mfma4(ktl[hh][k2] * sk, qt, acc) * inv_qk;
           const int kb = 16 * kt + g4;
           sc[k2].x = (kb + 0 < TK) ? sc[k2].x : -INFINITY;
@@ -476,16 +438,16 @@ DEV void ns1_attention(Ns1AttnLds& A, const OutGluArgs& g, int b, int f0, int w,
           lw += (sc[k2].x + sc[k2].y) + (sc[k2].z + sc[k2].w);
         }
         lw = group_sum(lw);
-        const Split8 pf = split8(sc[0] * splat4(SP), sc[1] * splat4(SP));
+        const Split8 pf = split8h(sc[0] * splat4(SP), sc[1] * splat4(SP));
 #pragma unroll
         for (int i = 0; i < A_OT; ++i) {
           const f32x4 lo = {ve[hh][i][0], ve[hh][i][1], ve[hh][i][2], ve[hh][i][3]}, hi = {ve[hh][i][4], ve[hh][i][5], ve[hh][i][6], ve[hh][i][7]};
           Split8 vf;
           if constexpr ((NS_DIAG & 64) != 0) { vf.t[0] = __builtin_bit_cast(u32x4_t, lo); vf.t[1] = __builtin_bit_cast(u32x4_t, hi); }   // timing only
-          else vf = split8(lo * splat4(sv), hi * splat4(sv));
-          o[i] = ns_mfma(vf.t[1], pf.t[0], o[i]);
-          o[i] = ns_mfma(vf.t[0], pf.t[1], o[i]);
-          o[i] = ns_mfma(vf.t[0], pf.t[0], o[i]);
+          else vf = split8h(lo * splat4(sv), hi * splat4(sv));
+          o[i] = mma32h(vf.t[1], pf.t[0], o[i]);
+          o[i] = mma32h(vf.t[0], pf.t[1], o[i]);
+          o[i] = mma32h(vf.t[0], pf.t[0], o[i]);
         }
       }
       if (gq == 0) { A.pm[hh][w][c] = mw; A.pl[hh][w][c] = lw; }
@@ -547,9 +509,9 @@ __global__ __launch_bounds__(NW * 64) void ns1_out_glu_kernel(OutGluArgs a, int 
   }
   Split8 xf[KS];
   {
-    const float sx = pp_pow2_scale(ns_row_max(xs));
-    ns1_split_rows(xf, xs, g4, sx);
-    const f32x4 inv = splat4(pp_recip_pow2(a.pp_sw_out * sx));
+    const float sx = pow2_scale<15>(row_max(xs));
+    split_operand(xf, xs, g4, sx);
+    const f32x4 inv = splat4(recip_pow2(a.pp_sw_out * sx));
     const u32x4_t* wo = reinterpret_cast<const u32x4_t*>(a.ns_out);
     // nine column tiles: wave w takes tiles w, w + NW, w + 2 NW (< 9); every wave needs the whole row afterwards
 #pragma unroll
@@ -571,10 +533,10 @@ __global__ __launch_bounds__(NW * 64) void ns1_out_glu_kernel(OutGluArgs a, int 
 #pragma unroll
     for (int i = 0; i < KB; ++i) stg4(a.x2 + tl.row + 16 * i + g4, x2[i]);
   }
-  ns1_ln(xs, L.par[0], L.par[1], g4, a.eps);
-  const float sx = pp_pow2_scale(ns_row_max(xs));
-  ns1_split_rows(xf, xs, g4, sx);
-  const float inv = pp_recip_pow2(a.pp_sw_pw1 * sx);
+  ln_lds(xs, L.par[0], L.par[1], g4, a.eps);
+  const float sx = pow2_scale<15>(row_max(xs));
+  split_operand(xf, xs, g4, sx);
+  const float inv = recip_pow2(a.pp_sw_pw1 * sx);
   const u32x4_t* wp = reinterpret_cast<const u32x4_t*>(a.ns_pw1);
   // value tile i and gate tile 9 + i in the same wave; wave w takes i = w, w + NW (< 9): one ns1_plain3 holds (value, gate, -)
 #pragma unroll 1
@@ -664,10 +626,10 @@ __global__ __launch_bounds__(NW * 64) void ns1_tail_kernel(TailFf2Args a, Ff1Qkv
   NS1_STAMP(1);
   Split8 xf[KS];
   {
-    const NsTok tk = ns_chain_scales(a.pp_sc[0], ns_row_max(xs));
+    const PpTok tk = pp_chain_scales(a.pp_sc[0], row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = w == 0 ? (y[i] + lds4(L.par[5], i, g4)) * splat4(tk.s2) : splat4(0.f);
-    ns1_split_rows(xf, xs, g4, tk.sx);
+    split_operand(xf, xs, g4, tk.sx);
     NS1_STAMP(2);
     ns1_chain<9, NW>(y, xf, pool, reinterpret_cast<const u32x4_t*>(a.ns_cv_w1), reinterpret_cast<const u32x4_t*>(a.ns_cv_w2), w, lane, tk.k1, tk.ik2);
     ns1_prime<18, NW>(pool2, reinterpret_cast<const u32x4_t*>(a.ns_ff_w1), w, lane);         // ff_module_2's first fragments: under the exchange + LayerNorm
@@ -680,12 +642,12 @@ __global__ __launch_bounds__(NW * 64) void ns1_tail_kernel(TailFf2Args a, Ff1Qkv
   const float inv_fc = 1.0f / a.fc;
 #pragma unroll
   for (int i = 0; i < KB; ++i) xs[i] = y[i];
-  ns1_ln(xs, L.par[6], L.par[7], g4, a.eps);
+  ln_lds(xs, L.par[6], L.par[7], g4, a.eps);
   {
-    const NsTok tk = ns_chain_scales(a.pp_sc[1], ns_row_max(xs));
+    const PpTok tk = pp_chain_scales(a.pp_sc[1], row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = w == 0 ? (lds4(L.par[8], i, g4) + splat4(inv_fc) * y[i]) * splat4(tk.s2) : splat4(0.f);
-    ns1_split_rows(xf, xs, g4, tk.sx);
+    split_operand(xf, xs, g4, tk.sx);
     NS1_STAMP(5);
     ns1_chain<18, NW>(y, xf, pool2, reinterpret_cast<const u32x4_t*>(a.ns_ff_w1), reinterpret_cast<const u32x4_t*>(a.ns_ff_w2), w, lane, tk.k1, tk.ik2);
     if constexpr (FF1) ns1_prime<18, NW>(pool, reinterpret_cast<const u32x4_t*>(b.ns_w1), w, lane);      // the next block's ff_module_1
@@ -695,7 +657,7 @@ __global__ __launch_bounds__(NW * 64) void ns1_tail_kernel(TailFf2Args a, Ff1Qkv
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = splat4(a.fc * tk.inv2) * y[i];
   }
-  ns1_ln(y, L.par[9], L.par[10], g4, a.eps);                                                // block-final LayerNorm
+  ln_lds(y, L.par[9], L.par[10], g4, a.eps);                                                // block-final LayerNorm
   if (a.y && w == 0 && tl.live) {
 #pragma unroll
     for (int i = 0; i < KB; ++i) stg4(a.y + tl.row + 16 * i + g4, y[i]);
@@ -733,9 +695,9 @@ __global__ __launch_bounds__(NW * 64) void ns1_sublinear_kernel(StreamGemmArgs a
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) xs[kb] = ldg4(xrow + (size_t)f * D + 16 * kb);
     Split8 xf[KS];
-    const float sx = pp_pow2_scale(ns_row_max(xs));
-    ns1_split_rows(xf, xs, g4, sx);
-    const f32x4 inv = splat4(pp_recip_pow2(sw * sx));
+    const float sx = pow2_scale<15>(row_max(xs));
+    split_operand(xf, xs, g4, sx);
+    const f32x4 inv = splat4(recip_pow2(sw * sx));
     const u32x4_t* wp = ns + (size_t)(KB * f) * 128;
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
@@ -767,9 +729,9 @@ __global__ __launch_bounds__(NW * 64) void ns1_head_kernel(GemmArgs a, const u32
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) xs[kb] = ldg4(a.x + tl.row + 16 * kb + g4);
   Split8 xf[KS];
-  const float sx = pp_pow2_scale(ns_row_max(xs));
-  ns1_split_rows(xf, xs, g4, sx);
-  const float inv = pp_recip_pow2(sw * sx);
+  const float sx = pow2_scale<15>(row_max(xs));
+  split_operand(xf, xs, g4, sx);
+  const float inv = recip_pow2(sw * sx);
   const int NT = KB * groups;
   const u32x4_t* wp = ns;
   float best_v = -INFINITY;

@@ -22,7 +22,7 @@
 //
 // Operand scheme (round 3, second half): TWO fp16 terms, THREE products.  A weight matrix is streamed as hi + lo fp16 terms of
 // W * sw (sw = the power of two that puts max |W| in [2^14, 2^15); api.hip: append_pp_chain), an operand row x as hi + lo of
-// x * sx with sx the power of two that puts the ROW's largest magnitude in [2^13, 2^14) (pp_row_max: the rows are this lane's
+// x * sx with sx the power of two that puts the ROW's largest magnitude in [2^13, 2^14) (mfma_ops.h: row_max; the rows are this lane's
 // token, so every scale is a per-lane register), hi = fp16(v), lo = fp16(v - hi), both round-to-nearest: |v - hi - lo| <=
 // 2^-22 |v| while lo is a normal fp16 (|v| >= 2^-2), 2^-25 absolute below.  a b ~ a_hi b_hi + a_hi b_lo + a_lo b_hi: three
 // v_mfma_f32_16x16x32_f16 per fragment pair; what is dropped (a_lo b_lo, the representation errors) is of the size of the
@@ -44,8 +44,6 @@
 
 namespace {
 
-constexpr int D = 144;
-constexpr int KB = D / 16;      // 9
 constexpr int KS32X = 5;        // 32-wide steps over K = 144 (+ the bias row 144)
 constexpr int LD_THREADS = 2 * BLOCK_THREADS;
 
@@ -55,91 +53,6 @@ constexpr int LD_THREADS = 2 * BLOCK_THREADS;
 #ifndef PP_DMA_SLEEP
 #define PP_DMA_SLEEP 0      // s_sleep units (64 cycles) between the pieces a loader wave issues (experiments)
 #endif
-DEV void dma16(const u32x4_t* gsrc, u32x4_t* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, PP_DMA_AUX);
-}
-// s_waitcnt vmcnt(PER * ahead) lgkmcnt(0) for a wave-uniform run-time `ahead` in [0, MAXA] (the count is an immediate)
-template <int PER, int MAXA>
-DEV void wait_dma_ahead(int ahead) {
-  static_for<0, MAXA + 1>([&](auto K) {
-    constexpr int k = decltype(K)::value, n = PER * k;
-    if (ahead == k) __builtin_amdgcn_s_waitcnt(0x0070 | (n & 15) | ((n >> 4) << 14));
-  });
-}
-template <int N>
-struct StashRegs { float r[(N + BLOCK_THREADS - 1) / BLOCK_THREADS]; };
-template <int N>
-DEV StashRegs<N> stash_load(const float* __restrict__ src) {
-  StashRegs<N> s;
-#pragma unroll
-  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
-    const int idx = threadIdx.x + BLOCK_THREADS * k;
-    s.r[k] = idx < N ? src[idx] : 0.f;
-  }
-  return s;
-}
-template <int N>
-DEV void stash_store(float* dst, const StashRegs<N>& s) {
-#pragma unroll
-  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
-    const int idx = threadIdx.x + BLOCK_THREADS * k;
-    if (idx < N) dst[idx] = s.r[k];
-  }
-}
-template <int OFF>
-DEV u32x4_t lds_read16(unsigned addr) {
-  u32x4_t v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-
-struct WaveCtx {
-  int lane, g4, t, tok;
-  size_t row;
-  bool live;
-};
-// T > 0: utterance-aligned tiling (depthwise conv folded in): workgroup (blockIdx.x, blockIdx.y) = 64-frame chunk blockIdx.x of
-// utterance blockIdx.y, so that the conv window of a workgroup never crosses an utterance; T = 0: tokens tiled flat
-DEV void tok_of(WaveCtx& c, unsigned tid, int M, int T) {
-  c.lane = tid & 63;
-  c.g4 = (c.lane >> 4) * 4;
-  c.t = c.lane & 15;
-  const int wv = (int)(tid >> 6);
-  if (T > 0) {
-    const int f = (blockIdx.x * WAVES_PER_BLOCK + wv) * 16 + c.t;      // frame inside the utterance
-    c.live = f < T;
-    c.tok = blockIdx.y * T + min(f, T - 1);                             // frames past the end recompute the last one
-    c.row = (size_t)c.tok * D;
-    return;
-  }
-  const int wid = blockIdx.x * WAVES_PER_BLOCK + wv;
-  c.tok = wid * 16 + c.t;
-  c.live = c.tok < M;
-  c.row = (size_t)min(c.tok, M - 1) * D;     // waves past the end recompute the last token and store nothing
-  if (!c.live) c.tok = M - 1;
-}
-DEV WaveCtx wave_ctx(int M, int T = 0) {
-  WaveCtx c;
-  tok_of(c, threadIdx.x, M, T);
-  return c;
-}
-// recomputed from an opaque copy of the thread index before the stores (keeps the 64-bit row offset out of the stream's
-// live ranges: it was the value the register allocator spilled in the round-2 kernels)
-DEV WaveCtx wave_ctx_fresh(int M, int T = 0) {
-  unsigned tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  WaveCtx c;
-  tok_of(c, tid, M, T);
-  return c;
-}
-DEV void ln_lds(f32x4 (&xs)[KB], const float* ga, const float* be, int g4, float eps) {
-  float mean, rstd;
-  ln_stats<KB>(xs, eps, mean, rstd);
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) xs[kb] = (xs[kb] - splat4(mean)) * splat4(rstd) * lds4(ga, kb, g4) + lds4(be, kb, g4);
-}
-
 DEV void pp_fake_prep(PpPrep& pc) {      // DG bit 0: consumes the hidden tiles and defines the operand without any work
   asm volatile("; no prep" : "=v"(pc.out.t[0]), "=v"(pc.out.t[1]) : "v"(pc.lo), "v"(pc.hi));
 }
@@ -198,7 +111,7 @@ struct PpLoader {
     if constexpr (DG & 16) return;
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
-      dma16(g + BLOCK_THREADS * q, l + BLOCK_THREADS * q);
+      dma16<PP_DMA_AUX>(g + BLOCK_THREADS * q, l + BLOCK_THREADS * q);
       if constexpr (PP_DMA_SLEEP > 0) __builtin_amdgcn_s_sleep(PP_DMA_SLEEP);
     }
   }
@@ -209,7 +122,7 @@ struct PpLoader {
     const u32x4_t* g = slab_ptr(slab) + 64 * (wv - 2) + lane;
     u32x4_t* l = ring + slot * PP_SLB + 64 * (wv - 2);
 #pragma unroll
-    for (int q = 0; q < PP_FR / 2; ++q) dma16(g + 128 * q, l + 128 * q);
+    for (int q = 0; q < PP_FR / 2; ++q) dma16<PP_DMA_AUX>(g + 128 * q, l + 128 * q);
   }
   // pro(): work between the first slabs and the rest of the prefill (the depthwise-conv prologue: PRE0 = 2, the LDS of
   // ring slots 2.. is scratch until pro() returns); every barrier inside pro() has its twin on the consumer side
@@ -344,38 +257,6 @@ DEV void pp_chain(f32x4 (&y)[KB], const Split8 (&xf)[KS32X], PpPool& pl, ST& st,
   }
 }
 
-// largest magnitude of this lane's token row (the row is spread over the four lanes c, c + 16, c + 32, c + 48)
-DEV float pp_row_max(const f32x4 (&xs)[KB]) {
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < KB; ++i)
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(xs[i].x), fabsf(xs[i].y))), fmaxf(fabsf(xs[i].z), fabsf(xs[i].w)));
-  return group_max(m);
-}
-// scales of one chain y += W2 act(W1aug [x ; 1]) for this lane's token (ChainSc: the chain's host-side constants)
-struct PpTok { float sx, k1, ik2, s2, inv2; };
-DEV PpTok pp_chain_scales(const PpChainSc& c, float xmax) {
-  PpTok t;
-  t.sx = pp_pow2_scale(xmax);
-  const float sh = pp_pow2_scale(fmaf(c.l1, xmax, c.bmax));      // |swish(h)| <= |h| <= l1 max|x| + max|b|
-  const float u1 = c.sw1 * t.sx;                                  // unit of the hidden accumulators
-  t.k1 = -1.4426950408889634f * pp_recip_pow2(u1);
-  t.ik2 = u1 * pp_recip_pow2(sh);
-  t.s2 = c.sw2 * sh;                                              // unit of the output accumulators
-  t.inv2 = pp_recip_pow2(t.s2);
-  return t;
-}
-// the five split operands of a 16-token tile for the W1 steps, in units of sx; k-slot 144 (the first padding slot of step 4)
-// carries 1.0 (= sx in those units): row 144 of the streamed W1 holds the bias
-DEV void split_operand(Split8 (&xf)[KS32X], const f32x4 (&xs)[KB], int g4, float sx) {
-  const f32x4 s4 = splat4(sx);
-#pragma unroll
-  for (int t = 0; t < KS32X - 1; ++t) xf[t] = split8(xs[2 * t] * s4, xs[2 * t + 1] * s4);
-  f32x4 oh = splat4(0.f);
-  oh.x = g4 == 0 ? sx : 0.0f;
-  xf[KS32X - 1] = split8(xs[KB - 1] * s4, oh);
-}
-
 struct PpTailLds { float pw2b[D], lng[D], lnb[D], b2[D], fg[D], fb[D]; };
 struct PpFf1Lds { float ln1g[D], ln1b[D], b2[D], ln2g[D], ln2b[D]; };
 
@@ -400,7 +281,7 @@ template <int DG, class ST>
 DEV void pp_tail_consume(const TailFf2Args& a, const PpTailLds& p, int g4, ST& st, PpPool& pl, f32x4 (&xs)[KB], f32x4 (&y)[KB]) {
   Split8 xf[KS32X];
   {
-    const PpTok t = pp_chain_scales(a.pp_sc[0], pp_row_max(xs));
+    const PpTok t = pp_chain_scales(a.pp_sc[0], row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = (y[i] + lds4(p.pw2b, i, g4)) * splat4(t.s2);
     split_operand(xf, xs, g4, t.sx);
@@ -414,7 +295,7 @@ DEV void pp_tail_consume(const TailFf2Args& a, const PpTailLds& p, int g4, ST& s
   for (int i = 0; i < KB; ++i) xs[i] = y[i];
   ln_lds(xs, p.lng, p.lnb, g4, a.eps);
   {
-    const PpTok t = pp_chain_scales(a.pp_sc[1], pp_row_max(xs));
+    const PpTok t = pp_chain_scales(a.pp_sc[1], row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = (lds4(p.b2, i, g4) + splat4(inv_fc) * y[i]) * splat4(t.s2);   // x3 / fc + b2 (+ W2 h)
     split_operand(xf, xs, g4, t.sx);
@@ -436,7 +317,7 @@ DEV void pp_ff1_consume(const Ff1QkvArgs& a, const PpFf1Lds& p, int g4, ST& st, 
   ln_lds(xs, p.ln1g, p.ln1b, g4, a.eps);
   Split8 xf[KS32X];
   {
-    const PpTok t = pp_chain_scales(a.pp_sc, pp_row_max(xs));
+    const PpTok t = pp_chain_scales(a.pp_sc, row_max(xs));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] = y[i] * splat4(t.s2);
     split_operand(xf, xs, g4, t.sx);
@@ -459,9 +340,9 @@ DEV void pp_ff1_consume(const Ff1QkvArgs& a, const PpFf1Lds& p, int g4, ST& st, 
     for (int i = 0; i < KB; ++i) xs[i] += ldg4(pe + 16 * i);
   }
   ln_lds(xs, p.ln2g, p.ln2b, g4, a.eps);
-  const float sx = pp_pow2_scale(pp_row_max(xs));
+  const float sx = pow2_scale<15>(row_max(xs));
   split_operand(xf, xs, g4, sx);                                                     // the q / k / v bias rides in row 144 too
-  const float invq = pp_recip_pow2(a.pp_sw_qkv * sx);
+  const float invq = recip_pow2(a.pp_sw_qkv * sx);
   const int nproj = a.xq_pe ? 1 : 3;                                                 // (the loaders stop behind the q group as well)
 #pragma unroll 1
   for (int q = 0; q < nproj; ++q) {
@@ -606,7 +487,7 @@ DEV void pp_og_tile(const OutGluArgs& g, const PpOgLds& p, ST& st, PpPool& pl, f
   const int g4 = (lane >> 4) * 4, c = lane & 15;
   Split8 xf[KS32X];
   {
-    const float sx = pp_pow2_scale(pp_row_max(xs));
+    const float sx = pow2_scale<15>(row_max(xs));
     split_operand(xf, xs, g4, sx);
     f32x4 acc[KB];
 #pragma unroll
@@ -616,12 +497,12 @@ DEV void pp_og_tile(const OutGluArgs& g, const PpOgLds& p, ST& st, PpPool& pl, f
       pp_unit_S<DG>(acc, xf[t], pl, st);
     });
     pp_pool_land(pl);
-    const f32x4 inv = splat4(pp_recip_pow2(g.pp_sw_out * sx));
+    const f32x4 inv = splat4(recip_pow2(g.pp_sw_out * sx));
 #pragma unroll
     for (int i = 0; i < KB; ++i) { x2[i] += acc[i] * inv; xs[i] = x2[i]; }                // x2 = x1 + attention (+ bias: row 144)
   }
   ln_lds(xs, p.lng, p.lnb, g4, g.eps);
-  const float sx = pp_pow2_scale(pp_row_max(xs));
+  const float sx = pow2_scale<15>(row_max(xs));
   split_operand(xf, xs, g4, sx);
   f32x4 val[KB], gate[KB];
 #pragma unroll
@@ -635,7 +516,7 @@ DEV void pp_og_tile(const OutGluArgs& g, const PpOgLds& p, ST& st, PpPool& pl, f
     pp_unit_S<DG>(gate, xf[t], pl, st);
   });
   pp_pool_land(pl);                                       // the reads into the slot behind the stream: landed, then forgotten
-  const float inv = pp_recip_pow2(g.pp_sw_pw1 * sx);
+  const float inv = recip_pow2(g.pp_sw_pw1 * sx);
   const int f = frame0 + c, r = f - f0;                   // this lane's frame and its window row
   const bool inside = f >= 0 && f < T;
   if (r >= 0 && r < DW_ROWS) {
@@ -653,9 +534,9 @@ DEV void pp_og_tile(const OutGluArgs& g, const PpOgLds& p, ST& st, PpPool& pl, f
 template <int DG, class ST>
 DEV void pp_head_consume(const TailFf2Args& a, int g4, int lane, ST& st, PpPool& pl, const f32x4 (&xs)[KB], int T) {
   Split8 xf[KS32X];
-  const float sx = pp_pow2_scale(pp_row_max(xs));
+  const float sx = pow2_scale<15>(row_max(xs));
   split_operand(xf, xs, g4, sx);
-  const float inv = pp_recip_pow2(a.head_sw * sx);
+  const float inv = recip_pow2(a.head_sw * sx);
   float best_v = -INFINITY;
   int best_i = 0;
   const bool want_max = a.head_argmax != nullptr || a.head_maxval != nullptr;
@@ -828,7 +709,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_block_kernel(TailFf2Args a, Ff1
 #pragma unroll 1
     for (int f = 0; f < b.pre_chunks; ++f) {
       Split8 xf[KS32X];
-      const float sx = pp_pow2_scale(pp_row_max(xs));
+      const float sx = pow2_scale<15>(row_max(xs));
       split_operand(xf, xs, c.g4, sx);
       if (f + 1 < b.pre_chunks) {
 #pragma unroll
@@ -842,7 +723,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_block_kernel(TailFf2Args a, Ff1
         pp_unit_S<DG>(acc, xf[t], pl, st);
       });
       pp_pool_land(pl);
-      const f32x4 inv = splat4(pp_recip_pow2(b.pre_sw * sx));
+      const f32x4 inv = splat4(recip_pow2(b.pre_sw * sx));
 #pragma unroll
       for (int i = 0; i < KB; ++i) y[i] += acc[i] * inv;
     }
@@ -898,7 +779,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_out_glu_kernel(OutGluArgs a) {
   pp_pool_land(pl);
   Split8 xf[KS32X];
   {
-    const float sx = pp_pow2_scale(pp_row_max(xs));
+    const float sx = pow2_scale<15>(row_max(xs));
     split_operand(xf, xs, c.g4, sx);
     f32x4 acc[KB];
 #pragma unroll
@@ -908,7 +789,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_out_glu_kernel(OutGluArgs a) {
       pp_unit_S<DG>(acc, xf[t], pl, st);
     });
     pp_pool_land(pl);
-    const f32x4 inv = splat4(pp_recip_pow2(a.pp_sw_out * sx));
+    const f32x4 inv = splat4(recip_pow2(a.pp_sw_out * sx));
 #pragma unroll
     for (int i = 0; i < KB; ++i) { x2[i] += acc[i] * inv; xs[i] = x2[i]; }                // x2 = x1 + attention (+ bias: row 144)
   }
@@ -920,7 +801,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_out_glu_kernel(OutGluArgs a) {
     }
   }
   ln_lds(xs, p.lng, p.lnb, c.g4, a.eps);
-  const float sx = pp_pow2_scale(pp_row_max(xs));
+  const float sx = pow2_scale<15>(row_max(xs));
   split_operand(xf, xs, c.g4, sx);
   f32x4 val[KB], gate[KB];
 #pragma unroll
@@ -934,7 +815,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_out_glu_kernel(OutGluArgs a) {
     pp_unit_S<DG>(gate, xf[t], pl, st);
   });
   pp_pool_land(pl);                                       // the pool's reads past the last slot
-  const float inv = pp_recip_pow2(a.pp_sw_pw1 * sx);
+  const float inv = recip_pow2(a.pp_sw_pw1 * sx);
   const WaveCtx e = wave_ctx_fresh(a.M);
   if (e.live) {
 #pragma unroll
@@ -972,9 +853,9 @@ __global__ __launch_bounds__(LD_THREADS) void pp_head_kernel(GemmArgs a, const u
     f32x4 xs[KB];
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) xs[kb] = ldg4(a.x + c.row + 16 * kb + c.g4);
-    const float sx = pp_pow2_scale(pp_row_max(xs));
+    const float sx = pow2_scale<15>(row_max(xs));
     split_operand(xf, xs, c.g4, sx);
-    inv = pp_recip_pow2(pp_sw * sx);
+    inv = recip_pow2(pp_sw * sx);
   }
   st.sync();
   PpPool pl;
@@ -1077,7 +958,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_sublinear_kernel(StreamGemmArgs
 #pragma unroll 1
   for (int f = 0; f < chunks; ++f) {
     Split8 xf[KS32X];
-    const float sx = pp_pow2_scale(pp_row_max(xs));
+    const float sx = pow2_scale<15>(row_max(xs));
     split_operand(xf, xs, g4, sx);
     if (f + 1 < chunks) {
 #pragma unroll
@@ -1091,7 +972,7 @@ __global__ __launch_bounds__(LD_THREADS) void pp_sublinear_kernel(StreamGemmArgs
       pp_unit_S<DG>(acc, xf[t], pl, st);
     });
     pp_pool_land(pl);
-    const f32x4 inv = splat4(pp_recip_pow2(pp_sw * sx));
+    const f32x4 inv = splat4(recip_pow2(pp_sw * sx));
 #pragma unroll
     for (int i = 0; i < KB; ++i) y[i] += acc[i] * inv;
   }

@@ -3,7 +3,7 @@
 //     Y[M, N] = epilogue( LN?(X)[M, K] . W[K, N] + b ),   K a multiple of 128, N a multiple of 128,
 // the Gemm16Args contract of bf16.hip (same epilogues, same call sites in run_block) with fp32 results: every fp32
 // operand is the exact sum of three bf16 terms and the six term pairs with i + j <= 2 go through
-// v_mfma_f32_16x16x32_bf16, smallest first (subconv.hip / leaf.hip: as accurate as an fp32 FMA chain, 6 x 16 cycles
+// v_mfma_f32_16x16x32_bf16, smallest first (mfma_ops.h: as accurate as an fp32 FMA chain, 6 x 16 cycles
 // per 32 k-slots instead of 8 x 32 for v_mfma_f32_16x16x4_f32).
 //
 // Shape of the work (the conv-subsampling slab kernel of subconv.hip with a token row as the operand):
@@ -14,7 +14,7 @@
 //     MFMAs per wave and slab);
 //   * the X operand: lane (token c, group g) loads x[token][32 s + 4 g .. + 3] and [32 s + 16 + 4 g .. + 3] four steps
 //     ahead (two with two row tiles per wave: registers; a first version with one slab and two operand steps in flight ran at the memory latency: 2 us per step),
-//     applies the prologue LayerNorm (two-pass statistics, gamma / beta in LDS) and splits into three bf16x8 terms --
+//     applies the prologue LayerNorm (two-pass statistics, gamma / beta in LDS) and splits into three bf16x8_t terms --
 //     by the lower waves before the MFMAs of the step, by the upper waves (their SIMD partners) for the next step after
 //     them, so one wave's VALU phase faces the other's MFMAs;
 //   * the wait before a step's barrier is a counted vmcnt: everything issued after the slab of the NEXT step -- two
@@ -29,6 +29,7 @@
 #include "env.h"
 #include "launch.h"
 #include "wstream.h"
+#include "mfma_ops.h"
 
 namespace {
 
@@ -38,57 +39,28 @@ constexpr int GNB = 8;                            // column tiles per workgroup
 constexpr int GLN_MAX = 512;                      // widest prologue LayerNorm (dmodel)
 constexpr int GUNR = 4;                           // unroll of the step loop (slab slots and operand stages divide it)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-DEV void dma16(const u32x4* gsrc, u32x4* lds) {   // 16 bytes per lane, global -> LDS; lane i lands at lds + 16 i
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-template <int OFF>
-DEV u32x4 lds_read16(unsigned addr) {             // not visible to the compiler as an LDS access: see mfma_step
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-
 // TERMS = 3: fp32 operands, exactly split.  TERMS = 1: bf16 mode (BASELINE config 3) -- weights rounded once on the host,
 // activations rounded to nearest even at the operand, one MFMA per tile and step; same arithmetic as bf16.hip.
 template <int TERMS>
-struct Frag { u32x4 t[TERMS]; };                  // 8 k-slots x TERMS terms
+struct Frag { u32x4_t t[TERMS]; };                  // 8 k-slots x TERMS terms
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-// exact three-term bf16 split of eight fp32 values by truncation (remainders exact), two values per dword; or the eight
-// values rounded to nearest-even bf16
+// the operand of a k-step: the exact three-term split (mfma_ops.h: split8), or the eight values rounded to nearest-even bf16
 template <int TERMS>
-DEV Frag<TERMS> split8(f32x4 lo, f32x4 hi) {
-  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+DEV Frag<TERMS> split_frag(f32x4 lo, f32x4 hi) {
   Frag<TERMS> f;
   if constexpr (TERMS == 1) {
+    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     unsigned d[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const f32x2 pr = {v[2 * k], v[2 * k + 1]};
       d[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(pr, bf16x2_t));     // v_cvt_pk_bf16_f32
     }
-    f.t[0] = u32x4{d[0], d[1], d[2], d[3]};
+    f.t[0] = u32x4_t{d[0], d[1], d[2], d[3]};
   } else {
+    const Split8x3 s = split8(lo, hi);
 #pragma unroll
-    for (int term = 0; term < 3; ++term) {
-      unsigned d[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * k]), a1 = __builtin_bit_cast(unsigned, v[2 * k + 1]);
-        d[k] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);           // (a0 >> 16) | (a1 & 0xffff0000)
-        if (term < 2) {
-          v[2 * k] -= __builtin_bit_cast(float, a0 & 0xffff0000u);
-          v[2 * k + 1] -= __builtin_bit_cast(float, a1 & 0xffff0000u);
-        }
-      }
-      f.t[term] = u32x4{d[0], d[1], d[2], d[3]};
-    }
+    for (int t = 0; t < 3; ++t) f.t[t] = s.t[t];
   }
   return f;
 }
@@ -117,9 +89,9 @@ DEV void ln_row_sq(const float* p, float mean, float& q) {
 struct XRegs { f32x4 lo, hi; };                   // one lane's eight operand values of one k-step, before LN / split
 
 template <int EPI, bool LN, int RT, int RING, int TERMS, bool EDMA>
-__global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u32x4* __restrict__ wring, int cpw) {
+__global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u32x4_t* __restrict__ wring, int cpw) {
   constexpr int GSLAB = GNB * TERMS * 64;
-  __shared__ __attribute__((aligned(16))) u32x4 wl[RING][GSLAB];
+  __shared__ __attribute__((aligned(16))) u32x4_t wl[RING][GSLAB];
   __shared__ __attribute__((aligned(16))) float p_gb[2 * (LN ? GLN_MAX : 4)];   // LayerNorm gamma, then beta
   float* const p_g = p_gb;
   float* const p_b = p_gb + (LN ? GLN_MAX : 4);
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
   // (the class head split over ranges of chunks: the last range may hold fewer)
   const int ncc = (EPI == E16_HEAD && a.head_chunks > 0) ? min(cpw, a.head_chunks - chunk0) : cpw;
   const int steps = a.K / 32, total = ncc * steps;
-  const u32x4* __restrict__ wg = wring + (size_t)chunk0 * steps * GSLAB;
+  const u32x4_t* __restrict__ wg = wring + (size_t)chunk0 * steps * GSLAB;
   constexpr int NQ = (GSLAB + GT - 1) / GT;       // DMA instructions per wave and slab: 3, or 1 in bf16 mode
   // EDMA: only the lower four waves (the ones that split before their MFMAs) issue slab DMAs, twice as many each: an
   // LDS-DMA instruction holds the issuing wave for ~100 cycles, and the upper waves' MFMAs are what the SIMD should be
@@ -143,7 +115,7 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
   // the first RING - 1 slabs
 #pragma unroll
   for (int st = 0; st < RING - 1; ++st) {
-    const u32x4* src = wg + (size_t)min(st, total - 1) * GSLAB;
+    const u32x4_t* src = wg + (size_t)min(st, total - 1) * GSLAB;
     if constexpr (EDMA) {
       if (wv < GW / 2) {
 #pragma unroll
@@ -236,7 +208,7 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
   constexpr unsigned LN_B = sizeof(float) * (LN ? GLN_MAX : 4);      // p_b follows p_g
   auto xsplit = [&](int st, const XRegs (&x)[RT], Frag<TERMS> (&f)[RT]) {
     const int sc = st >= steps ? st - steps : st;
-    u32x4 gl = {}, gh = {}, bl = {}, bh = {};
+    u32x4_t gl = {}, gh = {}, bl = {}, bh = {};
     if (LN) {
       const unsigned at = ln_base + 128u * (unsigned)sc;
       gl = lds_read16<0>(at); gh = lds_read16<64>(at); bl = lds_read16<LN_B>(at); bh = lds_read16<LN_B + 64>(at);
@@ -250,7 +222,7 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
         lo = (lo - m) * r * __builtin_bit_cast(f32x4, gl) + __builtin_bit_cast(f32x4, bl);
         hi = (hi - m) * r * __builtin_bit_cast(f32x4, gh) + __builtin_bit_cast(f32x4, bh);
       }
-      f[rt] = split8<TERMS>(lo, hi);
+      f[rt] = split_frag<TERMS>(lo, hi);
     }
   };
 
@@ -269,16 +241,14 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
   __builtin_amdgcn_s_waitcnt(0x0f70);             // vmcnt(0): the first slabs and operands
   __syncthreads();
 
-  // The weight fragments are read with inline-asm ds_read_b128 and counted lgkmcnt waits: a compiler-visible LDS read of
-  // the ring makes hipcc wait for vmcnt(0) first -- it cannot tell the slot being read from the slots the LDS-DMA in
-  // flight is writing -- which put the whole DMA latency into every step (the first version of this kernel: 23 % MFMA
-  // busy).  Two column tiles at a time (six MFMAs in a row on one accumulator would each wait for the one before), the
+  // The weight fragments are read with lds_read16 and counted lgkmcnt waits (wstream.h has the reason; the first version of
+  // this kernel, with compiler-visible reads, ran at 23 % MFMA busy).  Two column tiles at a time (six MFMAs in a row on one accumulator would each wait for the one before), the
   // next pair requested before the MFMAs of the current one; LDS returns in order, so lgkmcnt(6) = "all but the six
   // newest reads".
   auto mfma_step = [&](int slot) {
     const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(&wl[slot][lane]);
-    u32x4 wa[2][TERMS], wb[2][TERMS];
-    auto fetch = [&](u32x4 (&w)[2][TERMS], auto PAIR_T) {
+    u32x4_t wa[2][TERMS], wb[2][TERMS];
+    auto fetch = [&](u32x4_t (&w)[2][TERMS], auto PAIR_T) {
       constexpr int PAIR = decltype(PAIR_T)::value;
       static_for<0, 2>([&](auto H_T) {
         constexpr int h = decltype(H_T)::value;
@@ -288,14 +258,14 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
         });
       });
     };
-    auto wait = [&](u32x4 (&w)[2][TERMS], auto N_T) {
+    auto wait = [&](u32x4_t (&w)[2][TERMS], auto N_T) {
       constexpr int N = decltype(N_T)::value;
       if constexpr (TERMS == 3)
         asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[0][2]), "+v"(w[1][0]), "+v"(w[1][1]), "+v"(w[1][2]) : "n"(N));
       else
         asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w[0][0]), "+v"(w[1][0]) : "n"(N));
     };
-    auto mma = [&](const u32x4 (&w)[2][TERMS], auto PAIR_T) {
+    auto mma = [&](const u32x4_t (&w)[2][TERMS], auto PAIR_T) {
       constexpr int PAIR = decltype(PAIR_T)::value;
 #pragma unroll
       for (int ord = TERMS - 1; ord >= 0; --ord)
@@ -305,8 +275,8 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
-              acc[rt][2 * PAIR + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w[h][ord - p]),
-                  __builtin_bit_cast(bf16x8, xa[rt].t[p]), acc[rt][2 * PAIR + h], 0, 0, 0);
+              acc[rt][2 * PAIR + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[h][ord - p]),
+                  __builtin_bit_cast(bf16x8_t, xa[rt].t[p]), acc[rt][2 * PAIR + h], 0, 0, 0);
     };
     constexpr int NEW = 2 * TERMS;                // reads of one pair: "all but the newest pair" = lgkmcnt(NEW)
     fetch(wa, std::integral_constant<int, 0>{});
@@ -323,7 +293,7 @@ __global__ __launch_bounds__(GT, 2) void gemm_ring_kernel(Gemm16Args a, const u3
     mma(wb, std::integral_constant<int, 3>{});
   };
   auto slab_dma = [&](int st, int slot, auto LATE_T) {     // slab `st` into a slot last read in step st - RING
-    const u32x4* src = wg + (size_t)min(st, total - 1) * GSLAB;
+    const u32x4_t* src = wg + (size_t)min(st, total - 1) * GSLAB;
     if constexpr (EDMA) {
       if constexpr (!decltype(LATE_T)::value) {
 #pragma unroll
@@ -576,9 +546,9 @@ int go(const Gemm16Args& a, const void* ring, hipStream_t s) {
         cpw = (chunks + best_nr - 1) / best_nr;
         grid.y = best_nr;
         if (force_slots == 2 || (force_slots != 4 && (long)grid.x * grid.y > 320))
-          hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 2, TERMS, EDMA>), grid, dim3(GT), 0, s, b, (const u32x4*)ring, cpw);
+          hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 2, TERMS, EDMA>), grid, dim3(GT), 0, s, b, (const u32x4_t*)ring, cpw);
         else
-          hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, b, (const u32x4*)ring, cpw);
+          hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, b, (const u32x4_t*)ring, cpw);
         return launch_head_combine(a.part_v, a.part_i, best_nr, a.M, a.argmax_out, nullptr, s);
       }
     }
@@ -586,13 +556,13 @@ int go(const Gemm16Args& a, const void* ring, hipStream_t s) {
 
   if (best_rt == 2 && force_slots != 2) {
     if constexpr (EPI != E16_HEAD)
-      hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 2, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4*)ring, cpw);
+      hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 2, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4_t*)ring, cpw);
   } else if (best_rt == 2)
     return -1;
   else if (force_slots == 2 || (force_slots != 4 && (long)grid.x * grid.y > 320))
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 2, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4*)ring, cpw);
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 2, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4_t*)ring, cpw);
   else
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4*)ring, cpw);
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI, LN, 1, 4, TERMS, EDMA>), grid, dim3(GT), 0, s, a, (const u32x4_t*)ring, cpw);
   return 0;
 }
 

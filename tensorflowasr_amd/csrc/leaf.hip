@@ -166,8 +166,6 @@ static_assert(SPOS == 64 * SW, "one wave per 64 positions");
 constexpr int XSTAGE = SPOS + 32 * KB32 + 8;  // staged samples
 constexpr int XSTRIDE = 2080;               // bytes between shifted copies (>= 2 * XSTAGE + 16, = 32 mod 256)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 DEV unsigned bf16_rne_bits(float v) {
   unsigned u = __builtin_bit_cast(unsigned, v);
@@ -183,7 +181,7 @@ template <int NS>
 __global__ __launch_bounds__(STH, 2) void leaf_conv_pool_split_kernel(LeafConvArgs a) {
   constexpr int SLAB = NTL * NS * 64;        // 16-byte fragments per 32 taps
   constexpr int NQ = (SLAB + STH - 1) / STH;
-  __shared__ __attribute__((aligned(16))) u32x4 wlds[2][SLAB];
+  __shared__ __attribute__((aligned(16))) u32x4_t wlds[2][SLAB];
   __shared__ __attribute__((aligned(16))) unsigned char xlds[NS * 8 * XSTRIDE];
   __shared__ float red[SW][4][80];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -191,13 +189,13 @@ __global__ __launch_bounds__(STH, 2) void leaf_conv_pool_split_kernel(LeafConvAr
   const int h = blockIdx.x, b = blockIdx.y;
   const int L = a.L, padl = (KTAPS - 1) / 2;
   const float* __restrict__ x = a.wav + (size_t)b * L;
-  const u32x4* __restrict__ wg = reinterpret_cast<const u32x4*>(a.wp);
+  const u32x4_t* __restrict__ wg = reinterpret_cast<const u32x4_t*>(a.wp);
   // first weight slab: global -> registers
-  u32x4 nw[NQ];
+  u32x4_t nw[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int idx = threadIdx.x + STH * q;
-    nw[q] = u32x4{0u, 0u, 0u, 0u};
+    nw[q] = u32x4_t{0u, 0u, 0u, 0u};
     if (idx < SLAB) nw[q] = wg[idx];
   }
   // ---- stage xp[s] = p0 x[s] + p1 x[s+1] for s = SPOS h - 200 .. + XSTAGE, split, 8 shifted copies per term
@@ -232,24 +230,24 @@ __global__ __launch_bounds__(STH, 2) void leaf_conv_pool_split_kernel(LeafConvAr
   for (int kb = 0; kb < KB32; ++kb) {
     const int cur = kb & 1;
     if (kb + 1 < KB32) {
-      const u32x4* src = wg + (size_t)(kb + 1) * SLAB;
+      const u32x4_t* src = wg + (size_t)(kb + 1) * SLAB;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int idx = threadIdx.x + STH * q;
         if (idx < SLAB) nw[q] = src[idx];
       }
     }
-    bf16x8 xf[4][NS];
+    bf16x8_t xf[4][NS];
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
       for (int sp = 0; sp < NS; ++sp)
-        xf[rt][sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xb + sp * 8 * XSTRIDE + 32 * rt + 64 * kb));
+        xf[rt][sp] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(xb + sp * 8 * XSTRIDE + 32 * rt + 64 * kb));
 #pragma unroll
     for (int i = 0; i < NTL; ++i) {
-      bf16x8 wf[NS];
+      bf16x8_t wf[NS];
 #pragma unroll
-      for (int sp = 0; sp < NS; ++sp) wf[sp] = __builtin_bit_cast(bf16x8, wlds[cur][(i * NS + sp) * 64 + lane]);
+      for (int sp = 0; sp < NS; ++sp) wf[sp] = __builtin_bit_cast(bf16x8_t, wlds[cur][(i * NS + sp) * 64 + lane]);
       // terms x_p w_q with p + q = ord, smallest first
 #pragma unroll
       for (int ord = NS - 1; ord >= 0; --ord)

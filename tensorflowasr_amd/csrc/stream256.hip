@@ -39,12 +39,10 @@
 
 #include "common.h"
 #include "launch.h"
+#include "mfma_ops.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 #ifndef MI355ASR_S256_DIAG
@@ -69,7 +67,7 @@ DEV u32x4_t operand(f32x4 lo, f32x4 hi) {
 }
 DEV f32x4 mma(u32x4_t w, u32x4_t x, f32x4 c) {
   if constexpr (S_DG & 64) { c.x += __builtin_bit_cast(float, w.x ^ x.x); return c; }
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
+  return mma32(w, x, c);
 }
 DEV f32x4 act_swish(f32x4 v) { if constexpr (S_DG & 32) return v; else return swish4(v); }
 DEV float act_sigmoid(float v) { if constexpr (S_DG & 32) return v; else return fast_sigmoid(v); }

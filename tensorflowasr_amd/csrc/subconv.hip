@@ -17,6 +17,7 @@
 #include "env.h"
 #include "launch.h"
 #include "wstream.h"
+#include "mfma_ops.h"
 
 MI355_SCALAR_F32_BEGIN     // common.h: no packed f32 VALU in this file (measured faster: profiles/valu_diet_mi355x.md)
 
@@ -207,9 +208,6 @@ constexpr int NPAIR = 4;                           // regular MFMA steps per cha
 constexpr int ninth_steps(int kb) { return (kb + 1) / 2; }
 constexpr int MELP = 8192;                         // floats of LDS for the mel patch
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // Round 5: the weight slabs of subconv_split_ring_kernel travel through a ring of SRING LDS slots, fetched SRING - 1 steps
 // ahead.  With the two-term operands a step's work (conv1 VALU + 54 MFMAs per wave) had shrunk below the latency of one slab's
 // DMA (~1.3 us when every workgroup asks L2 for the same lines), and with a double buffer -- slab s + 1 requested in step s and
@@ -227,6 +225,7 @@ constexpr int SRING = MI355ASR_SUBCONV_RING;
 static_assert(SRING >= 2 && (SRING & (SRING - 1)) == 0, "ring slots: a power of two");
 // s_waitcnt vmcnt(n) with a run-time (wave-uniform) n: the slab DMAs are the only vector-memory operations in flight in the step
 // loop and return in order, so "at most n outstanding" = "everything but the newest n pieces has landed"
+// (kept beside wstream.h's wait_dma_ahead: this one leaves lgkmcnt alone, and the pieces per slab differ from wave to wave)
 DEV void wait_vmcnt(int n) {
   switch (n) {
     case 0: __builtin_amdgcn_s_waitcnt(0x0f70); break;
@@ -241,23 +240,6 @@ DEV void wait_vmcnt(int n) {
   }
 }
 
-// 16 bytes per lane, global -> LDS without a register round trip; `lds` is the wave's (uniform) base, lane i writes
-// lds + 16 i.  Completion is counted by vmcnt.
-DEV void dma16(const u32x4* gsrc, u32x4* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-// A weight fragment from the LDS slab, as inline asm: a compiler-visible LDS read makes hipcc wait for vmcnt(0) first
-// whenever an LDS-DMA is in flight (it cannot tell the buffer being read from the one being written), which exposed the
-// latency of the next slab's DMA in every step.  Waits are counted by hand (LDS returns in order).
-template <int OFF>
-DEV u32x4 lds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-
 // Round 5: the conv1 evaluation's VALU phase was TWICE the MFMA phase of a step (3600 cycles per step interval against 2 x 864
 // of matrix work per SIMD): 36 ds_read_b32 per step, each waited for with lgkmcnt(0) in front of its four v_fmac_f32.  V2:
 // the mel patch in plain row-major order so that a lane's window columns are one or two vector reads per row (all of a tap's
@@ -268,55 +250,13 @@ DEV u32x4 lds_read16(unsigned addr) {
 #define MI355ASR_CONV1_V2 1
 #endif
 #define MI355ASR_CONV1_PK MI355ASR_CONV1_V2
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-struct SplitFrag { u32x4 t[3]; };                  // 8 k-slots x 3 terms
-
-// exact three-term bf16 split of eight fp32 values (slots 0..3 = lo, 4..7 = hi), two values per dword
-DEV SplitFrag split8(f32x4 lo, f32x4 hi) {
-  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  SplitFrag f;
-#pragma unroll
-  for (int term = 0; term < 3; ++term) {
-    unsigned d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * k]), a1 = __builtin_bit_cast(unsigned, v[2 * k + 1]);
-      d[k] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);           // (a0 >> 16) | (a1 & 0xffff0000)
-      if (term < 2) {
-        v[2 * k] -= __builtin_bit_cast(float, a0 & 0xffff0000u);
-        v[2 * k + 1] -= __builtin_bit_cast(float, a1 & 0xffff0000u);
-      }
-    }
-    f.t[term] = u32x4{d[0], d[1], d[2], d[3]};
-  }
-  return f;
-}
-
 // Two-term scheme (round 3): x * scale = hi + lo with hi = fp16(x * scale), lo = fp16(x * scale - hi), both round-to-nearest:
 // |x * scale - hi - lo| <= 2^-22 |x * scale| as long as lo is a normal fp16 (|x * scale| >= 2^-2; below that the error is
 // 2^-25 absolute -- the scale puts the layer's bound at 2^15).  a b ~ a_hi b_hi + a_hi b_lo + a_lo b_hi: three MFMAs instead
 // of six, the dropped a_lo b_lo and the representation errors are of the size of the terms the six-product bf16 scheme
 // drops (measured: the same distance from the fp64 oracle; Ootomo & Yokota's error-corrected fp16 GEMM without its
-// second accumulator, which the power-of-two scales make unnecessary here).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-DEV SplitFrag split8h(f32x4 lo, f32x4 hi) {     // the shared three-instruction split (common.h: split8_f16)
-  SplitFrag f;
-  unsigned d0[4], d1[4];
-  split8_f16(lo, hi, d0, d1);
-  f.t[0] = u32x4{d0[0], d0[1], d0[2], d0[3]};
-  f.t[1] = u32x4{d1[0], d1[1], d1[2], d1[3]};
-  f.t[2] = u32x4{0u, 0u, 0u, 0u};
-  return f;
-}
-template <int TM>
-DEV SplitFrag split_terms(f32x4 lo, f32x4 hi) {
-  if constexpr (TM == 2) return split8h(lo, hi); else return split8(lo, hi);
-}
-template <int TM>
-DEV f32x4 mma_terms(u32x4 w, u32x4 x, f32x4 c) {
-  if constexpr (TM == 2) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
+// second accumulator, which the power-of-two scales make unnecessary here).  Both schemes: mfma_ops.h (split_tm<TM>, mma32_tm<TM>);
+// the slab DMAs and fragment reads: wstream.h (dma16, lds_read16).
 
 // PK: conv1's multiply-adds as v_pk_fma_f32 (operands in aligned register pairs).  dmodel 144 only: the 128-channel-chunk
 // kernels of dmodel 256 / 512 hold two weight-fragment groups per step and have no room for the pairs (they would spill).
@@ -418,7 +358,7 @@ DEV f32x4 conv1_at(const float* melp, PatchGeom RS, const SL& sl, int rt, const 
 #endif
 
 template <int PAIR, int DIAG = 0, int TM = 3, int RTN, class SL>
-DEV void frags_for(SplitFrag (&xf)[RTN], const float* melp, PatchGeom RS, const SL& sl, const f32x4 (&w1r)[9], f32x4 b1v) {
+DEV void frags_for(Split8x3 (&xf)[RTN], const float* melp, PatchGeom RS, const SL& sl, const f32x4 (&w1r)[9], f32x4 b1v) {
 #pragma unroll
   for (int rt = 0; rt < RTN; ++rt) {
     f32x4 lo, hi;
@@ -434,10 +374,10 @@ DEV void frags_for(SplitFrag (&xf)[RTN], const float* melp, PatchGeom RS, const 
       hi = conv1_at<2 * PAIR + 1, DIAG>(melp, RS, sl, rt, w1r, b1v);
     }
     if constexpr (DIAG == 6) {               // no split: the raw bits as three "terms"
-      const u32x4 l = __builtin_bit_cast(u32x4, lo), h = __builtin_bit_cast(u32x4, hi);
+      const u32x4_t l = __builtin_bit_cast(u32x4_t, lo), h = __builtin_bit_cast(u32x4_t, hi);
       xf[rt].t[0] = l; xf[rt].t[1] = h; xf[rt].t[2] = l ^ h;
     } else {
-      xf[rt] = split_terms<TM>(lo, hi);
+      xf[rt] = split_tm<TM>(lo, hi);
     }
   }
 }
@@ -445,7 +385,7 @@ DEV void frags_for(SplitFrag (&xf)[RTN], const float* melp, PatchGeom RS, const 
 // operand of a ninth-tap step: conv1 at tap 8 for channel block cbA (slots 0..3) and cbA + 1 (slots 4..7; zeros past the
 // last block); the conv1 taps of the two blocks pass through the same registers one after the other
 template <int DIAG, int TM, class LT, int RTN, class SL>
-DEV void frags_ninth(SplitFrag (&xf)[RTN], const float* melp, PatchGeom RS, const SL& sl, f32x4 (&w1r)[9], const float* p_b1,
+DEV void frags_ninth(Split8x3 (&xf)[RTN], const float* melp, PatchGeom RS, const SL& sl, f32x4 (&w1r)[9], const float* p_b1,
                      int g4, int cbA, int KBn, LT&& load_taps) {
   f32x4 lo[RTN], hi[RTN];
   load_taps(cbA);
@@ -460,7 +400,7 @@ DEV void frags_ninth(SplitFrag (&xf)[RTN], const float* melp, PatchGeom RS, cons
     for (int rt = 0; rt < RTN; ++rt) hi[rt] = splat4(0.f);
   }
 #pragma unroll
-  for (int rt = 0; rt < RTN; ++rt) xf[rt] = split_terms<TM>(lo[rt], hi[rt]);
+  for (int rt = 0; rt < RTN; ++rt) xf[rt] = split_tm<TM>(lo[rt], hi[rt]);
 }
 
 // ---- conv1 on the matrix pipe (round 5; two-term kernel of dmodel 144: template flag C1M) ----------------------------------------
@@ -486,20 +426,17 @@ struct C1Lane {
   unsigned valid[RTN];
 };
 template <int KT>
-DEV u32x4 c1_read(unsigned addr) {                 // eight fp16 bins of window row 2 KT + g: 16 bytes at an 8-byte aligned address
-  u32x4 v;
+DEV u32x4_t c1_read(unsigned addr) {                 // eight fp16 bins of window row 2 KT + g: 16 bytes at an 8-byte aligned address
+  u32x4_t v;
   asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%3" : "=v"(v) : "v"(addr), "n"(KT * (2 * C1_ROWB / 8)), "n"(KT * (2 * C1_ROWB / 8) + 1));
   return v;
 }
 struct C1Taps { unsigned ph, qh, pl, ql; };        // (w0, w1), (w2, 0) of this lane's (channel, window row) as fp16 hi and lo
 template <int KF>
-DEV u32x4 c1_place(unsigned p, unsigned q) {       // the three weights at slots 2 KF .. 2 KF + 2 of the lane's eight
-  if constexpr (KF == 0) return u32x4{p, q, 0u, 0u};
-  else if constexpr (KF == 1) return u32x4{0u, p, q, 0u};
-  else return u32x4{0u, 0u, p, q};
-}
-DEV f32x4 c1_mma(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+DEV u32x4_t c1_place(unsigned p, unsigned q) {       // the three weights at slots 2 KF .. 2 KF + 2 of the lane's eight
+  if constexpr (KF == 0) return u32x4_t{p, q, 0u, 0u};
+  else if constexpr (KF == 1) return u32x4_t{0u, p, q, 0u};
+  else return u32x4_t{0u, 0u, p, q};
 }
 // ReLU + conv2's zero padding (v_med3_f32) and the step from conv1's accumulator unit (2^m 2^w) to the conv2 operand scale
 template <int Q, class SL>
@@ -510,16 +447,16 @@ DEV f32x4 c1_finish(f32x4 v, const SL& sl, int rt, float kmul) {
 }
 // the operand of a tap-pair step: taps 2 PAIR (k-slots 0..3) and 2 PAIR + 1 (slots 4..7) of the channel block whose taps are in tp
 template <int PAIR, int RTN, class SL>
-DEV void frags_for_mm(SplitFrag (&xf)[RTN], const SL& sl, const C1Taps& tp, f32x4 c0v, float kmul) {
+DEV void frags_for_mm(Split8x3 (&xf)[RTN], const SL& sl, const C1Taps& tp, f32x4 c0v, float kmul) {
   constexpr int QA = 2 * PAIR, QB = 2 * PAIR + 1;
-  u32x4 wh[RTN][2], wlo[RTN][2];
+  u32x4_t wh[RTN][2], wlo[RTN][2];
 #pragma unroll
   for (int rt = 0; rt < RTN; ++rt) {
     wh[rt][0] = c1_read<QA / 3>(sl.bh[rt]); wlo[rt][0] = c1_read<QA / 3>(sl.bl[rt]);
     wh[rt][1] = c1_read<QB / 3>(sl.bh[rt]); wlo[rt][1] = c1_read<QB / 3>(sl.bl[rt]);
   }
-  const u32x4 ah[2] = {c1_place<QA % 3>(tp.ph, tp.qh), c1_place<QB % 3>(tp.ph, tp.qh)};
-  const u32x4 al[2] = {c1_place<QA % 3>(tp.pl, tp.ql), c1_place<QB % 3>(tp.pl, tp.ql)};
+  const u32x4_t ah[2] = {c1_place<QA % 3>(tp.ph, tp.qh), c1_place<QB % 3>(tp.ph, tp.qh)};
+  const u32x4_t al[2] = {c1_place<QA % 3>(tp.pl, tp.ql), c1_place<QB % 3>(tp.pl, tp.ql)};
   f32x4 v[RTN][2];
 #pragma unroll
   for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = c0v; v[rt][1] = c0v; }
@@ -528,45 +465,45 @@ DEV void frags_for_mm(SplitFrag (&xf)[RTN], const SL& sl, const C1Taps& tp, f32x
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wh[rt][0]), "+v"(wlo[rt][0]), "+v"(wh[rt][1]), "+v"(wlo[rt][1]));
   // smallest products first; the 2 RTN accumulators take turns
 #pragma unroll
-  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = c1_mma(al[0], wh[rt][0], v[rt][0]); v[rt][1] = c1_mma(al[1], wh[rt][1], v[rt][1]); }
+  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = mma32h(al[0], wh[rt][0], v[rt][0]); v[rt][1] = mma32h(al[1], wh[rt][1], v[rt][1]); }
 #pragma unroll
-  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = c1_mma(ah[0], wlo[rt][0], v[rt][0]); v[rt][1] = c1_mma(ah[1], wlo[rt][1], v[rt][1]); }
+  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = mma32h(ah[0], wlo[rt][0], v[rt][0]); v[rt][1] = mma32h(ah[1], wlo[rt][1], v[rt][1]); }
 #pragma unroll
-  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = c1_mma(ah[0], wh[rt][0], v[rt][0]); v[rt][1] = c1_mma(ah[1], wh[rt][1], v[rt][1]); }
+  for (int rt = 0; rt < RTN; ++rt) { v[rt][0] = mma32h(ah[0], wh[rt][0], v[rt][0]); v[rt][1] = mma32h(ah[1], wh[rt][1], v[rt][1]); }
 #pragma unroll
   for (int rt = 0; rt < RTN; ++rt)
-    xf[rt] = split8h(c1_finish<QA>(v[rt][0], sl, rt, kmul), c1_finish<QB>(v[rt][1], sl, rt, kmul));
+    xf[rt] = split_tm<2>(c1_finish<QA>(v[rt][0], sl, rt, kmul), c1_finish<QB>(v[rt][1], sl, rt, kmul));
 }
 // the operand of a ninth-tap step: tap 8 of channel block cbA (slots 0..3) and cbA + 1 (slots 4..7; zeros past the last block)
 template <int RTN, class SL, class LT>
-DEV void frags_ninth_mm(SplitFrag (&xf)[RTN], const SL& sl, C1Taps& tp, const float* p_b1, int g4, int cbA, int KBn, float kmul, LT&& load_taps) {
-  u32x4 wh[RTN], wlo[RTN];
+DEV void frags_ninth_mm(Split8x3 (&xf)[RTN], const SL& sl, C1Taps& tp, const float* p_b1, int g4, int cbA, int KBn, float kmul, LT&& load_taps) {
+  u32x4_t wh[RTN], wlo[RTN];
 #pragma unroll
   for (int rt = 0; rt < RTN; ++rt) { wh[rt] = c1_read<2>(sl.bh[rt]); wlo[rt] = c1_read<2>(sl.bl[rt]); }
   f32x4 lo[RTN], hi[RTN];
   load_taps(cbA);
   {
-    const u32x4 ah = c1_place<2>(tp.ph, tp.qh), al = c1_place<2>(tp.pl, tp.ql);
+    const u32x4_t ah = c1_place<2>(tp.ph, tp.qh), al = c1_place<2>(tp.pl, tp.ql);
     const f32x4 c0v = lds4(p_b1, cbA, g4);
 #pragma unroll
     for (int rt = 0; rt < RTN; ++rt) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wh[rt]), "+v"(wlo[rt]));
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) lo[rt] = c1_mma(al, wh[rt], c0v);
+    for (int rt = 0; rt < RTN; ++rt) lo[rt] = mma32h(al, wh[rt], c0v);
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) lo[rt] = c1_mma(ah, wlo[rt], lo[rt]);
+    for (int rt = 0; rt < RTN; ++rt) lo[rt] = mma32h(ah, wlo[rt], lo[rt]);
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) lo[rt] = c1_mma(ah, wh[rt], lo[rt]);
+    for (int rt = 0; rt < RTN; ++rt) lo[rt] = mma32h(ah, wh[rt], lo[rt]);
   }
   if (cbA + 1 < KBn) {
     load_taps(cbA + 1);
-    const u32x4 ah = c1_place<2>(tp.ph, tp.qh), al = c1_place<2>(tp.pl, tp.ql);
+    const u32x4_t ah = c1_place<2>(tp.ph, tp.qh), al = c1_place<2>(tp.pl, tp.ql);
     const f32x4 c0v = lds4(p_b1, cbA + 1, g4);
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) hi[rt] = c1_mma(al, wh[rt], c0v);
+    for (int rt = 0; rt < RTN; ++rt) hi[rt] = mma32h(al, wh[rt], c0v);
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) hi[rt] = c1_mma(ah, wlo[rt], hi[rt]);
+    for (int rt = 0; rt < RTN; ++rt) hi[rt] = mma32h(ah, wlo[rt], hi[rt]);
 #pragma unroll
-    for (int rt = 0; rt < RTN; ++rt) hi[rt] = c1_mma(ah, wh[rt], hi[rt]);
+    for (int rt = 0; rt < RTN; ++rt) hi[rt] = mma32h(ah, wh[rt], hi[rt]);
 #pragma unroll
     for (int rt = 0; rt < RTN; ++rt) hi[rt] = c1_finish<8>(hi[rt], sl, rt, kmul);
   } else {
@@ -574,7 +511,7 @@ DEV void frags_ninth_mm(SplitFrag (&xf)[RTN], const SL& sl, C1Taps& tp, const fl
     for (int rt = 0; rt < RTN; ++rt) hi[rt] = splat4(0.f);
   }
 #pragma unroll
-  for (int rt = 0; rt < RTN; ++rt) xf[rt] = split8h(c1_finish<8>(lo[rt], sl, rt, kmul), hi[rt]);
+  for (int rt = 0; rt < RTN; ++rt) xf[rt] = split_tm<2>(c1_finish<8>(lo[rt], sl, rt, kmul), hi[rt]);
 }
 
 // DIAG != 0: timing experiments only (results are wrong): 1 = no conv1 / split work, 2 = one weight-fragment read per
@@ -595,7 +532,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   static_assert(!C1M || (TM == 2 && (DM == 144 || DM == 256)), "conv1 on the matrix pipe: the two-term kernels of dmodel 144 / 256");
   constexpr int KB = DM / 16, NB = NBW, NI = ninth_steps(KB), NK32 = KB * NPAIR + NI, SLABF = NBW * TM * 64, D = DM;
   const int c0 = blockIdx.z * NBW;               // first output column tile of this workgroup
-  __shared__ __attribute__((aligned(16))) u32x4 wl[SRING][SLABF];      // the slab ring: slab s in slot s % SRING
+  __shared__ __attribute__((aligned(16))) u32x4_t wl[SRING][SLABF];      // the slab ring: slab s in slot s % SRING
   __shared__ __attribute__((aligned(16))) float melp[MELP];
   __shared__ __attribute__((aligned(16))) float p_w1[9 * D], p_b1[D], p_b2[D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -609,7 +546,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     ragged_same_pad(F, 3, a.st1, &T1, &pt1);
     ragged_same_pad(T1, 3, 2, &t2_, &pt2);
   }
-  const u32x4* __restrict__ wg = reinterpret_cast<const u32x4*>(TM == 2 ? a.w2h : a.w2s) + (size_t)blockIdx.z * NK32 * SLABF;
+  const u32x4_t* __restrict__ wg = reinterpret_cast<const u32x4_t*>(TM == 2 ? a.w2h : a.w2s) + (size_t)blockIdx.z * NK32 * SLABF;
   float s1 = TM == 2 ? a.h_scale : 1.f;
   if (TM == 2 && a.h_melmax) {                   // features without a static bound: the scale from the UTTERANCE's own maximum
     const float bound = fmaf(a.h_l1, __uint_as_float(a.h_melmax[b]), a.h_bmax);
@@ -629,11 +566,11 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     kmul = s1 / (sm * a.c1_wscale);
   }
   constexpr int NQ = (SLABF + SCT - 1) / SCT;
-  u32x4 nw[NQ];
+  u32x4_t nw[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int idx = threadIdx.x + SCT * q;
-    nw[q] = u32x4{0u, 0u, 0u, 0u};
+    nw[q] = u32x4_t{0u, 0u, 0u, 0u};
     if (idx < SLABF) nw[q] = wg[idx];
   }
   // mel patch: rows tm_base .. + rows, bins fm_base .. + RS (zero outside the utterance / the mel range)
@@ -730,17 +667,17 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   auto sl_bh = [&](int rt) { if constexpr (C1M) return sl.bh[rt]; else return 0u; };
   auto sl_bl = [&](int rt) { if constexpr (C1M) return sl.bl[rt]; else return 0u; };
   constexpr bool C1I = C1M && MI355ASR_SUBCONV_C1I;    // interleaved operand production: two operand buffers, step s reads xbuf[s & 1]
-  SplitFrag xbuf[C1I ? 2 : 1][RTN];
-  SplitFrag (&xa)[RTN] = xbuf[0];
+  Split8x3 xbuf[C1I ? 2 : 1][RTN];
+  Split8x3 (&xa)[RTN] = xbuf[0];
   // the operand of a step through either evaluation, into operand buffer DST
   auto frags_pair = [&](auto PI, int cb, auto DST) {
     constexpr int pair = decltype(PI)::value;
-    SplitFrag (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
+    Split8x3 (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
     if constexpr (C1M) frags_for_mm<pair>(dst, sl, c1t, lds4(p_b1, cb, g4), kmul);
     else frags_for<pair, DIAG, TM>(dst, melp, RS, sl, w1r, lds4(p_b1, cb, g4));
   };
   auto frags_9th = [&](int cbA, auto DST) {
-    SplitFrag (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
+    Split8x3 (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
     if constexpr (C1M) frags_ninth_mm(dst, sl, c1t, p_b1, g4, cbA, KB, kmul, load_taps);
     else frags_ninth<DIAG, TM>(dst, melp, RS, sl, w1r, p_b1, g4, cbA, KB, load_taps);
   };
@@ -748,11 +685,11 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   // interleaved mode: the operand of a tap-pair step in pieces, called behind fragment group GI of the previous step's MFMAs.  By
   // the time piece GI + 1 runs, the counted lgkmcnt wait in front of group GI + 1 has covered the window reads piece GI issued
   // (LDS returns in order and they are older than the fragment reads that wait leaves outstanding).
-  u32x4 c1w[4];                 // the window fragments of one row tile: taps A / B, hi / lo plane
+  u32x4_t c1w[4];                 // the window fragments of one row tile: taps A / B, hi / lo plane
   f32x4 c1v[2];                 // conv1 accumulators of that row tile
   auto c1_piece = [&](auto PI, auto GI, int cb, auto DST) {
     constexpr int pair = decltype(PI)::value, gi = decltype(GI)::value, QA = 2 * pair, QB = 2 * pair + 1;
-    SplitFrag (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
+    Split8x3 (&dst)[RTN] = xbuf[C1I ? decltype(DST)::value : 0];
     auto reads = [&](int rt) {
       c1w[0] = c1_read<QA / 3>(sl_bh(rt)); c1w[1] = c1_read<QA / 3>(sl_bl(rt));
       c1w[2] = c1_read<QB / 3>(sl_bh(rt)); c1w[3] = c1_read<QB / 3>(sl_bl(rt));
@@ -760,13 +697,13 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
     auto conv = [&]() {
       asm volatile("" : "+v"(c1w[0]), "+v"(c1w[1]), "+v"(c1w[2]), "+v"(c1w[3]));
       const f32x4 c0v = lds4(p_b1, cb, g4);
-      const u32x4 ahA = c1_place<QA % 3>(c1t.ph, c1t.qh), alA = c1_place<QA % 3>(c1t.pl, c1t.ql);
-      const u32x4 ahB = c1_place<QB % 3>(c1t.ph, c1t.qh), alB = c1_place<QB % 3>(c1t.pl, c1t.ql);
-      c1v[0] = c1_mma(alA, c1w[0], c0v); c1v[1] = c1_mma(alB, c1w[2], c0v);
-      c1v[0] = c1_mma(ahA, c1w[1], c1v[0]); c1v[1] = c1_mma(ahB, c1w[3], c1v[1]);
-      c1v[0] = c1_mma(ahA, c1w[0], c1v[0]); c1v[1] = c1_mma(ahB, c1w[2], c1v[1]);
+      const u32x4_t ahA = c1_place<QA % 3>(c1t.ph, c1t.qh), alA = c1_place<QA % 3>(c1t.pl, c1t.ql);
+      const u32x4_t ahB = c1_place<QB % 3>(c1t.ph, c1t.qh), alB = c1_place<QB % 3>(c1t.pl, c1t.ql);
+      c1v[0] = mma32h(alA, c1w[0], c0v); c1v[1] = mma32h(alB, c1w[2], c0v);
+      c1v[0] = mma32h(ahA, c1w[1], c1v[0]); c1v[1] = mma32h(ahB, c1w[3], c1v[1]);
+      c1v[0] = mma32h(ahA, c1w[0], c1v[0]); c1v[1] = mma32h(ahB, c1w[2], c1v[1]);
     };
-    auto finish = [&](int rt) { dst[rt] = split8h(c1_finish<QA>(c1v[0], sl, rt, kmul), c1_finish<QB>(c1v[1], sl, rt, kmul)); };
+    auto finish = [&](int rt) { dst[rt] = split_tm<2>(c1_finish<QA>(c1v[0], sl, rt, kmul), c1_finish<QB>(c1v[1], sl, rt, kmul)); };
     if constexpr (gi == 0) reads(0);
     else if constexpr (gi == 1) conv();
     else if constexpr (gi == 2) { finish(0); if constexpr (RTN > 1) reads(1); }
@@ -777,7 +714,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
 #pragma unroll
     for (int rt = 0; rt < RTN; ++rt)
 #pragma unroll
-      for (int t = 0; t < 3; ++t) xa[rt].t[t] = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+      for (int t = 0; t < 3; ++t) xa[rt].t[t] = u32x4_t{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
   }
   // which waves run MFMAs first: the SIMD partner of a wave must take the other order (see the step loop)
   const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -788,7 +725,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   for (int q = 0; q < NQ; ++q) my_pieces += (SCT * q + 64 * wv < SLABF) ? 1 : 0;
   auto issue_slab = [&](int t) {       // slab t -> ring slot t % SRING
     if (t < NK32 && DIAG != 3) {
-      const u32x4* src = wg + (size_t)t * SLABF;
+      const u32x4_t* src = wg + (size_t)t * SLABF;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int w0 = SCT * q + 64 * wv;                        // wave-uniform
@@ -809,7 +746,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
   // frags_next() = the operand of step s + 1 (late waves, after the MFMAs)
   auto step_body = [&](int s, auto&& frags_this, auto&& frags_next, auto PAR_T) {
       const int cur = s & (SRING - 1);
-      SplitFrag (&xin)[RTN] = xbuf[(C1M && MI355ASR_SUBCONV_C1I) ? decltype(PAR_T)::value : 0];    // the operand this step's MFMAs read
+      Split8x3 (&xin)[RTN] = xbuf[(C1M && MI355ASR_SUBCONV_C1I) ? decltype(PAR_T)::value : 0];    // the operand this step's MFMAs read
       // slab s + SRING - 1: global -> LDS directly (global_load_lds_dwordx4: lane i of a wave lands at base + 16 i) into the slot
       // that was last read in step s - 1, whose barrier every wave has passed.
       auto slab_dma = [&]() { issue_slab(s + SRING - 1); };
@@ -818,8 +755,8 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
       auto mfma_cur = [&](auto&& between) {         // between(GI): called behind the MFMAs of every fragment group
         constexpr int G = NB % 2 == 0 ? 2 : 1, NG = NB / G;
         const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(&wl[cur][lane]);
-        u32x4 wa[G][3], wb[G][3];
-        auto fetch = [&](u32x4 (&w)[G][3], auto GI) {
+        u32x4_t wa[G][3], wb[G][3];
+        auto fetch = [&](u32x4_t (&w)[G][3], auto GI) {
           constexpr int gi = decltype(GI)::value;
           static_for<0, G>([&](auto HI) {
             constexpr int h = decltype(HI)::value;
@@ -829,7 +766,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
             if constexpr (TM == 3) w[h][2] = lds_read16<((gi * G + h) * TM + 2) * 1024>(base);
           });
         };
-        auto wait = [&](u32x4 (&w)[G][3], auto N_T) {
+        auto wait = [&](u32x4_t (&w)[G][3], auto N_T) {
           constexpr int N = decltype(N_T)::value;
           if constexpr (TM == 2 && G == 1)
             asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w[0][0]), "+v"(w[0][1]) : "n"(N));
@@ -841,7 +778,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
             asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[0][2]), "+v"(w[1][0]), "+v"(w[1][1]),
                          "+v"(w[1][2]) : "n"(N));
         };
-        auto mma = [&](const u32x4 (&w)[G][3], auto GI) {
+        auto mma = [&](const u32x4_t (&w)[G][3], auto GI) {
           constexpr int gi = decltype(GI)::value;
 #pragma unroll
           for (int ord = DIAG == 7 ? 1 : TM - 1; ord >= 0; --ord)   // DIAG 7: without the three products of order 2^-16
@@ -854,7 +791,7 @@ __global__ __launch_bounds__(SCT, 2) void subconv_split_ring_kernel(SubConvArgs 
                   if constexpr (DIAG == 8)        // no matrix work: the operands are consumed by one VALU op per fragment pair
                     acc[rt][gi * G + h] += __builtin_bit_cast(f32x4, w[h][ord - p] ^ xin[rt].t[p]);
                   else
-                    acc[rt][gi * G + h] = mma_terms<TM>(w[h][ord - p], xin[rt].t[p], acc[rt][gi * G + h]);
+                    acc[rt][gi * G + h] = mma32_tm<TM>(w[h][ord - p], xin[rt].t[p], acc[rt][gi * G + h]);
                 }
         };
         fetch(wa, std::integral_constant<int, 0>{});

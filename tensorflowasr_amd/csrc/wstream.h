@@ -1,4 +1,5 @@
-// Register-resident weight stream for the one-wave-per-16-rows GEMM kernels (fused.hip, subconv in frontend.hip).
+// Weight streams of the GEMM kernels: the parameter stash, the DMA / LDS-read plumbing of the slab-ring kernels, and the
+// register-resident stream of the one-wave-per-16-rows fp32 kernel (subconv.hip: subconv144_kernel).
 #pragma once
 #include <type_traits>
 
@@ -21,6 +22,58 @@ DEV void stash(float* dst, const float* __restrict__ src, int n) {
 }
 // this lane's float4 of tile `tile` of a stashed vector (lanes of one 16-lane group read the same address)
 DEV f32x4 lds4(const float* v, int tile, int g4) { return *reinterpret_cast<const f32x4*>(v + 16 * tile + g4); }
+// the stash in two phases: all global loads of a kernel first, then the LDS writes (stash() per array makes one L2 round trip per
+// array: load, wait, write)
+template <int N>
+struct StashRegs { float r[(N + BLOCK_THREADS - 1) / BLOCK_THREADS]; };
+template <int N>
+DEV StashRegs<N> stash_load(const float* __restrict__ src) {
+  StashRegs<N> s;
+#pragma unroll
+  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
+    const int idx = threadIdx.x + BLOCK_THREADS * k;
+    s.r[k] = idx < N ? src[idx] : 0.f;
+  }
+  return s;
+}
+template <int N>
+DEV void stash_store(float* dst, const StashRegs<N>& s) {
+#pragma unroll
+  for (int k = 0; k < (N + BLOCK_THREADS - 1) / BLOCK_THREADS; ++k) {
+    const int idx = threadIdx.x + BLOCK_THREADS * k;
+    if (idx < N) dst[idx] = s.r[k];
+  }
+}
+
+// ---- weight slabs through LDS by DMA ----------------------------------------------------------------------------------------
+// The slab kernels (fused.hip, fused_pp.hip, gemm_ring.hip, subconv.hip) stream weight fragments global -> LDS into a ring of
+// slots, several slabs ahead, and read them back as MFMA operands.
+// dma16: 16 bytes per lane without a register round trip (global_load_lds_dwordx4); `lds` is the wave's (uniform) base, lane i
+// lands at lds + 16 i; AUX = the cache-policy bits.  Completion is counted by vmcnt, in issue order.
+template <int AUX = 0>
+DEV void dma16(const u32x4_t* gsrc, u32x4_t* lds) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds, 16, 0, AUX);
+}
+// A fragment read from the ring is inline asm, and the barrier that hands a slot over is a bare s_barrier: hipcc tracks LDS-DMA per
+// LDS object (a ring indexed at run time is one object), so it would put vmcnt(0) in front of every LDS read it can see while a DMA
+// may be pending -- exposing the next slab's latency in every step -- and the fence of __syncthreads() waits for all DMAs too.
+// Hence every wait is counted by hand: LDS returns in order (lgkmcnt(n) = "everything but the n newest reads"), and so do the
+// DMAs, as long as they are the only vector-memory operations in flight.
+template <int OFF>
+DEV u32x4_t lds_read16(unsigned addr) {
+  u32x4_t v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+// s_waitcnt vmcnt(PER * ahead) lgkmcnt(0) for a wave-uniform run-time `ahead` in [0, MAXA] (the count is an immediate)
+template <int PER, int MAXA>
+DEV void wait_dma_ahead(int ahead) {
+  static_for<0, MAXA + 1>([&](auto K) {
+    constexpr int k = decltype(K)::value, n = PER * k;
+    if (ahead == k) __builtin_amdgcn_s_waitcnt(0x0070 | (n & 15) | ((n >> 4) << 14));
+  });
+}
 
 // ---- weight stream ----------------------------------------------------------------------------------------
 // The weight stream of a kernel is one sequence of NB-fragment batches (one k-block x NB column tiles) that runs

@@ -942,7 +942,7 @@ def test_two_term_fp16_scheme_is_as_close_to_fp64_as_the_six_product_bf16_scheme
     """The operand schemes of DESIGN.md section 2 restated in NumPy on one FFN-sized layer (512 x 144 x 576, fp64 products and
     sums, so only the operand representation and the dropped term pairs show): three bf16 terms / six products, and two
     fp16 terms (round-to-nearest hi + lo of the operand times the power of two that puts its bound in [2^13, 2^14) -- the
-    kernels' pp_pow2_scale) / three products.  Both land within 4e-7 of the fp64 result (a plain fp32 matmul: 2e-6, its
+    kernels' pow2_scale<15>) / three products.  Both land within 4e-7 of the fp64 result (a plain fp32 matmul: 2e-6, its
     accumulation); without the scales the lo terms of small weights go subnormal and the scheme is five times worse."""
     rng = np.random.default_rng(0)
     M, K, N = 512, 144, 576
@@ -959,7 +959,7 @@ def test_two_term_fp16_scheme_is_as_close_to_fp64_as_the_six_product_bf16_scheme
             r = (r - hi).astype(np.float32)
         return out
 
-    def pow2_scale(bound):                      # fused_pp.hip: pp_pow2_scale
+    def pow2_scale(bound):                      # mfma_ops.h: pow2_scale<15>
         e = (np.float32(bound).view(np.uint32) >> 23) & 255
         return np.float32(2.0) ** np.clip(140 - e.astype(np.int64), -14, 15)
 
