@@ -994,7 +994,7 @@ SWITCHES = {
     "MI355ASR_PP_OUTGLU": "0: three-term out_glu_ld_kernel | test_opt_in_kernel_variants, test_two_term_fp16_block_and_attention_under_adversarial_operand_bounds",
     "MI355ASR_PP_HEAD": "0: three-term head_ld_kernel | test_opt_in_kernel_variants",
     "MI355ASR_PP_SUBLINEAR": "0: three-term sublinear_split_ld_kernel | test_opt_in_kernel_variants",
-    "MI355ASR_SUBCONV_TERMS": "3: three-term subsampling conv; 22: two-term also for caller-supplied features | test_two_term_fp16_subsampling_conv_...",
+    "MI355ASR_SUBCONV_TERMS": "3: three-term subsampling conv; 22: two-term also for caller-supplied features | test_two_term_fp16_subsampling_conv_..., test_conv_subsampling_two_term_in_a_fresh_process",
     "MI355ASR_ATTN_TERMS": "3: three-term attention_split_kernel | test_opt_in_kernel_variants, adversarial test",
     "MI355ASR_FFT_TERMS": "3: three-term STFT | test_opt_in_kernel_variants",
     "MI355ASR_LEAF_TERMS": "0: fp32 LEAF Gabor convolution | test_leaf_*",
@@ -1018,23 +1018,23 @@ SWITCHES = {
     "MI355ASR_NS1_ATTN": "0: the attention of a small-batch block (one-tile-per-workgroup kernels) as its own launch instead of inside the out-projection launch | test_small_batches_one_tile_per_workgroup_against_the_pair_pipelined_kernels_and_the_oracle",
     "MI355ASR_STREAM256": "0: bf16 mode, dmodel 256, chunks of <= 16 rows: one launch per layer / module instead of the whole block stack in stream256_kernel | test_streaming_block_stack_in_one_launch_vs_layer_at_a_time_and_rounding_oracle",
     "MI355ASR_CHAIN256_RT": "1 / 2 / 4 / 5: row tiles per workgroup of chain256_bf16_kernel (default by row count) | test_bf16_chain256_against_layer_at_a_time",
-    "MI355ASR_SUBCONV_RT": "1 / 2: row tiles per wave of the two-term subsampling conv (default: one while that gives no CU a second workgroup) | test_two_term_subsampling_conv_one_row_tile_per_wave_bit_identical",
+    "MI355ASR_SUBCONV_RT": "1 / 2: row tiles per wave of the two-term subsampling conv (default: one while that gives no CU a second workgroup) | test_two_term_subsampling_conv_one_row_tile_per_wave_bit_identical, test_conv_subsampling_row_tiles_per_wave_are_bit_identical",
     "MI355ASR_SUBCONV_C1M": "0: conv1 of the two-term subsampling conv on the VALU in fp32 instead of on the matrix pipe | test_subsampling_conv1_on_the_matrix_pipe_against_the_valu_evaluation",
     "MI355ASR_QKV_HEAD_MAJOR": "0: q / k / v as token-major [B T, 3 D] rows instead of head-major planes | test_head_major_qkv_bit_identical_to_token_major",
     "MI355ASR_ATTN_BAND_LDS": "0: band attention with K / V straight from L2 (no staged window) | test_band_attention_staged_window_bit_identical",
     "MI355ASR_PP_HEADF": "0: the class head as its own launch instead of in the CTC block's tail launch | test_layer_in_front_of_a_block_in_its_first_launch_bit_for_bit",
     "MI355ASR_PP_PRE": "0: subsampling Dense and CTC projection as their own launches | test_layer_in_front_of_a_block_in_its_first_launch_bit_for_bit",
     "MI355ASR_GEMM16": "1: layer-at-a-time gemm16 kernels for every row count | test_bf16 / gemm16 tests",
-    "MI355ASR_GEMM_RING": "0: dmodel 256 / 512 without the slab-ring GEMMs | test_ring_gemm_at_16000_rows_...",
+    "MI355ASR_GEMM_RING": "0: dmodel 256 / 512 without the slab-ring GEMMs | test_ring_gemm_at_16000_rows_..., test_without_the_ring_above_the_crossover_in_a_fresh_process",
     "MI355ASR_SMALL_M": "rows up to which the layer-at-a-time kernels run (default 48) | test_fused_block_path_at_short_utterances",
-    "MI355ASR_RING_MIN_M": "rows from which gemm_ring runs | ring tests",
-    "MI355ASR_RING_RT": "forces the ring GEMM's row tiles per wave (tests) | ring tests",
+    "MI355ASR_RING_MIN_M": "rows from which gemm_ring runs | ring tests, test_forced_ring_shapes_on_grids_with_a_partial_last_row_workgroup",
+    "MI355ASR_RING_RT": "forces the ring GEMM's row tiles per wave (tests) | ring tests, test_forced_ring_shapes_on_grids_with_a_partial_last_row_workgroup",
     "MI355ASR_GEMM256": "0: dense layers of dmodel 256 in bf16 mode stay on the ring kernel at many rows (gemm256_bf16_kernel off) | config 3 tests",
     "MI355ASR_GEMM256_MIN_M": "rows from which gemm256_bf16_kernel takes a K = 256 layer (default 8192) | config 3 tests",
-    "MI355ASR_RING_SLOTS": "forces the ring depth (tests) | ring tests",
-    "MI355ASR_RING_CPW": "forces column chunks per workgroup (tests) | ring tests",
+    "MI355ASR_RING_SLOTS": "forces the ring depth (tests) | ring tests, test_forced_ring_shapes_on_grids_with_a_partial_last_row_workgroup",
+    "MI355ASR_RING_CPW": "forces column chunks per workgroup (tests) | ring tests, test_forced_ring_shapes_on_grids_with_a_partial_last_row_workgroup",
     "MI355ASR_PP_HEAD_RANGES": "forces the number of class ranges of the two-term class head (1: one workgroup per row tile) | head tests",
-    "MI355ASR_RING_HEAD_RANGES": "forces the number of class ranges of the ring class head (1: one workgroup per row tile) | ring tests",
+    "MI355ASR_RING_HEAD_RANGES": "forces the number of class ranges of the ring class head (1: one workgroup per row tile) | ring tests, test_ring_head_of_1332_classes_in_forced_ranges",
     "MI355ASR_TOPN_REG": "0: LDS top-n kernel instead of the register-resident one | test_prefix_beam_topn_*",
     "MI355ASR_BEAM_DEVICE": "0: prefix search on host threads | test_prefix_beam_device_path_matches_reference_kats",
     # diagnostics (timing-only kernels need -DMI355ASR_DIAG_KERNELS; results are wrong by construction)
