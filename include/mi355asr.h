@@ -629,6 +629,46 @@ int mi355asr_vad_enhancer_create(const mi355asr_vad_config* cfg, mi355asr_model*
 int mi355asr_vad_enhance(mi355asr_model* m, const float* wav_dev, int32_t B, int32_t L, const int32_t* in_len_dev,
                          float* scores_dev, float* enhanced_dev, void* stream);
 
+/* ---- Punctuation restoration: token ids -> class probabilities per token --------------------------------------
+ * replaces: Punc.punc_recover's onnxruntime session on Inference/PythonInference/punc_recover/models/punc.onnx
+ * (PuncTransformer.inference of punc_recover/models/punc_transformer.py).  Per sentence of T ids (<S> first, </S> last):
+ *   x = embedding[id] * sqrt(d_model) + pos_encoding[:T];  x = ELU(x W + b)
+ *   num_layers times: x = x + ReLU(causal Conv1D k=3 (EncoderLayer(x)))
+ *   x = (x W19 + b19) W20 + b20 (64 -> 768 -> 64, no activation between);  max(num_layers - 1, 1) more EncoderLayers
+ *   probs = softmax(x Wf + bf)
+ * EncoderLayer (post-LN, eps 1e-6): out1 = LN1(x + dense(MHA(x))), out2 = LN2(out1 + W2 relu(W1 out1)); 8 heads of 8, logits
+ * scaled by 1 / sqrt(8), -1e9 added at a key whose id is 0.  One launch per ragged batch, one workgroup per sentence.
+ * Weight names (fp32, Keras layouts; <L> = encoder/layer_<i>, i < num_layers, or map/layer_<i>, i < max(num_layers - 1, 1)):
+ *   embedding [vocab, 64], pos_encoding [pe_input, 64], encoder/dense/{kernel [64, 64], bias [64]}
+ *   <L>/mha/{wq,wk,wv,dense}/{kernel [64, 64], bias [64]}, <L>/ffn/{dense_1,dense_2}/{kernel [64, 64], bias [64]}
+ *   <L>/layernorm1/{gamma,beta} [64], <L>/layernorm2/{gamma,beta} [64]
+ *   encoder/conv_<i>/kernel [3 taps, 64 in, 64 out] (tap 2 is the current token), encoder/conv_<i>/bias [64]
+ *   to_bert/kernel [64, 768], to_bert/bias [768], to_hidden/kernel [768, 64], to_hidden/bias [64]
+ *   final/kernel [64, classes], final/bias [classes]
+ * load with mi355asr_load_weight, then mi355asr_finalize_weights; mi355asr_destroy frees the handle. */
+typedef struct {
+  int32_t d_model;             /* 64 */
+  int32_t enc_embedding_dim;   /* 64 */
+  int32_t num_heads;           /* 8 */
+  int32_t dff;                 /* 64 */
+  int32_t num_layers;          /* 1 .. 6 */
+  int32_t vocab;               /* rows of the embedding table */
+  int32_t classes;             /* <= 64 */
+  int32_t pe_input;            /* rows of pos_encoding, <= 1024: the longest sentence */
+} mi355asr_punc_config;
+int mi355asr_punc_create(const mi355asr_punc_config* cfg, mi355asr_model** out);
+/* lds_tokens: the longest sentence whose activations stay in LDS; max_tokens = pe_input: the longest sentence at all */
+int mi355asr_punc_limits(const mi355asr_model* m, int32_t* lds_tokens, int32_t* max_tokens);
+/* 0 for T <= lds_tokens; beyond that one activation region per sentence */
+int mi355asr_punc_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t T, size_t* bytes);
+/* ids_dev i32 [B, T]; len_dev i32 [B] tokens per row (clamped to [0, T]) or NULL (every row has T); probs_dev f32
+ * [B, T, classes]; cls_dev i32 [B, T] (arg-max class, the lowest on a tie) and pmax_dev f32 [B, T] (its probability), either may
+ * be NULL.  Row b is computed as if it were alone: ids at or past len[b] are never keys, and every output at or past len[b] is
+ * written as 0.  An id outside [0, vocab) is clamped into the table.  A row of more than lds_tokens tokens keeps its
+ * activations in the workspace, whatever T and B are.  T > max_tokens is MI355ASR_EINVAL before anything is launched. */
+int mi355asr_punc_forward(mi355asr_model* m, const int32_t* ids_dev, const int32_t* len_dev, int32_t B, int32_t T,
+                          float* probs_dev, int32_t* cls_dev, float* pmax_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* ---- Polyphase resampling (scipy.signal.resample_poly, default Kaiser filter) ------------------------------------
  * replaces: the host resampling of utils/speech_featurizers.py read_raw_audio (librosa.load at another rate).
  * A ratio up / down (sr_out / sr_in in lowest terms, max(up, down) <= 640; anything else is MI355ASR_EINVAL naming it) has

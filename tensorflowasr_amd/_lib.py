@@ -44,6 +44,12 @@ class VadConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("dmodel", "frame", "decimate")]
 
 
+class PuncConfig(ctypes.Structure):
+    """mirror of `mi355asr_punc_config`."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("d_model", "enc_embedding_dim", "num_heads", "dff", "num_layers", "vocab",
+                                              "classes", "pe_input")]
+
+
 class ChunkOutputs(ctypes.Structure):
     """mirror of `mi355asr_chunk_outputs`."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("front_out", "enc_out", "picker_logits", "picker_hidden", "picked",
@@ -155,6 +161,10 @@ SIGNATURES = {
     "mi355asr_vad_forward": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "mi355asr_vad_enhancer_create": (ctypes.c_int, [ctypes.POINTER(VadConfig), ctypes.POINTER(_P)]),
     "mi355asr_vad_enhance": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "mi355asr_punc_create": (ctypes.c_int, [ctypes.POINTER(PuncConfig), ctypes.POINTER(_P)]),
+    "mi355asr_punc_limits": (ctypes.c_int, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mi355asr_punc_workspace_bytes": (ctypes.c_int, [_P, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_punc_forward": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_resample_plan": (ctypes.c_int, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mi355asr_resample": (ctypes.c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _I, _P, _P, ctypes.c_int64, _P]),
     "mi355asr_resample_streams_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),

@@ -224,6 +224,7 @@ int check_ready(const mi355asr_model* m, bool need_encoder = false) {
   if (m->is_chunk) return fail(MI355ASR_ESTATE, "ChunkConformer handle: use mi355asr_chunk_predict");
   if (m->is_translator) return fail(MI355ASR_ESTATE, "Translator handle: use mi355asr_translator_forward");
   if (m->is_vad) return fail(MI355ASR_ESTATE, "VAD handle: use mi355asr_vad_forward");
+  if (m->is_punc) return fail(MI355ASR_ESTATE, "Punc handle: use mi355asr_punc_forward");
   if (need_encoder && !m->cfg.has_encoder) return fail(MI355ASR_ESTATE, "model was created without an encoder (has_encoder=0)");
   return 0;
 }

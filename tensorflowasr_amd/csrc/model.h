@@ -1,5 +1,5 @@
 // Internal host-side model definitions shared by the host files: weights.hip, api.hip, api_beam.hip, api_chunk.hip,
-// api_translator.hip, block_path.hip (and the handle kinds of vad.hip / stream_hist.hip).
+// api_translator.hip, block_path.hip (and the handle kinds of vad.hip / punc.hip / stream_hist.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -185,6 +185,9 @@ struct mi355asr_model {
   bool is_vad = false;
   bool vad_enhance = false;   // mi355asr_vad_enhancer_create: the arena also holds audio_voice_mask
   mi355asr_vad_config vcfg;
+  // punctuation restorer (mi355asr_punc_create): packed weights, embedding and positional table in `arena` (punc.hip)
+  bool is_punc = false;
+  mi355asr_punc_config pcfg;
   StackDev c_enc, c_picker, c_helper, c_decoder;
   std::vector<int32_t> cs_tab;   // batched chunk streams: the host side of a tick's slot table while its copy is in flight
   // optional per-kernel timing with HIP events on the launch stream (mi355asr_profile_*)
@@ -474,5 +477,6 @@ int walk_block_rows(const mi355asr_model* m, const BlockDev& w, const BlockOpts&
 int finalize_chunk(mi355asr_model* m, hipStream_t s);        // api_chunk.hip
 int finalize_translator(mi355asr_model* m, hipStream_t s);   // api_translator.hip
 int finalize_vad(mi355asr_model* m, hipStream_t s);          // vad.hip
+int finalize_punc(mi355asr_model* m, hipStream_t s);         // punc.hip
 
 }  // namespace mi355

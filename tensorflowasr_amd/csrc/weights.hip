@@ -943,6 +943,7 @@ int mi355asr_finalize_weights(mi355asr_model* m, void* stream) {
   if (m->is_chunk) return finalize_chunk(m, s);
   if (m->is_translator) return finalize_translator(m, s);
   if (m->is_vad) return finalize_vad(m, s);
+  if (m->is_punc) return finalize_punc(m, s);
   const auto& c = m->cfg;
   const int d = c.dmodel;
   ArenaBuilder ab;

@@ -7,8 +7,10 @@ recognition per segment.
 
 Each segment is decoded as its own utterance (`ASR.offline_stt_wave` on the slice): zero-padding segments into one plain
 batch would change their results.  `ASR.offline_stt_batch(segments)` decodes segments of different lengths in ragged
-batches (mi355asr_*_ragged) with the per-segment results, for callers that batch them.  Punctuation (the reference's Punc model) is not
-applied; `best_text` is the Translator's text.  The segmentation is the reference's OfflineVAD (vad.py), including
+batches (mi355asr_*_ragged) with the per-segment results, for callers that batch them.  Punctuation: with `punc=` (a callable
+text -> list or string; `tensorflowasr_amd.punc.Punc` is the reference's Punc model on the GPU) a segment's text of more than
+5 characters goes through it, the offline reference's test, and the result is joined into `best_text`; the default `None`
+leaves `best_text` the Translator's text.  The segmentation is the reference's OfflineVAD (vad.py), including
 its behaviour of returning at most one segment, from the first speech onset to the end of the recording."""
 import numpy as np
 
@@ -17,8 +19,9 @@ from .vad import OfflineVAD
 
 
 class ASRSession:
-    def __init__(self, asr, vad, session="asr_1", sample_rate=16000):
+    def __init__(self, asr, vad, session="asr_1", sample_rate=16000, punc=None):
         self.session = session
+        self.punc = punc
         self.sample_rate = sample_rate
         self.asr = asr
         self.offline_vad = OfflineVAD(sr=sample_rate)
@@ -54,6 +57,8 @@ class ASRSession:
         for idx, (s, e) in enumerate(self.offline_vad.vad(wav)):
             data = wav[int(s * self.sample_rate):int(e * self.sample_rate)]
             phones, text = self.asr.offline_stt_wave(data)
+            if self.punc is not None and len(text) > 5:
+                text = "".join(self.punc(text))
             self.phones.append(phones)
             responses.append({"session": "asr_1", "sentence_index": idx, "sentence_begin_time": int(s * 1000),
                               "best_text": text, "sentence_end_time": int(e * 1000)})

@@ -34,8 +34,10 @@ reference's one by one (tests/golden/stream_session_ref.json), so its quirks are
 * the reference's `final_send` looks up a task id that only an answered inter break of the same sentence leaves behind, and
   raises KeyError otherwise; here the sentence-end event is returned (it never carried the id).
 
-Punctuation: the reference passes texts of 5 or more characters through its Punc model.  The project has none; `punc` is an
-optional callable applied at the same places, the default leaves the text as it is (as the offline `ASRSession`)."""
+Punctuation: the reference passes texts of 5 or more characters through its Punc model.  `punc` is an optional callable
+(text -> list or string) applied at the same places -- `tensorflowasr_amd.punc.Punc` is that model on the GPU, and an instance is
+the hook; the default leaves the text as it is (as the offline `ASRSession`).  A hook with `punc_recover_batch` (Punc has it) is
+called once per server tick with all the texts due, instead of once per text."""
 import collections
 import enum
 
@@ -231,12 +233,17 @@ class _Stream:
             self.task_content.close()
         return self.task_content.want(closing)
 
-    def _text(self, text):
-        if len(text) >= 5 and self.punc is not None:
+    def wants_punc(self, text):
+        return self.punc is not None and text is not None and len(text) >= 5
+
+    def _text(self, text, punctuated=None):
+        if punctuated is not None:           # the server ran the hook for this text already (one call per tick)
+            text = punctuated
+        elif self.wants_punc(text):
             text = self.punc(text)
         return "".join(text)
 
-    def finish(self, action, text=None, closing=False):
+    def finish(self, action, text=None, closing=False, punctuated=None):
         tc = self.task_content
         resp = None
         if action == BEGIN:
@@ -244,12 +251,12 @@ class _Stream:
                         sentence_begin_time=int(tc.clock * 1000 - 200))
         elif action in (END, FINAL):
             resp = dict(session=self.session, event_type="sentence end", sentence_index=int(self.sentence_id),
-                        sentence_begin_time=int(tc.begin_s * 1000), best_text=str(self._text(text)),
+                        sentence_begin_time=int(tc.begin_s * 1000), best_text=str(self._text(text, punctuated)),
                         sentence_end_time=int(tc.end_s * 1000))
             self.sentence_id += 1
         elif action == INTER:
             resp = dict(session=self.session, event_type="inter break", sentence_begin_time=int(tc.begin_s * 1000),
-                        sentence_end_time=int(tc.end_s * 1000), best_text=str(self._text(text)))
+                        sentence_end_time=int(tc.end_s * 1000), best_text=str(self._text(text, punctuated)))
         tc.settle(action)
         if closing:
             tc.restart()
@@ -378,6 +385,7 @@ class StreamingASRServer:
     def __init__(self, asr, vad, n_streams, max_history_s=60., session="asr", sample_rate=16000, punc=None):
         self.asr, self.vad, self.n = asr, vad, int(n_streams)
         self.sample_rate = sample_rate
+        self.punc = punc
         self.streams = [_Stream("%s_%d" % (session, i + 1), sample_rate, punc) for i in range(self.n)]
         self.device_path = hasattr(asr, "encoder") and hasattr(asr, "ctc_model") and hasattr(asr, "translator")
         self.max_history_s = float(max_history_s)
@@ -491,8 +499,14 @@ class StreamingASRServer:
             if action in (END, INTER, FINAL):
                 decode.append((i, audio is not None))
         texts = self._recognise(encode, decode) if (encode or decode) else {}
+        punctuated = {}
+        if hasattr(self.punc, "punc_recover_batch"):
+            # every text this tick's events carry, through the hook in one call (a hook without the batch form runs per text)
+            due = [i for i, action in live.items() if action in (END, INTER, FINAL) and self.streams[i].wants_punc(texts.get(i))]
+            if due:
+                punctuated = dict(zip(due, self.punc.punc_recover_batch([texts[i] for i in due])))
         for i, action in live.items():
-            out[i] = finish(self.streams[i], action, texts.get(i))
+            out[i] = finish(self.streams[i], action, texts.get(i), punctuated.get(i))
             if action in (END, FINAL):
                 self._reset_history(i)
         return out
@@ -508,13 +522,13 @@ class StreamingASRServer:
             if p is not None:
                 tcs[i].step(preds.get(i))
                 plans[i] = self.streams[i].plan()
-        return self._tick(plans, lambda st, action, text: st.finish(action, text))
+        return self._tick(plans, lambda st, action, text, punctuated: st.finish(action, text, punctuated=punctuated))
 
     def final_send(self, streams=None):
         """end the given streams (default: all) -> one event or None per stream of the server (None for the others)"""
         idx = range(self.n) if streams is None else ([streams] if isinstance(streams, int) else streams)
         plans = {i: self.streams[i].plan(closing=True) for i in idx}
-        out = self._tick(plans, lambda st, action, text: st.finish(action, text, closing=True))
+        out = self._tick(plans, lambda st, action, text, punctuated: st.finish(action, text, closing=True, punctuated=punctuated))
         for i in idx:
             self._reset_history(i)
         return out
