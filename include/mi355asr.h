@@ -117,7 +117,7 @@ int mi355asr_load_weight(mi355asr_model* m, const char* name, const float* data_
 #define MI355ASR_DT_F16 1
 #define MI355ASR_DT_BF16 2
 #define MI355ASR_DT_F64 3
-#define MI355ASR_DT_I16 4   /* mi355asr_resample input only */
+#define MI355ASR_DT_I16 4   /* mi355asr_resample and mi355asr_fir_ragged input only */
 int mi355asr_load_weight_typed(mi355asr_model* m, const char* name, const void* data_host, int32_t dtype, int32_t rank,
                                const int64_t* dims);
 /* number of tensors the configuration expects / name of the i-th one (so loaders can iterate) */
@@ -705,6 +705,44 @@ int mi355asr_resample_streams_step(void* state_dev, int32_t up, int32_t down, in
                                    const int32_t* n_in_host, int32_t n, int32_t flush, const float* x_dev, int32_t Ppad,
                                    float* y_dev, int32_t out_cap, int32_t* n_out_host, void* ws_dev, size_t ws_bytes,
                                    void* stream);
+
+/* ---- Far-field simulation: image-source room impulse responses, reverberation, noise at a given SNR ----------------
+ * replaces: augmentations/augments.py -- SignalRIR (rir_generator.generate + scipy.signal.convolve), SignalNoise.Add_noise
+ * and the clip / 16-bit quantisation of Augmentation.process.  Stateless, like mi355asr_resample.
+ *
+ * mi355asr_rir_generate: B impulse responses by the image-source method (Habets' rir_generator: omnidirectional
+ * microphone, 3-D, unlimited reflection order; DESIGN.md section 19 spells the definition out).  params_host is f64
+ * [B, 20], copied by the call: room L[3], source s[3], receiver r[3] in metres; sound speed c (m/s); sample rate fs;
+ * reverberation_time in seconds (> 0: all six reflection coefficients are sqrt(1 - alpha), alpha = 24 V ln 10 / (c S T);
+ * <= 0: the six coefficients that follow are used); beta[6] in the order x1 x2 y1 y2 z1 z2; hp_filter (0 or 1); nsample.
+ * h_dev f32 [B, Kpad]: row b holds its nsample samples and zeros after them.  Distances, fractional delays, the gains and
+ * the sums are float64; a row is the same bits in every run and in every batch (no atomics: each output sample adds its
+ * images in image order).  ws_dev holds the call's device table (mi355asr_rir_workspace_bytes, 8-byte aligned).
+ * One generator launch for all B rows, followed by one launch of the float64 high-pass recurrence when a row asks for it.
+ * Refused as MI355ASR_EINVAL before anything is launched: nsample outside 1 .. min(16384, Kpad); a position outside
+ * [0, L]; the source at the receiver; alpha > 1; |beta| > 1; a window 2 round(0.004 fs) above 1024 taps; more than 255
+ * images per side on an axis (ceil(nsample / (2 L fs / c))). */
+int mi355asr_rir_workspace_bytes(int32_t B, size_t* ws_bytes);
+int mi355asr_rir_generate(const double* params_host, int32_t B, float* h_dev, int32_t Kpad, void* ws_dev, size_t ws_bytes,
+                          void* stream);
+/* Full convolution of a ragged batch: x_dev [B, Lpad] of dtype MI355ASR_DT_F32 or MI355ASR_DT_I16 (converted as x / 32768),
+ * in_len_dev i32 [B] (clamped to [0, Lpad]), h_dev f32 [B, Kpad] -- or [1, Kpad], one filter for every row, when
+ * shared_filter != 0 -- of which K taps (1 .. 16384) are used, y_dev f32 [B, Opad].  Row b gets in_len[b] + K - 1 outputs
+ * (scipy.signal.convolve(x, h, mode="full")), a row of length 0 none; columns past the row's output length (or all of
+ * Opad, if that is smaller) are written as 0.  Samples at or past in_len[b] and taps at or past K are never read.  A row
+ * is computed as if it were alone.  Exact fp32 products summed in fp32 (v_mfma_f32_16x16x4_f32):
+ * |y[n] - y64[n]| <= (K + 2) 2^-23 sum_k |h[k]| |x[n - k]|.  Asynchronous on `stream`. */
+int mi355asr_fir_ragged(const void* x_dev, int32_t dtype, const int32_t* in_len_dev, int32_t B, int64_t Lpad,
+                        const float* h_dev, int32_t K, int64_t Kpad, int32_t shared_filter, float* y_dev, int64_t Opad,
+                        void* stream);
+/* y = x + g d per row, g = float32(sqrt(P_x / 10^(snr_db / 10) / P_d)) with P_x = sum x^2, P_d = sum d^2 over the row's
+ * len[b] samples (clamped to [0, Lpad]), both in float64: x_dev f32 [B, Lpad], d_dev f32 [B, Dpad] (Dpad >= Lpad; len[b]
+ * samples of a row are read), snr_db_dev f32 [B], y_dev f32 [B, Lpad] (zeros past len[b]; may be x_dev).  P_x == 0 or
+ * P_d == 0 gives g = 0, y = x (the reference divides by zero there).  quantise != 0 applies Augmentation.process's last
+ * step, trunc(clamp(y, -1, 1) * 32768) / 32768 (truncation toward zero, exact in fp32).  Before quantisation
+ * |y - y64| <= 2^-23 (|x| + 2 |g64 d|).  One launch, asynchronous on `stream`. */
+int mi355asr_mix_snr(const float* x_dev, const int32_t* len_dev, const float* d_dev, const float* snr_db_dev, int32_t B,
+                     int64_t Lpad, int64_t Dpad, int32_t quantise, float* y_dev, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per

@@ -238,7 +238,7 @@ class ASR:
             cache[rate] = Resampler(rate, self.speech_config["sample_rate"], device=self.device)
         return cache[rate]
 
-    def offline_stt_batch(self, items, max_batch_samples=None, sample_rates=None):
+    def offline_stt_batch(self, items, max_batch_samples=None, sample_rates=None, augment=None):
         """offline_stt_wave for every item of a list -- paths or 1-D waveforms -- in ragged batches: one encoder, CTC and
         Translator call per batch (mi355asr_*_ragged), each row computed as if alone.  Returns [(phones, text), ...] in the
         order of `items`, what [offline_stt_wave(w) for w in items] returns.  max_batch_samples bounds B x Lmax of a batch
@@ -249,11 +249,15 @@ class ASR:
         array item with a rate (float32, or int16 PCM) is resampled on the device from that rate; a path item with a rate is
         read at the file's own rate (featurizers.read_wav_native), which has to be the stated one, and resampled on the
         device.  Items of one rate in one batch share one resampler launch (resample.Resampler), and the resampled rows go
-        into the batch's device tensor without passing over the host."""
-        waves, rates = batch_items(items, sample_rates, self.speech_featurizer.load_wav, int(self.speech_config["sample_rate"]))
-        return self._stt_batch(waves, rates, max_batch_samples)
+        into the batch's device tensor without passing over the host.
 
-    def _stt_batch(self, waves, rates, max_batch_samples):
+        augment: a callable (x [B, W], lengths int32 [B]) -> (y [B, W'] float32 on the device, out_len int32 [B] on the device),
+        such as an augment.FarField: applied to every batch on the device, after loading and resampling and before the
+        encoder, which then sees out_len[b] samples of row b.  None (the default): nothing is applied."""
+        waves, rates = batch_items(items, sample_rates, self.speech_featurizer.load_wav, int(self.speech_config["sample_rate"]))
+        return self._stt_batch(waves, rates, max_batch_samples, augment)
+
+    def _stt_batch(self, waves, rates, max_batch_samples, augment=None):
         """offline_stt_batch on 1-D arrays; rates: None, or per item None / the rate it is resampled from on the device"""
         import torch
         mc, sc = self.model_config, self.speech_config
@@ -265,6 +269,11 @@ class ASR:
         for idx in batches:
             lens = np.array([n16[i] for i in idx], np.int32)
             x = batch_rows(waves, rates, idx, lens, max(min_L, int(lens.max())), self._resampler, self.device)
+            if augment is not None:
+                x, out_len = augment(x, lens)
+                lens = out_len.cpu().numpy().astype(np.int32)
+                if x.shape[1] < min_L:
+                    x = torch.nn.functional.pad(x, (0, min_L - x.shape[1]))
             enc, enc_len = self.encoder(x, training=False, lengths=lens)
             _, frame_ids = self.ctc_model(enc, training=False, return_argmax=True, return_logits=False, lengths=enc_len)
             ids, tok = ctc_greedy_decode(frame_ids, enc_len, blank=blank)

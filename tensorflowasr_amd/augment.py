@@ -1,0 +1,387 @@
+"""Far-field simulation on the device: what the reference's augmentations/augments.py does on the host with rir_generator,
+scipy.signal.convolve and NumPy -- image-source room impulse responses (`ImageSourceRIR`), reverberation of a ragged batch
+(`Reverb`), noise at a given SNR (`AddNoise`), the three in a row (`FarField`) and the reference's `Augmentation` class for
+its keys `rir` and `noise`.  The kernels are csrc/augment.hip; there is no CPU path.
+
+    rir = ImageSourceRIR(16000)                                   # SignalRIR's room: 5 x 4 x 6 m, T60 0.4 s, 4096 taps
+    h = rir.generate(sources, receivers)                          # [B, 4096] float32 on the device
+    y, out_len = Reverb()(x, lengths, h)                          # row b: lengths[b] + 4095 samples
+    y = AddNoise()(y, out_len, noise, snr_db, quantise=True)
+
+    ff = FarField(rir, noise_bank=[n0, n1], snr=(0, 15))
+    y, out_len = ff(x, lengths, np.random.default_rng(0))
+    asr.offline_stt_batch(items, augment=ff)                      # what does the model hear in that room at that SNR
+"""
+import ctypes
+import random
+
+import numpy as np
+
+MAX_TAPS = 16384          # the longest filter mi355asr_fir_ragged takes, and the longest response mi355asr_rir_generate writes
+UNSUPPORTED = ("masking", "pitch", "speed", "hz", "vc", "spec_aug")     # the reference's other augmentations: not built here
+KEYS = ("noise", "rir") + UNSUPPORTED
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(device):
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _rows(x, device, allow_int16=True):
+    """x [L] or [B, L], NumPy or tensor -> a contiguous float32 (or int16) tensor [B, max(L, 1)] on the device, and L"""
+    import torch
+    if isinstance(x, np.ndarray):
+        if not (allow_int16 and x.dtype == np.int16):
+            x = np.asarray(x, np.float32)
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    elif not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x, np.float32))
+    if not (allow_int16 and x.dtype == torch.int16):
+        x = x.to(torch.float32)
+    if x.dim() == 1:
+        x = x.reshape(1, -1)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError("expected [L] or [B, L] with B >= 1, got %s" % (tuple(x.shape),))
+    L = int(x.shape[1])
+    if L == 0:
+        x = torch.zeros((x.shape[0], 1), dtype=x.dtype)
+    return x.to(device).contiguous(), L
+
+
+def _lengths(lengths, B, L, device):
+    import torch
+    if lengths is None:
+        return torch.full((B,), L, dtype=torch.int32, device=device)
+    ln = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths))
+    ln = ln.reshape(-1).to(device=device, dtype=torch.int32).clamp(0, L).contiguous()
+    if ln.numel() != B:
+        raise ValueError("%d rows, %d lengths" % (B, ln.numel()))
+    return ln
+
+
+class ImageSourceRIR:
+    """Room impulse responses by the image-source method (Habets' rir_generator for an omnidirectional microphone, 3-D, every
+    reflection order; DESIGN.md section 19 has the definition -- equality with the PyPI package has not been checked).  The
+    defaults are SignalRIR's; `hp_filter` defaults to the package's (on).  Give `beta` (six reflection coefficients, x1 x2 y1
+    y2 z1 z2) instead of `reverberation_time` to set the walls directly."""
+
+    def __init__(self, sample_rate, room=(5, 4, 6), reverberation_time=0.4, nsample=4096, c=340, beta=None, hp_filter=True,
+                 device="cuda:0"):
+        self.sample_rate, self.c = float(sample_rate), float(c)
+        self.room = tuple(float(v) for v in room)
+        self.nsample, self.hp_filter, self.device = int(nsample), bool(hp_filter), device
+        if len(self.room) != 3 or min(self.room) <= 0 or self.sample_rate <= 0 or self.c <= 0:
+            raise ValueError("room %s, sample rate %g, sound speed %g: all must be positive" % (self.room, self.sample_rate, self.c))
+        if not 1 <= self.nsample <= MAX_TAPS:
+            raise ValueError("nsample = %d is outside 1 .. %d" % (self.nsample, MAX_TAPS))
+        if beta is not None:
+            self.beta, self.reverberation_time = [float(b) for b in beta], 0.0
+            if len(self.beta) != 6 or max(abs(b) for b in self.beta) > 1:
+                raise ValueError("beta: six reflection coefficients within [-1, 1], got %s" % (beta,))
+        else:
+            self.reverberation_time = float(reverberation_time)
+            Lx, Ly, Lz = self.room
+            alpha = 24 * Lx * Ly * Lz * np.log(10.0) / (self.c * 2 * (Lx * Lz + Ly * Lz + Lx * Ly) * self.reverberation_time) \
+                if self.reverberation_time > 0 else np.inf
+            if alpha > 1:
+                raise ValueError("reverberation_time = %g s is too short for the room %s: alpha = %g > 1"
+                                 % (self.reverberation_time, self.room, alpha))
+            self.beta = [float(np.sqrt(1 - alpha))] * 6
+
+    def params(self, sources, receivers):
+        """the [B, 20] float64 table mi355asr_rir_generate takes; ValueError for a position outside the room or a source at
+        its receiver"""
+        s = np.asarray(sources, np.float64).reshape(-1, 3)
+        r = np.asarray(receivers, np.float64).reshape(-1, 3)
+        if len(s) != len(r) or not len(s):
+            raise ValueError("%d sources, %d receivers" % (len(s), len(r)))
+        room = np.asarray(self.room)
+        for name, p in (("source", s), ("receiver", r)):
+            bad = np.argwhere((p < 0) | (p > room) | ~np.isfinite(p))
+            if len(bad):
+                raise ValueError("%s %d at %s is outside the room %s" % (name, bad[0][0], tuple(p[bad[0][0]]), self.room))
+        same = np.all(s == r, axis=1)
+        if same.any():
+            raise ValueError("row %d: the source is at the receiver %s" % (int(np.argmax(same)), tuple(s[np.argmax(same)])))
+        t = np.zeros((len(s), 20), np.float64)
+        t[:, 0:3], t[:, 3:6], t[:, 6:9] = room, s, r
+        t[:, 9], t[:, 10], t[:, 11] = self.c, self.sample_rate, self.reverberation_time
+        t[:, 12:18] = self.beta
+        t[:, 18], t[:, 19] = float(self.hp_filter), self.nsample
+        return t
+
+    def generate(self, sources, receivers):
+        """sources, receivers [B, 3] in metres -> h [B, nsample] float32 on the device"""
+        import torch
+        from . import _lib
+        lib = _lib.lib()
+        t = np.ascontiguousarray(self.params(sources, receivers))
+        B = len(t)
+        wb = ctypes.c_size_t()
+        _lib.check(lib.mi355asr_rir_workspace_bytes(B, ctypes.byref(wb)))
+        ws = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        h = torch.empty((B, self.nsample), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mi355asr_rir_generate(t.ctypes.data_as(ctypes.c_void_p), B, _ptr(h), self.nsample, _ptr(ws), wb.value,
+                                                 _stream(self.device)))
+        self._keep = ws                                 # the table of an asynchronous call
+        return h
+
+
+class Reverb:
+    """Full convolution of a ragged batch with one filter per row (or one for all): scipy.signal.convolve(x, h) per row."""
+
+    def __init__(self, device="cuda:0"):
+        self.device = device
+
+    def __call__(self, x, lengths, h, out_pad=None, taps=None):
+        """x [L] or [B, L] float32 or int16 (x / 32768); lengths [B] or None; h [B, K], or [K] / [1, K] shared by every row
+        (taps: use the first `taps` columns of h only) -> (y [B, L + K - 1] float32 on the device, or `out_pad` columns; out_len int32 [B] on the device: lengths + K - 1, 0
+        for an empty row).  Row b is computed as if alone; zeros after its out_len[b] samples."""
+        import torch
+        from . import _lib
+        x, L = _rows(x, self.device)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        h, K = _rows(h, self.device, allow_int16=False)
+        if taps is not None:
+            if not 1 <= int(taps) <= K:
+                raise ValueError("taps = %d of a filter of %d columns" % (taps, K))
+            K = int(taps)
+        if not 1 <= K <= MAX_TAPS:
+            raise ValueError("a filter of %d taps is outside 1 .. %d" % (K, MAX_TAPS))
+        if h.shape[0] not in (1, B):
+            raise ValueError("%d rows, %d filters" % (B, h.shape[0]))
+        shared = h.shape[0] == 1
+        O = max(1, L + K - 1 if out_pad is None else int(out_pad))
+        y = torch.empty((B, O), dtype=torch.float32, device=self.device)
+        out_len = torch.where(ln > 0, ln + (K - 1), torch.zeros_like(ln)).clamp(max=O)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mi355asr_fir_ragged(_ptr(x), 4 if x.dtype == torch.int16 else 0, _ptr(ln), B, int(x.shape[1]), _ptr(h),
+                                                      K, int(h.shape[1]), int(shared), _ptr(y), O,
+                                                      _stream(self.device)))
+        self._keep = (x, ln, h)                         # inputs of an asynchronous call
+        return y, out_len
+
+
+class AddNoise:
+    """SignalNoise.Add_noise per row, with the powers in float64: y = x + sqrt(P_x / 10^(snr_db / 10) / P_d) d.  A silent
+    row or silent noise gives y = x (the reference divides by zero there).  quantise: Augmentation.process's clip and
+    truncation to 16 bits."""
+
+    def __init__(self, device="cuda:0"):
+        self.device = device
+
+    def __call__(self, x, lengths, noise, snr_db, quantise=False):
+        """x [B, L] float32; noise [B, >= L]: lengths[b] samples of row b are used; snr_db a number or [B] -> y [B, L] on the device"""
+        import torch
+        from . import _lib
+        x, L = _rows(x, self.device, allow_int16=False)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        d, D = _rows(noise, self.device, allow_int16=False)
+        if d.shape[0] != B or d.shape[1] < x.shape[1]:
+            raise ValueError("noise %s does not cover the batch %s" % (tuple(d.shape), tuple(x.shape)))
+        snr = torch.as_tensor(np.broadcast_to(np.asarray(snr_db.cpu() if torch.is_tensor(snr_db) else snr_db, np.float32), (B,)).copy())
+        snr = snr.to(self.device)
+        y = torch.empty_like(x)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mi355asr_mix_snr(_ptr(x), _ptr(ln), _ptr(d), _ptr(snr), B, int(x.shape[1]), int(d.shape[1]),
+                                                   int(bool(quantise)), _ptr(y), _stream(self.device)))
+        self._keep = (x, ln, d, snr)
+        return y if L else y[:, :0]
+
+
+def cut_noise(noise, n, start_draw):
+    """SignalNoise.augment's rule: the recording doubled until it is longer than n + 20, then n samples from a drawn start;
+    start_draw(high) -> an integer in [0, high) is called once, with high = len(doubled) - n - 10"""
+    noise = np.asarray(noise, np.float32).reshape(-1)
+    if not len(noise):
+        raise ValueError("an empty noise recording")
+    while n + 20 > len(noise):
+        noise = np.hstack((noise, noise))
+    start = int(start_draw(len(noise) - n - 10))
+    return noise[start:start + n]
+
+
+def draw_position(room, draw):
+    """SignalRIR.get_num: each coordinate one of the 10 L_d decimetre marks 0, 0.1, ... below L_d; draw(high) -> [0, high)"""
+    return [draw(int(d) * 10) / 10.0 for d in room]
+
+
+class FarField:
+    """Reverberation, then noise, then the 16-bit quantisation, on the device; positions, noise segments and SNRs are drawn on
+    the host from `rng` (a numpy.random.Generator).  rir: an ImageSourceRIR (a source and a receiver are drawn per row on the
+    room's decimetre grid, redrawn when they coincide), a fixed filter (array [K]), or None: no reverberation.  noise_bank: a
+    list of 1-D recordings, or None: no noise.  snr: integers are drawn from [snr[0], snr[1]).  The draws of the last call are
+    kept in `last`."""
+
+    def __init__(self, rir=None, noise_bank=None, snr=(0, 15), quantise=True, device="cuda:0", seed=0):
+        self.rir, self.snr, self.quantise, self.device = rir, (int(snr[0]), int(snr[1])), bool(quantise), device
+        self.noise_bank = None if noise_bank is None else [np.asarray(n, np.float32).reshape(-1) for n in noise_bank]
+        self.rng = np.random.default_rng(seed)
+        self.reverb, self.add_noise = Reverb(device), AddNoise(device)
+        self.last = {}
+
+    def __call__(self, x, lengths=None, rng=None):
+        """-> (y [B, L'] float32 on the device, out_len int32 [B] on the device)"""
+        import torch
+        rng = self.rng if rng is None else rng
+        x, L = _rows(x, self.device)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        self.last = {}
+        if isinstance(self.rir, ImageSourceRIR):
+            draw = lambda high: int(rng.integers(0, high))
+            rec, src = [], []
+            for _ in range(B):
+                r = draw_position(self.rir.room, draw)
+                s = draw_position(self.rir.room, draw)
+                while s == r:
+                    s = draw_position(self.rir.room, draw)
+                rec.append(r)
+                src.append(s)
+            self.last.update(sources=src, receivers=rec)
+            x, ln = self.reverb(x, ln, self.rir.generate(src, rec))
+        elif self.rir is not None:
+            x, ln = self.reverb(x, ln, self.rir)
+        elif x.dtype != torch.float32:
+            x = x.to(torch.float32) / 32768.0
+        if self.noise_bank:
+            lens = ln.cpu().numpy()
+            W = int(x.shape[1])
+            d = np.zeros((B, W), np.float32)
+            picks, starts, snrs = [], [], []
+            for b in range(B):
+                picks.append(int(rng.integers(0, len(self.noise_bank))))
+                d[b, :lens[b]] = cut_noise(self.noise_bank[picks[-1]], int(lens[b]),
+                                           lambda high: starts.append(int(rng.integers(0, high))) or starts[-1])
+                snrs.append(int(rng.integers(self.snr[0], self.snr[1])))
+            self.last.update(noise=picks, starts=starts, snr_db=snrs)
+            x = self.add_noise(x, ln, d, np.asarray(snrs, np.float32), quantise=self.quantise)
+        elif self.quantise:
+            x = self.add_noise(x, ln, torch.zeros_like(x), 0.0, quantise=True)
+        return x, ln
+
+
+class _RirAug:
+    """SignalRIR: its draws (host) and its constants"""
+    key = "rir"
+
+    def __init__(self, sample_rate):
+        self.sample_rate = sample_rate
+        self.room = (5, 4, 6)
+
+    def draw(self, n):
+        """the receiver, then the source, as SignalRIR.augment calls get_num; the source is redrawn while it is at the receiver
+        (the reference would hand rir_generator a zero distance)"""
+        draw = lambda high: random.sample(list(range(high)), 1)[0]
+        r = draw_position(self.room, draw)
+        s = draw_position(self.room, draw)
+        while s == r:
+            s = draw_position(self.room, draw)
+        return {"receiver": r, "source": s}
+
+
+class _NoiseAug:
+    """SignalNoise: its draws (host) over a bank of recordings"""
+    key = "noise"
+
+    def __init__(self, sample_rate=16000, SNR=(-10, 10), noises="", bank=None):
+        self.sample_rate, self.SNR = sample_rate, SNR
+        if bank is None:
+            from .featurizers import read_raw_audio
+            with open(noises) as f:
+                paths = [ln.strip() for ln in f.readlines()]
+            bank = [read_raw_audio(p, sample_rate) for p in paths if p]
+        self.bank = [np.asarray(b, np.float32).reshape(-1) for b in bank]
+
+    def draw(self, n):
+        """np.random.randint in SignalNoise.augment's order: the recording, the start of the segment, the SNR"""
+        pick = int(np.random.randint(0, len(self.bank)))
+        start = []
+        seg = cut_noise(self.bank[pick], n, lambda high: start.append(int(np.random.randint(0, high))) or start[-1])
+        snr = int(np.random.randint(self.SNR[0], self.SNR[1]))
+        return {"noise": pick, "start": start[0], "snr_db": snr, "segment": seg}
+
+
+class Augmentation(dict):
+    """The reference's `Augmentation(config["augments_config"])` for its keys `rir` and `noise`, on the device.  An unknown
+    key is a KeyError, as there.  An active key among masking, pitch, speed, hz, vc, spec_aug raises NotImplementedError
+    naming it; unsupported="skip" drops those keys instead (the shipped am_data.yml has spec_aug active).  process /
+    process_batch pick one active augmentation per utterance with random.sample and make the reference's `random` /
+    `np.random` calls in its order, so a seeded run draws the reference's positions, segments and SNRs; the one deviation: a
+    source drawn at the receiver is drawn again.  noise_bank: recordings to use instead of reading the `noises` list file."""
+
+    def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0"):
+        if unsupported not in ("raise", "skip"):
+            raise ValueError("unsupported must be 'raise' or 'skip', got %r" % (unsupported,))
+        super().__init__(config or {})
+        self.device = device
+        self.augmentations = []
+        self.skipped = []
+        for key, value in self.items():
+            if key not in KEYS:
+                raise KeyError("No augmentation named: %s\nAvailable augmentations: %s" % (key, list(KEYS)))
+            if not value["active"]:
+                continue
+            kw = {k: v for k, v in value.items() if k != "active"}
+            if key in UNSUPPORTED:
+                if unsupported == "raise":
+                    raise NotImplementedError("augmentation '%s' is active and not built here (unsupported='skip' drops it)" % key)
+                self.skipped.append(key)
+            elif key == "rir":
+                self.augmentations.append(_RirAug(**kw))
+            else:
+                self.augmentations.append(_NoiseAug(bank=noise_bank, **kw))
+        self._rirs = {}
+
+    def __missing__(self, key):
+        return None
+
+    def available(self):
+        return len(self.augmentations) > 0
+
+    def draw(self, n):
+        """the host side of process() for an utterance of n samples: (the augmentation picked, its draws)"""
+        aug = random.sample(self.augmentations, 1)[0]
+        return aug, aug.draw(n)
+
+    def process(self, wav):
+        return self.process_batch([wav])[0]
+
+    def process_batch(self, wavs):
+        """-> one float32 array per utterance: reverberated (len + 4095 samples) or with noise added, clipped and quantised"""
+        wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
+        drawn = [self.draw(len(w)) for w in wavs]
+        out = [None] * len(wavs)
+        for key in ("rir", "noise"):
+            rows = [i for i, (aug, _) in enumerate(drawn) if aug.key == key]
+            if not rows:
+                continue
+            lens = np.array([len(wavs[i]) for i in rows], np.int32)
+            x = np.zeros((len(rows), max(1, int(lens.max()))), np.float32)
+            for k, i in enumerate(rows):
+                x[k, :lens[k]] = wavs[i]
+            if key == "rir":
+                aug = drawn[rows[0]][0]
+                if aug.sample_rate not in self._rirs:
+                    self._rirs[aug.sample_rate] = ImageSourceRIR(aug.sample_rate, device=self.device)
+                h = self._rirs[aug.sample_rate].generate([drawn[i][1]["source"] for i in rows], [drawn[i][1]["receiver"] for i in rows])
+                y, ln = Reverb(self.device)(x, lens, h)
+                y = AddNoise(self.device)(y, ln, np.zeros((len(rows), int(y.shape[1])), np.float32), 0.0, quantise=True)
+                ln = ln.cpu().numpy()
+            else:
+                d = np.zeros_like(x)
+                for k, i in enumerate(rows):
+                    d[k, :lens[k]] = drawn[i][1]["segment"]
+                y = AddNoise(self.device)(x, lens, d, np.array([drawn[i][1]["snr_db"] for i in rows], np.float32), quantise=True)
+                ln = lens
+            yh = y.cpu().numpy()
+            for k, i in enumerate(rows):
+                out[i] = yh[k, :ln[k]].copy()
+        return out
