@@ -744,6 +744,54 @@ int mi355asr_fir_ragged(const void* x_dev, int32_t dtype, const int32_t* in_len_
 int mi355asr_mix_snr(const float* x_dev, const int32_t* len_dev, const float* d_dev, const float* snr_db_dev, int32_t B,
                      int64_t Lpad, int64_t Dpad, int32_t quantise, float* y_dev, void* stream);
 
+/* ---- Ragged STFT / ISTFT pair, spec_aug and the phase vocoder ---------------------------------------------------------
+ * replaces: librosa.stft / librosa.istft / librosa.phase_vocoder (librosa 0.9: center=True, pad_mode="reflect", a periodic
+ * Hann window of win_length zero-padded on both sides to n_fft) as augmentations/augments.py calls them in SignalSpecAug and,
+ * through librosa.effects.time_stretch, in SignalSpeed.  Stateless.  (n_fft, win_length, hop) is (1024, 800, 160) or
+ * (2048, 2048, 512); anything else is MI355ASR_EINVAL.  Both DFT stages of both directions run on v_mfma_f32_16x16x4_f32 with
+ * stage matrices computed in float64; the overlap-add is owner-computes in ascending frame order; there are no atomics: a
+ * row is the same bits in every run and in every batch.  The tables of a size are uploaded to the current device on the
+ * first call that uses it (one hipMalloc and one blocking copy) and kept for the life of the process.  DESIGN.md section 20.
+ *
+ * mi355asr_stft_frames: frames of a row of n_samples: 1 + n_samples / hop, or 0 when n_samples < n_fft / 2 + 1 (reflect
+ * padding needs that many; librosa raises there).
+ * mi355asr_stft_ragged: x_dev [B, Lpad] of dtype MI355ASR_DT_F32 or MI355ASR_DT_I16 (x / 32768), len_dev i32 [B] (clamped
+ * to [0, Lpad]) -> S_dev complex64 [B, Fpad, n_fft / 2 + 1] interleaved, frame-major (librosa's layout transposed); frames
+ * at or past the row's count are zeros; a row with more than Fpad frames is cut at Fpad.  frames_dev i32 [B] (may be null)
+ * receives the counts.  Samples at or past len[b] are never read.  One launch.
+ * mi355asr_istft_ragged: S_dev as above with frames_dev i32 [B] -> y_dev f32 [B, Opad]: irfft of each frame (1 / n_fft
+ * included), times the window, overlap-added, divided by the window's sum of squares where that exceeds tiny(float32), the
+ * first n_fft / 2 samples dropped.  Row b gets out_len_dev[b] samples (librosa.istft(..., length=); zeros where no frame
+ * reaches) or, with out_len_dev null, hop (frames[b] - 1); zeros after them.  The imaginary parts of bins 0 and n_fft / 2 are
+ * ignored.  ws_dev (16-byte aligned) holds the windowed frames, B Fpad win_length floats.  Two launches.
+ * mi355asr_spec_aug: SignalSpecAug at (1024, 800, 160) without the spectrum in memory: every frame goes forward, has the
+ * bins [max(h_ - window, 0), h_ + window) zeroed for every centre (h_, w_) of its row with max(w_ - window, 0) <= frame <
+ * w_ + window, and comes back, on chip; its windowed samples go to ws_dev and are overlap-added by a second launch.
+ * centres_dev i32 [B, Npad, 2] holds (h_, w_) pairs, counts_dev i32 [B] how many of a row's are used.  y_dev f32 [B, Opad]:
+ * row b gets 160 (len[b] / 160) samples; a row with fewer than 513 samples is copied through (len[b] samples).  With no
+ * centres the result is that of stft_ragged followed by istft_ragged, bit for bit.  The counts are read back before anything
+ * is launched (the call waits for `stream` once): a count above 513 (the reference's random.sample raises there) or above
+ * Npad, or a negative window, is MI355ASR_EINVAL.
+ * mi355asr_phase_vocoder: librosa.phase_vocoder on S_dev / frames_dev: row b is resampled in time by rates_host[b]
+ * (float64; the time steps t * rate are float64) into out_frames_host[b] <= Tpad frames of O_dev complex64 [B, Tpad,
+ * n_fft / 2 + 1]; zeros after them.  The expected phase advance is reduced modulo 2 pi in float64 on the host and the
+ * accumulated phase is kept in [-pi, pi].  Both host arrays are copied by the call into ws_dev.  One launch. */
+int mi355asr_stft_frames(int32_t n_fft, int32_t win_length, int32_t hop, int64_t n_samples, int32_t* frames);
+int mi355asr_stft_ragged(const void* x_dev, int32_t dtype, const int32_t* len_dev, int32_t B, int64_t Lpad, int32_t n_fft,
+                         int32_t win_length, int32_t hop, float* S_dev, int32_t Fpad, int32_t* frames_dev, void* stream);
+int mi355asr_istft_workspace_bytes(int32_t B, int32_t Fpad, int32_t n_fft, int32_t win_length, int32_t hop, size_t* ws_bytes);
+int mi355asr_istft_ragged(const float* S_dev, const int32_t* frames_dev, int32_t B, int32_t Fpad, int32_t n_fft,
+                          int32_t win_length, int32_t hop, const int32_t* out_len_dev, float* y_dev, int64_t Opad,
+                          void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_spec_aug_workspace_bytes(int32_t B, int64_t Lpad, size_t* ws_bytes);
+int mi355asr_spec_aug(const void* x_dev, int32_t dtype, const int32_t* len_dev, int32_t B, int64_t Lpad,
+                      const int32_t* centres_dev, int32_t Npad, const int32_t* counts_dev, int32_t window, float* y_dev,
+                      int64_t Opad, void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_phase_vocoder_workspace_bytes(int32_t B, size_t* ws_bytes);
+int mi355asr_phase_vocoder(const float* S_dev, const int32_t* frames_dev, int32_t B, int32_t Fpad, int32_t n_fft,
+                           int32_t win_length, int32_t hop, const double* rates_host, const int32_t* out_frames_host,
+                           float* O_dev, int32_t Tpad, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

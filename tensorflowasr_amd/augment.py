@@ -11,6 +11,13 @@ its keys `rir` and `noise`.  The kernels are csrc/augment.hip; there is no CPU p
     ff = FarField(rir, noise_bank=[n0, n1], snr=(0, 15))
     y, out_len = ff(x, lengths, np.random.default_rng(0))
     asr.offline_stt_batch(items, augment=ff)                      # what does the model hear in that room at that SNR
+
+The reference's spectral augmentations that need an STFT and its inverse (csrc/stft.hip, stft.py): `SpecAug` is SignalSpecAug,
+`TimeStretch` is librosa.effects.time_stretch and `Speed` is SignalSpeed on top of it; `Augmentation(config, enable=("spec_aug",
+"speed"))` runs those two keys on the device as well.
+
+    y, out_len = SpecAug(window=10, ratio=0.5)(x, lengths)        # row b: 160 (lengths[b] // 160) samples
+    y, out_len = TimeStretch()(x, lengths, rates)                 # row b: int(round(lengths[b] / rates[b])) samples
 """
 import ctypes
 import random
@@ -268,6 +275,157 @@ class FarField:
         return x, ln
 
 
+class SpecAug:
+    """SignalSpecAug on the device: the STFT at (1024, 800, 160), `int(frames * ratio)` blocks of up to 2 window x 2 window
+    bins and frames zeroed around drawn centres, the inverse STFT.  One frame-local pass: the spectrum is never written to
+    memory (mi355asr_spec_aug).  The last call's centres are kept in `last`."""
+    N_FFT, WIN, HOP, BINS = 1024, 800, 160, 513
+
+    def __init__(self, window=10, ratio=0.5, device="cuda:0"):
+        self.window, self.ratio, self.device = int(window), float(ratio), device
+        if self.window < 0 or self.ratio < 0:
+            raise ValueError("window = %d and ratio = %g must not be negative" % (self.window, self.ratio))
+        self.last = []
+
+    def frames(self, n):
+        return 1 + int(n) // self.HOP if int(n) >= self.BINS else 0
+
+    def draw(self, n_frames):
+        """the reference's two random.sample calls in its order -- the frames, then the bins -- as [nums, 2] pairs (h_, w_);
+        ValueError, as there, when int(n_frames * ratio) exceeds the 513 bins (or the frames)"""
+        nums = int(n_frames * self.ratio)
+        ws = random.sample(list(range(n_frames)), nums)
+        hs = random.sample(list(range(self.BINS)), nums)
+        return np.array(list(zip(hs, ws)), np.int32).reshape(-1, 2)
+
+    def __call__(self, x, lengths=None, centres=None):
+        """x [L] or [B, L] float32 or int16; lengths [B] or None; centres: one [n, 2] array of (h_, w_) per row, or None: drawn
+        with `draw` row by row -> (y [B, max(1, L)] float32 on the device, out_len int32 [B] on the device: 160 (len // 160); a row
+        with fewer than 513 samples has no frame and comes back unchanged, out_len = len)."""
+        import torch
+        from . import _lib
+        lib = _lib.lib()
+        x, L = _rows(x, self.device)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        lens = ln.cpu().numpy()
+        if centres is None:
+            centres = []
+            for b in range(B):
+                F = self.frames(lens[b])
+                if int(F * self.ratio) > min(self.BINS, F):
+                    raise ValueError("row %d: %d frames at ratio %g ask for %d centres, more than the %d bins random.sample can draw"
+                                     % (b, F, self.ratio, int(F * self.ratio), self.BINS))
+                centres.append(self.draw(F))
+        centres = [np.asarray(c, np.int32).reshape(-1, 2) for c in centres]
+        if len(centres) != B:
+            raise ValueError("%d rows, %d sets of centres" % (B, len(centres)))
+        for b, c in enumerate(centres):
+            if len(c) > self.BINS:
+                raise ValueError("row %d: %d centres, more than the %d bins random.sample can draw" % (b, len(c), self.BINS))
+        self.last = centres
+        Npad = max(1, max(len(c) for c in centres))
+        table = np.zeros((B, Npad, 2), np.int32)
+        for b, c in enumerate(centres):
+            table[b, :len(c)] = c
+        ce = torch.from_numpy(table).to(self.device)
+        counts = torch.tensor([len(c) for c in centres], dtype=torch.int32).to(self.device)
+        W = int(x.shape[1])
+        wb = ctypes.c_size_t()
+        _lib.check(lib.mi355asr_spec_aug_workspace_bytes(B, W, ctypes.byref(wb)))
+        ws = torch.empty(wb.value // 4, dtype=torch.float32, device=self.device)
+        y = torch.empty((B, W), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mi355asr_spec_aug(_ptr(x), 4 if x.dtype == torch.int16 else 0, _ptr(ln), B, W, _ptr(ce), Npad, _ptr(counts),
+                                             self.window, _ptr(y), W, _ptr(ws), wb.value, _stream(self.device)))
+        self._keep = (x, ln, ce, counts, ws)
+        out_len = torch.where(ln >= self.BINS, (ln // self.HOP) * self.HOP, ln).to(torch.int32)
+        return y, out_len
+
+
+class TimeStretch:
+    """librosa.effects.time_stretch (librosa 0.9) per row: the STFT at (2048, 2048, 512), the phase vocoder at the row's rate,
+    the inverse STFT cut or zero-filled to int(round(len / rate)) samples.  Three library calls, everything on the device."""
+    N_FFT, HOP = 2048, 512
+
+    def __init__(self, device="cuda:0"):
+        from .stft import STFT
+        self.device = device
+        self.stft = STFT(self.N_FFT, device=device)
+
+    def __call__(self, x, lengths, rates):
+        """x [L] or [B, L]; lengths [B] or None; rates: a number or [B], each > 0 -> (y [B, O] float32 on the device, out_len
+        int32 [B] on the device).  A row with fewer than 1025 samples has no frame (librosa raises there) and gives zeros."""
+        import torch
+        from . import _lib
+        lib = _lib.lib()
+        x, L = _rows(x, self.device)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        lens = ln.cpu().numpy()
+        rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, np.float64).reshape(-1), (B,)))
+        if not (rates > 0).all() or not np.isfinite(rates).all():
+            raise ValueError("rates must be positive, got %s" % (rates,))
+        S, frames = self.stft.forward(x, ln)
+        Fh = [1 + int(n) // self.HOP if n >= self.N_FFT // 2 + 1 else 0 for n in lens]
+        tc = np.array([len(np.arange(0, F, r, dtype=np.float64)) for F, r in zip(Fh, rates)], np.int32)
+        out_len = np.array([int(round(int(n) / r)) for n, r in zip(lens, rates)], np.int32)
+        Tpad = max(1, int(tc.max()))
+        S2 = torch.empty((B, Tpad, self.stft.bins), dtype=torch.complex64, device=self.device)
+        wb = ctypes.c_size_t()
+        _lib.check(lib.mi355asr_phase_vocoder_workspace_bytes(B, ctypes.byref(wb)))
+        ws = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mi355asr_phase_vocoder(_ptr(S), _ptr(frames), B, int(S.shape[1]), self.N_FFT, self.N_FFT, self.HOP,
+                                                  rates.ctypes.data_as(ctypes.c_void_p), tc.ctypes.data_as(ctypes.c_void_p), _ptr(S2),
+                                                  Tpad, _ptr(ws), wb.value, _stream(self.device)))
+        self._keep = (S, frames, ws)
+        return self.stft.inverse(S2, tc, out_lengths=out_len)
+
+
+class Speed:
+    """SignalSpeed: a rate drawn as np.random.random() * factor[1] clipped to [factor[0], factor[1]], then TimeStretch.  factor is
+    a pair or, as in the reference's configuration, its text."""
+    key = "speed"
+
+    def __init__(self, factor="(0.5,2)", device="cuda:0"):
+        if isinstance(factor, str):
+            import ast
+            factor = ast.literal_eval(factor)
+        self.factor = (float(factor[0]), float(factor[1]))
+        if not 0 < self.factor[0] <= self.factor[1]:
+            raise ValueError("factor = %s: need 0 < factor[0] <= factor[1]" % (factor,))
+        self.device = device
+        self._stretch = None
+
+    def draw(self, n=None):
+        return {"rate": float(np.clip(np.random.random() * self.factor[1], self.factor[0], self.factor[1]))}
+
+    def __call__(self, x, lengths=None, rates=None):
+        """rates None: one draw per row"""
+        if self._stretch is None:
+            self._stretch = TimeStretch(self.device)
+        x, L = _rows(x, self.device)
+        if rates is None:
+            rates = [self.draw()["rate"] for _ in range(int(x.shape[0]))]
+        return self._stretch(x, _lengths(lengths, int(x.shape[0]), L, self.device), rates)
+
+
+class _SpecAug(SpecAug):
+    """SignalSpecAug inside Augmentation: its draws for an utterance of n samples"""
+    key = "spec_aug"
+
+    def draw(self, n):
+        F = self.frames(n)
+        if int(F * self.ratio) > min(self.BINS, F):
+            raise ValueError("an utterance of %d samples has %d frames: ratio %g asks for %d centres, more than the %d bins "
+                             "random.sample can draw" % (n, F, self.ratio, int(F * self.ratio), self.BINS))
+        return {"centres": SpecAug.draw(self, F)}
+
+
+DEVICE_KEYS = ("spec_aug", "speed")      # UNSUPPORTED keys that Augmentation(..., enable=) can run on the device
+
+
 class _RirAug:
     """SignalRIR: its draws (host) and its constants"""
     key = "rir"
@@ -315,11 +473,17 @@ class Augmentation(dict):
     naming it; unsupported="skip" drops those keys instead (the shipped am_data.yml has spec_aug active).  process /
     process_batch pick one active augmentation per utterance with random.sample and make the reference's `random` /
     `np.random` calls in its order, so a seeded run draws the reference's positions, segments and SNRs; the one deviation: a
-    source drawn at the receiver is drawn again.  noise_bank: recordings to use instead of reading the `noises` list file."""
+    source drawn at the receiver is drawn again.  noise_bank: recordings to use instead of reading the `noises` list file.
+    enable: keys among spec_aug and speed to run on the device as well (SpecAug, Speed) instead of treating them as
+    unsupported; the default, none, leaves everything above as it is."""
 
-    def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0"):
+    def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0", enable=()):
         if unsupported not in ("raise", "skip"):
             raise ValueError("unsupported must be 'raise' or 'skip', got %r" % (unsupported,))
+        enable = (enable,) if isinstance(enable, str) else tuple(enable)
+        for key in enable:
+            if key not in DEVICE_KEYS:
+                raise ValueError("enable: %r is not one of %s" % (key, DEVICE_KEYS))
         super().__init__(config or {})
         self.device = device
         self.augmentations = []
@@ -330,7 +494,9 @@ class Augmentation(dict):
             if not value["active"]:
                 continue
             kw = {k: v for k, v in value.items() if k != "active"}
-            if key in UNSUPPORTED:
+            if key in enable:
+                self.augmentations.append(_SpecAug(device=device, **kw) if key == "spec_aug" else Speed(device=device, **kw))
+            elif key in UNSUPPORTED:
                 if unsupported == "raise":
                     raise NotImplementedError("augmentation '%s' is active and not built here (unsupported='skip' drops it)" % key)
                 self.skipped.append(key)
@@ -355,11 +521,13 @@ class Augmentation(dict):
         return self.process_batch([wav])[0]
 
     def process_batch(self, wavs):
-        """-> one float32 array per utterance: reverberated (len + 4095 samples) or with noise added, clipped and quantised"""
+        """-> one float32 array per utterance: reverberated (len + 4095 samples), with noise added, with blocks of its spectrum
+        zeroed (160 (len // 160) samples) or time-stretched (int(round(len / rate)) samples); clipped and quantised"""
+        import torch
         wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
         drawn = [self.draw(len(w)) for w in wavs]
         out = [None] * len(wavs)
-        for key in ("rir", "noise"):
+        for key in ("rir", "noise") + DEVICE_KEYS:
             rows = [i for i, (aug, _) in enumerate(drawn) if aug.key == key]
             if not rows:
                 continue
@@ -374,6 +542,14 @@ class Augmentation(dict):
                 h = self._rirs[aug.sample_rate].generate([drawn[i][1]["source"] for i in rows], [drawn[i][1]["receiver"] for i in rows])
                 y, ln = Reverb(self.device)(x, lens, h)
                 y = AddNoise(self.device)(y, ln, np.zeros((len(rows), int(y.shape[1])), np.float32), 0.0, quantise=True)
+                ln = ln.cpu().numpy()
+            elif key in DEVICE_KEYS:
+                aug = drawn[rows[0]][0]
+                if key == "spec_aug":
+                    y, ln = aug(x, lens, centres=[drawn[i][1]["centres"] for i in rows])
+                else:
+                    y, ln = aug(x, lens, rates=[drawn[i][1]["rate"] for i in rows])
+                y = AddNoise(self.device)(y, ln, torch.zeros_like(y), 0.0, quantise=True)
                 ln = ln.cpu().numpy()
             else:
                 d = np.zeros_like(x)
