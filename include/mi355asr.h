@@ -792,6 +792,51 @@ int mi355asr_phase_vocoder(const float* S_dev, const int32_t* frames_dev, int32_
                            int32_t win_length, int32_t hop, const double* rates_host, const int32_t* out_frames_host,
                            float* O_dev, int32_t Tpad, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- Ragged recursive (IIR) filters on second-order sections, and SignalMask -------------------------------------------
+ * replaces: scipy.signal.sosfilt / scipy.signal.sosfiltfilt per row, and with them augmentations/augments.py's SignalHz
+ * (scipy.signal.filtfilt of a 3rd-order Butterworth band-stop, plus uniform noise) and SignalMask.  Stateless.
+ *
+ * mi355asr_sos_ragged: x_dev [B, Lpad] of dtype MI355ASR_DT_F32 or MI355ASR_DT_I16 (x / 32768), len_dev i32 [B] (clamped to
+ * [0, Lpad]); sos_dev f64 [B, S, 6] -- or [1, S, 6], one filter for every row, when shared != 0 -- in SciPy's layout
+ * (b0 b1 b2 a0 a1 a2), 1 <= S <= 8; y_dev f32 [B, Opad].
+ *   mode 0: sosfilt(sos, x, zi=zi) per row.  zi_dev f64 [B, S, 2] (null: the zero state); zf_dev f64 [B, S, 2] (may be
+ *   null) receives the final state, which is zi for an empty row.  padlen is ignored.
+ *   mode 1: sosfiltfilt(sos, x, padtype="odd", padlen=padlen) per row, 0 <= padlen <= 1024: the odd extension (2 x[0] -
+ *   x[padlen .. 1], the row, the mirrored tail) is built inside the kernels; each pass starts from sosfilt_zi(sos) times
+ *   its first sample; forward, reversed, forward, reversed, the edges stripped.  zi_dev and zf_dev must be null
+ *   (MI355ASR_EINVAL otherwise).  A row with 0 < len <= padlen (SciPy raises there) is copied through, with the finish
+ *   below applied.
+ * The finish of a row: noise_dev f64 [B, Npad] (Npad >= Lpad), when not null, is added as y + noise_scale * noise in
+ * float64 (product and sum each rounded once); quantise != 0 applies trunc(clamp(y, -1, 1) * 32768) / 32768 to the
+ * float64 value; the result is rounded to float32 once.  Columns at or past len[b] (up to Opad) are written as 0.
+ * Samples and noise at or past len[b] are never read.
+ * All recursion arithmetic is float64 in direct form II transposed, one section at a time.  A row is cut into chunks of
+ * mi355asr_sos_chunk() samples at fixed positions of the extended row; a chunk's initial state comes from a sequential
+ * walk over the chunks' zero-state results with the chunk's 2 x 2 transition, itself obtained by running the recursion.
+ * No atomics: a row is the same bits in every run, in every batch and at every batch position.  Against a long-double
+ * evaluation y_ld of the same sections: |y - y_ld| <= 2^-24 |y_ld| + 8 D per sample, D = max |scipy - y_ld| over the row
+ * (at least 2^-50 max |x|); DESIGN.md section 21 has what was measured.
+ * The sections are read back before anything is launched (the call waits for `stream` once): a0 != 1 in any section is
+ * MI355ASR_EINVAL, as are S outside 1 .. 8, a null required pointer and padlen outside 0 .. 1024; y_dev is not touched
+ * then.  ws_dev (16-byte aligned, mi355asr_sos_workspace_bytes) holds the float64 intermediate signal and the chunk
+ * states.  Launches: 2 S + 1 in mode 0, 4 S + 2 in mode 1.
+ *
+ * mi355asr_mask_zone: SignalMask.augment per row: s = (int)(len zone_lo), e = (int)(len zone_hi) (float64 products,
+ * truncated; 0 <= zone <= 1); for s <= n < e with u = u_dev[b, n - s] (f64 [B, Upad]; Upad must cover e - s, a sample
+ * whose n - s is at or past Upad is left as it is): y = x m + (with_noise ? u (1 - m) : 0) in float64 with m = u <
+ * mask_ratio ? 0 : 1 -- the reference's expressions, so u where masked (0 without noise) and x elsewhere; outside the
+ * zone y = x.  Then the optional quantisation as above, one rounding to float32, zeros past len[b].  Exact: equal to the
+ * NumPy expressions bit for bit.  One launch. */
+int32_t mi355asr_sos_chunk(void);
+int mi355asr_sos_workspace_bytes(int32_t B, int64_t Lpad, int32_t S, int32_t mode, size_t* ws_bytes);
+int mi355asr_sos_ragged(const void* x_dev, int32_t dtype, const int32_t* len_dev, int32_t B, int64_t Lpad,
+                        const double* sos_dev, int32_t S, int32_t shared, int32_t mode, int32_t padlen,
+                        const double* zi_dev, double* zf_dev, const double* noise_dev, int64_t Npad, double noise_scale,
+                        int32_t quantise, float* y_dev, int64_t Opad, void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_mask_zone(const float* x_dev, const int32_t* len_dev, const double* u_dev, int32_t B, int64_t Lpad,
+                       int64_t Upad, double zone_lo, double zone_hi, double mask_ratio, int32_t with_noise,
+                       int32_t quantise, float* y_dev, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

@@ -182,6 +182,12 @@ SIGNATURES = {
     "mi355asr_spec_aug": (ctypes.c_int, [_P, _I, _P, _I, ctypes.c_int64, _P, _I, _P, _I, _P, ctypes.c_int64, _P, _SZ, _P]),
     "mi355asr_phase_vocoder_workspace_bytes": (ctypes.c_int, [_I, ctypes.POINTER(_SZ)]),
     "mi355asr_phase_vocoder": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _SZ, _P]),
+    "mi355asr_sos_chunk": (_I, []),
+    "mi355asr_sos_workspace_bytes": (ctypes.c_int, [_I, ctypes.c_int64, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_sos_ragged": (ctypes.c_int, [_P, _I, _P, _I, ctypes.c_int64, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64, ctypes.c_double,
+                                           _I, _P, ctypes.c_int64, _P, _SZ, _P]),
+    "mi355asr_mask_zone": (ctypes.c_int, [_P, _P, _P, _I, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          _I, _I, _P, _P]),
     "mi355asr_profile_enable": (ctypes.c_int, [_P, _I]),
     "mi355asr_profile_schemes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _I]),
     "mi355asr_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), _I, _I]),

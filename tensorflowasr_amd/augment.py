@@ -18,6 +18,12 @@ The reference's spectral augmentations that need an STFT and its inverse (csrc/s
 
     y, out_len = SpecAug(window=10, ratio=0.5)(x, lengths)        # row b: 160 (lengths[b] // 160) samples
     y, out_len = TimeStretch()(x, lengths, rates)                 # row b: int(round(lengths[b] / rates[b])) samples
+
+The two that work on the samples themselves (csrc/iir.hip, iir.py): `Hz` is SignalHz -- a 3rd-order Butterworth band-stop run
+forward and backward (scipy.signal.filtfilt) plus a little uniform noise -- and `Mask` is SignalMask; `enable=("hz", "masking")`.
+
+    y, out_len = Hz()(x, lengths, starts=[0.2, 0.5])              # row b: the band [starts[b], starts[b] + 0.3] of Nyquist removed
+    y, out_len = Mask("(0.1,0.9)", 0.3)(x, lengths)               # 30 % of the samples of the middle 80 % replaced by noise
 """
 import ctypes
 import random
@@ -423,7 +429,117 @@ class _SpecAug(SpecAug):
         return {"centres": SpecAug.draw(self, F)}
 
 
+class Hz:
+    """SignalHz on the device: scipy.signal.filtfilt of butter(3, [start, start + 0.3], "bandstop") plus 0.001 times uniform
+    noise, per row.  The filter runs as second-order sections in float64 (SOSFilter.sosfiltfilt with padlen = 21, which is
+    filtfilt's 3 max(len(a), len(b)); DESIGN.md section 21 has why the transfer-function form cannot be cut into chunks).  A row
+    of at most 21 samples, where SciPy raises, comes back unchanged (noise and quantisation still applied), as SpecAug returns a
+    row without a frame.  The last call's starts are kept in `last`."""
+    key = "hz"
+    PADLEN, WIDTH, NOISE = 21, 0.3, 0.001
+
+    def __init__(self, device="cuda:0"):
+        from .iir import SOSFilter
+        self.device = device
+        self.filter = SOSFilter(device)
+        self.last = None
+
+    @staticmethod
+    def draw_start():
+        return float(np.clip(np.random.random(), 0.01, 0.699))
+
+    def draw(self, n):
+        """the reference's np.random calls in its order: random() for the start, then random(n) for the noise"""
+        start = self.draw_start()
+        return {"start": start, "u": np.random.random(int(n))}
+
+    @staticmethod
+    def sections(start):
+        from scipy import signal            # lazy, as featurizers does: only the filter design needs SciPy
+        return signal.butter(3, [start, start + Hz.WIDTH], "bandstop", output="sos")
+
+    def __call__(self, x, lengths=None, starts=None, noise=None, quantise=False):
+        """x [L] or [B, L] float32 or int16; lengths [B] or None; starts: one number per row (or one for all), None: drawn per
+        row as np.clip(np.random.random(), 0.01, 0.699); noise: [B, L] float64 uniforms (scaled by 0.001 in the kernel), None:
+        drawn on the device, False: none -> (y [B, L] float32 on the device, out_len int32 [B] on the device: lengths)"""
+        import torch
+        x, L = _rows(x, self.device)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        if starts is None:
+            starts = [self.draw_start() for _ in range(B)]
+        starts = np.broadcast_to(np.asarray(starts, np.float64).reshape(-1), (B,)).copy()
+        if not ((starts > 0) & (starts + self.WIDTH < 1)).all():
+            raise ValueError("starts must lie in (0, %g), got %s" % (1 - self.WIDTH, starts))
+        self.last = starts
+        same = bool((starts == starts[0]).all())
+        sos = self.sections(starts[0]) if same else np.stack([self.sections(s) for s in starts])
+        if noise is None:
+            noise = torch.rand((B, int(x.shape[1])), dtype=torch.float64, device=self.device)
+        elif noise is False:
+            noise = None
+        y, _ = self.filter._run(x, ln, sos, 1, self.PADLEN, None, False, noise, self.NOISE, quantise, short_rows="copy")
+        return y, ln
+
+
+class Mask:
+    """SignalMask on the device: in the zone [int(len zone[0]), int(len zone[1])) of a row, the samples whose uniform draw u is
+    below mask_ratio are replaced by u itself (mask_with_noise) or by 0.  zone is a pair within [0, 1] or, as in the
+    reference's configuration, its text."""
+    key = "masking"
+
+    def __init__(self, zone="(0.1,0.9)", mask_ratio=0.3, mask_with_noise=True, device="cuda:0"):
+        if isinstance(zone, str):
+            import ast
+            zone = ast.literal_eval(zone)
+        self.zone = (float(zone[0]), float(zone[1]))
+        if not (0 <= self.zone[0] <= 1 and 0 <= self.zone[1] <= 1):
+            raise ValueError("zone = %s must lie within [0, 1]" % (zone,))
+        self.mask_ratio, self.mask_with_noise, self.device = float(mask_ratio), bool(mask_with_noise), device
+
+    def span(self, n):
+        """(s, e) of a row of n samples: Python's int() of the float64 products; e - s draws are used (none when e <= s)"""
+        return int(n * self.zone[0]), int(n * self.zone[1])
+
+    def draw(self, n):
+        """the reference's np.random call: random(e - s)"""
+        s, e = self.span(n)
+        return {"u": np.random.random(max(e - s, 0))}
+
+    def __call__(self, x, lengths=None, u=None, quantise=False):
+        """x [L] or [B, L] float32; lengths [B] or None; u: [B, >= e - s] float64 uniforms, or one array per row, None: drawn on
+        the device -> (y [B, L] float32 on the device, out_len int32 [B] on the device: lengths)"""
+        import torch
+        from . import _lib
+        x, L = _rows(x, self.device, allow_int16=False)
+        B, W = int(x.shape[0]), int(x.shape[1])
+        ln = _lengths(lengths, B, L, self.device)
+        if u is None:
+            u = torch.rand((B, W), dtype=torch.float64, device=self.device)
+        elif isinstance(u, (list, tuple)):
+            rows = [np.asarray(r, np.float64).reshape(-1) for r in u]
+            u = np.zeros((len(rows), max(1, max(len(r) for r in rows))), np.float64)
+            for b, r in enumerate(rows):
+                u[b, :len(r)] = r
+        if not torch.is_tensor(u):
+            u = torch.from_numpy(np.ascontiguousarray(np.asarray(u, np.float64)))
+        u = u.to(torch.float64).reshape(B, -1) if u.numel() else torch.zeros((B, 1), dtype=torch.float64)
+        spans = [self.span(int(n)) for n in ln.cpu().numpy()]
+        need = max([e - s for s, e in spans] + [0])
+        if u.shape[0] != B or u.shape[1] < need:
+            raise ValueError("u %s does not cover the zones of the batch: %d rows, up to %d draws" % (tuple(u.shape), B, need))
+        u = u.to(self.device).contiguous()
+        y = torch.empty((B, W), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mi355asr_mask_zone(_ptr(x), _ptr(ln), _ptr(u), B, W, int(u.shape[1]), self.zone[0], self.zone[1],
+                                                     self.mask_ratio, int(self.mask_with_noise), int(bool(quantise)), _ptr(y),
+                                                     _stream(self.device)))
+        self._keep = (x, ln, u)
+        return (y if L else y[:, :0]), ln
+
+
 DEVICE_KEYS = ("spec_aug", "speed")      # UNSUPPORTED keys that Augmentation(..., enable=) can run on the device
+SIGNAL_KEYS = ("hz", "masking")          # and the two that filter or mask the samples themselves (Hz, Mask)
 
 
 class _RirAug:
@@ -474,16 +590,17 @@ class Augmentation(dict):
     process_batch pick one active augmentation per utterance with random.sample and make the reference's `random` /
     `np.random` calls in its order, so a seeded run draws the reference's positions, segments and SNRs; the one deviation: a
     source drawn at the receiver is drawn again.  noise_bank: recordings to use instead of reading the `noises` list file.
-    enable: keys among spec_aug and speed to run on the device as well (SpecAug, Speed) instead of treating them as
-    unsupported; the default, none, leaves everything above as it is."""
+    enable: keys among spec_aug, speed, hz and masking to run on the device as well (SpecAug, Speed, Hz, Mask) instead of
+    treating them as unsupported; the default, none, leaves everything above as it is.  pitch (librosa's kaiser_best resampler)
+    and vc (TTS models) are not built."""
 
     def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0", enable=()):
         if unsupported not in ("raise", "skip"):
             raise ValueError("unsupported must be 'raise' or 'skip', got %r" % (unsupported,))
         enable = (enable,) if isinstance(enable, str) else tuple(enable)
         for key in enable:
-            if key not in DEVICE_KEYS:
-                raise ValueError("enable: %r is not one of %s" % (key, DEVICE_KEYS))
+            if key not in DEVICE_KEYS + SIGNAL_KEYS:
+                raise ValueError("enable: %r is not one of %s" % (key, DEVICE_KEYS + SIGNAL_KEYS))
         super().__init__(config or {})
         self.device = device
         self.augmentations = []
@@ -495,7 +612,8 @@ class Augmentation(dict):
                 continue
             kw = {k: v for k, v in value.items() if k != "active"}
             if key in enable:
-                self.augmentations.append(_SpecAug(device=device, **kw) if key == "spec_aug" else Speed(device=device, **kw))
+                cls = {"spec_aug": _SpecAug, "speed": Speed, "hz": Hz, "masking": Mask}[key]
+                self.augmentations.append(cls(device=device, **kw))
             elif key in UNSUPPORTED:
                 if unsupported == "raise":
                     raise NotImplementedError("augmentation '%s' is active and not built here (unsupported='skip' drops it)" % key)
@@ -522,12 +640,13 @@ class Augmentation(dict):
 
     def process_batch(self, wavs):
         """-> one float32 array per utterance: reverberated (len + 4095 samples), with noise added, with blocks of its spectrum
-        zeroed (160 (len // 160) samples) or time-stretched (int(round(len / rate)) samples); clipped and quantised"""
+        zeroed (160 (len // 160) samples), time-stretched (int(round(len / rate)) samples), band-stopped or masked (len samples);
+        clipped and quantised"""
         import torch
         wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
         drawn = [self.draw(len(w)) for w in wavs]
         out = [None] * len(wavs)
-        for key in ("rir", "noise") + DEVICE_KEYS:
+        for key in ("rir", "noise") + DEVICE_KEYS + SIGNAL_KEYS:
             rows = [i for i, (aug, _) in enumerate(drawn) if aug.key == key]
             if not rows:
                 continue
@@ -542,6 +661,16 @@ class Augmentation(dict):
                 h = self._rirs[aug.sample_rate].generate([drawn[i][1]["source"] for i in rows], [drawn[i][1]["receiver"] for i in rows])
                 y, ln = Reverb(self.device)(x, lens, h)
                 y = AddNoise(self.device)(y, ln, np.zeros((len(rows), int(y.shape[1])), np.float32), 0.0, quantise=True)
+                ln = ln.cpu().numpy()
+            elif key in SIGNAL_KEYS:
+                aug = drawn[rows[0]][0]
+                if key == "hz":
+                    u = np.zeros(x.shape, np.float64)
+                    for k, i in enumerate(rows):
+                        u[k, :lens[k]] = drawn[i][1]["u"]
+                    y, ln = aug(x, lens, starts=[drawn[i][1]["start"] for i in rows], noise=u, quantise=True)
+                else:
+                    y, ln = aug(x, lens, u=[drawn[i][1]["u"] for i in rows], quantise=True)
                 ln = ln.cpu().numpy()
             elif key in DEVICE_KEYS:
                 aug = drawn[rows[0]][0]
