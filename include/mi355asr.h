@@ -88,7 +88,10 @@ typedef struct {
                               *    reference, conformer_blocks.py:318-323: the n_dft/2+1 = 513 dB bins without the mel
                               *    matrix; n_mels is ignored and no freq2mel tensor exists)                        */
   int32_t add_wav_info;      /* speech_config.add_wav_info: 1 adds WavePickModel(waveform) (asr/models/wav_model.py:108-146)
-                              *    to the subsampled features (conformer_blocks.py:344-348); needs L % hop_size == 0   */
+                              *    to the subsampled features (conformer_blocks.py:344-348); needs L % hop_size == 0.
+                              *    Calls that run the encoder need at least 3 encoder frames per input (L > 2 * hop_size *
+                              *    reduction_factor samples, per chunk when streaming): the branch reflect-pads by two
+                              *    frames, which the reference defines for longer inputs only -- else MI355ASR_EINVAL */
 } mi355asr_config;
 
 const char* mi355asr_last_error(void);

@@ -54,6 +54,7 @@ int launch_gemm16(const mi355asr_model* m, int epi, bool ln, Gemm16Args& g, cons
 
 
 size_t wavpick_floats(const mi355asr_model* m, int Bp, int Lmax);
+constexpr int kWavMinFrames = 3;   // add_wav_info: the fewest encoder frames per input (REFLECT padding by 2, see encoder_impl)
 
 // Bp = number of independent encoder inputs (utterances, or utterances x blocks when streaming),
 // F mel frames and T encoder frames per input.
@@ -346,6 +347,15 @@ bool stream256_args(const mi355asr_model* m, int B, int T, const float* x, float
 
 int encoder_impl(mi355asr_model* m, const float* wav, const Geometry& g, const Plan& p, char* ws, float* enc_out,
                  hipStream_t s, const int32_t* wav_len, int32_t* enc_len) {
+  // add_wav_info: the residual stacks reflect-pad their input by two rows (wav_model.py:57-104), and tf.pad(..., "REFLECT")
+  // is defined for pad < size only -- below three frames the reference has no value, and the padded copies of run_wavpick
+  // outgrow their carve.  Refused before anything is launched.
+  if (m->cfg.add_wav_info && g.T < kWavMinFrames) {
+    const int per = m->dm.hop * m->cfg.reduction_factor;
+    return fail(MI355ASR_EINVAL, "add_wav_info: %d samples per %s give %d frames, the waveform branch's reflect padding needs at least "
+                "%d (a minimum length of %d samples)", g.Lb, m->cfg.chunk_size > 0 ? "chunk" : "utterance", g.T, kWavMinFrames,
+                (kWavMinFrames - 1) * per + 1);
+  }
   float* logp = (float*)(ws + p.logp);
   float* mel = (float*)(ws + p.mel);
   int rc = run_mel(m, wav, g.Bp, g.Lb, g.F, logp, (float*)(ws + p.pmax), (float*)(ws + p.umax), mel, s, wav_len);
