@@ -840,6 +840,40 @@ int mi355asr_mask_zone(const float* x_dev, const int32_t* len_dev, const double*
                        int64_t Upad, double zone_lo, double zone_hi, double mask_ratio, int32_t with_noise,
                        int32_t quantise, float* y_dev, void* stream);
 
+/* ---- Band-limited resampling at any real ratio, one ratio per row ----------------------------------------------------------
+ * replaces: resampy.resample(x, sr_in, sr_out, filter="kaiser_best") per row as librosa.effects.pitch_shift calls it, with
+ * librosa's fix_length behind it.  It follows the published algorithm (J. O. Smith's band-limited interpolation on a tabulated
+ * Kaiser-windowed sinc: 64 zero crossings, 512 entries per crossing, linear interpolation between entries); it has NOT been
+ * compared with the resampy or librosa packages, and the filter's four constants are quoted from resampy's documentation.
+ * Stateless.
+ *
+ * mi355asr_sinc_plan: tile = outputs per workgroup tile; wing = taps per wing at most at `ratio`, 32769 / (int)(min(1, ratio)
+ * 512); table_floats = floats of the table (32 772: win[0 .. 32768] in natural order, then three copies of win[32768]);
+ * ratio_min, ratio_max = the supported ratios, both inclusive (0.25 and 4).  tile, table_floats and the bounds are written
+ * whatever `ratio` is; a ratio that is not finite or outside the bounds is MI355ASR_EINVAL and leaves *wing alone.
+ *
+ * mi355asr_sinc_resample: x_dev f32 [B, Lpad]; on the host: ratios f64 [B] (sr_out / sr_in), len i64 [B] (0 .. Lpad),
+ * out_len i64 [B] (null: ceil(len ratio), the product in float64), off i64 [B] (may be null), valid i64 [B] (may be null:
+ * receives min(floor(len ratio), out_len), the outputs that are computed).  y_dev f32 [B, Opad].  With s = min(1, ratio)
+ * and step = (int)(512 s), output t < valid of a row is, with pos = t (1 / ratio) in float64, n = (int)pos, f = s (pos - n):
+ *     sum_{i < min(n + 1, (32769 - o) / step)} w(o + i step) x[n - i],  o = (int)(512 f), w(j) = win[j] + (512 f - o) (win[j + 1] - win[j])
+ *   + the same with f' = s - f over k < min(len - n - 1, (32769 - o') / step) and x[n + k + 1],
+ * times ratio when ratio < 1.  pos, n, o and 512 f - o are float64 or integers; weights, products and the sum are fp32 FMAs in
+ * that order into one accumulator: a row is the same bits alone, in any batch and in every run.  Outputs valid <= t <
+ * out_len are 0 (fix_length).  off null: row b holds its out_len[b] outputs from column 0 and zeros up to Opad.  off given:
+ * row b writes y[b, off[b] .. off[b] + out_len[b]) and nothing else of the row.  Samples at or past len[b] are never read.
+ * table_mode 0 keeps the table in LDS (one 1024-thread workgroup of 150 KiB per CU), 1 reads it through the caches: the
+ * same bits.  Against the float64 evaluation y64 of the same sums: |y - y64| <= 64 2^-24 sum_k |w_k x_k| per output.
+ * Refused as MI355ASR_EINVAL before anything is launched or copied: B outside 1 .. 65535, Lpad or Opad < 1, a ratio that is
+ * not finite or outside the bounds (named with the bounds), a length outside 0 .. Lpad, out_len < 0, off < 0 or off +
+ * out_len > Opad, a null required pointer, a table that is not 16-byte aligned.  ws_dev (8-byte aligned,
+ * mi355asr_sinc_workspace_bytes) receives the per-row parameters.  One launch, nothing is waited for. */
+int mi355asr_sinc_plan(double ratio, int32_t* tile, int32_t* wing, int32_t* table_floats, double* ratio_min, double* ratio_max);
+int mi355asr_sinc_workspace_bytes(int32_t B, size_t* ws_bytes);
+int mi355asr_sinc_resample(const float* x_dev, int32_t B, int64_t Lpad, const double* ratios_host, const int64_t* len_host,
+                           const int64_t* out_len_host, const int64_t* off_host, int64_t* valid_host, const float* table_dev,
+                           int32_t table_mode, float* y_dev, int64_t Opad, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

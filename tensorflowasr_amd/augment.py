@@ -24,6 +24,13 @@ forward and backward (scipy.signal.filtfilt) plus a little uniform noise -- and 
 
     y, out_len = Hz()(x, lengths, starts=[0.2, 0.5])              # row b: the band [starts[b], starts[b] + 0.3] of Nyquist removed
     y, out_len = Mask("(0.1,0.9)", 0.3)(x, lengths)               # 30 % of the samples of the middle 80 % replaced by noise
+
+`Pitch` is SignalPitch: librosa.effects.pitch_shift on the zone of a row, that is TimeStretch and then a band-limited resampler at
+an irrational ratio (csrc/sinc_resample.hip, resample.SincResampler).  The resampler restates the published algorithm behind
+resampy's kaiser_best and is pinned against the tests' float64 restatement of it, not against the resampy or librosa packages, so
+`Augmentation` runs the key only when asked with `unpinned=("pitch",)`.
+
+    y, out_len = Pitch("(0.2,0.8)")(x, lengths, steps=[-3, 2.5])  # the middle 60 % of row b shifted by steps[b] semitones
 """
 import ctypes
 import random
@@ -31,7 +38,7 @@ import random
 import numpy as np
 
 MAX_TAPS = 16384          # the longest filter mi355asr_fir_ragged takes, and the longest response mi355asr_rir_generate writes
-UNSUPPORTED = ("masking", "pitch", "speed", "hz", "vc", "spec_aug")     # the reference's other augmentations: not built here
+UNSUPPORTED = ("masking", "pitch", "speed", "hz", "vc", "spec_aug")     # the reference's other augmentations: off unless enable= / unpinned= name them
 KEYS = ("noise", "rir") + UNSUPPORTED
 
 
@@ -538,8 +545,92 @@ class Mask:
         return (y if L else y[:, :0]), ln
 
 
+class Pitch:
+    """SignalPitch on the device: librosa.effects.pitch_shift (librosa 0.9) on the zone [int(len zone[0]), int(len zone[1])) of a
+    row -- TimeStretch at rate = 2^(-steps / 12), then the band-limited resampler (resample.SincResampler) at the ratio `rate`
+    for ceil(len_stretched rate) samples, cut or zero-filled to the zone's length and written over the zone in the same launch.
+    Samples outside the zone keep the input's bits.  The resampler follows the published algorithm behind resampy's kaiser_best
+    and is pinned against the tests' float64 restatement of it; it has not been compared with the resampy or librosa packages
+    (DESIGN.md section 22).  A row whose rate is exactly 1.0 takes the stretched samples as they are (librosa's orig_sr ==
+    target_sr shortcut).  A zone of fewer than 1025 samples has no STFT frame: librosa raises there, here the row comes back
+    unchanged.  zone and factor are pairs or, as in the reference's configuration, their text.  The last call's steps are kept
+    in `last`."""
+    key = "pitch"
+    MIN_ZONE = 1025
+
+    def __init__(self, zone="(0.2,0.8)", sample_rate=16000, factor="(-1,5)", device="cuda:0"):
+        import ast
+        if isinstance(zone, str):
+            zone = ast.literal_eval(zone)
+        if isinstance(factor, str):
+            factor = ast.literal_eval(factor)
+        self.zone = (float(zone[0]), float(zone[1]))
+        self.factor = (float(factor[0]), float(factor[1]))
+        if not (0 <= self.zone[0] <= 1 and 0 <= self.zone[1] <= 1):
+            raise ValueError("zone = %s must lie within [0, 1]" % (zone,))
+        self.sample_rate, self.device = int(sample_rate), device
+        self.last = None
+        self._stretch = self._sinc = None
+
+    def span(self, n):
+        """(s, e) of a row of n samples: Python's int() of the float64 products"""
+        return int(n * self.zone[0]), int(n * self.zone[1])
+
+    def draw(self, n=None):
+        """the reference's np.random call: one random(), scaled to factor[1] - factor[0] and centred on 0"""
+        scale = self.factor[1] - self.factor[0]
+        return {"steps": float(np.random.random() * scale - scale / 2)}
+
+    @staticmethod
+    def rate(steps):
+        """librosa's 2.0 ** (-n_steps / bins_per_octave) with 12 bins per octave"""
+        return 2.0 ** (-float(steps) / 12)
+
+    def __call__(self, x, lengths=None, steps=None, quantise=False):
+        """x [L] or [B, L] float32; lengths [B] or None; steps: semitones, one number per row (or one for all), None: drawn per
+        row -> (y [B, L] float32 on the device, out_len int32 [B] on the device: lengths).  quantise: Augmentation.process's
+        clip and truncation to 16 bits, of the whole row."""
+        import torch
+        from .resample import SincResampler
+        if self._stretch is None:
+            self._stretch, self._sinc = TimeStretch(self.device), SincResampler(self.device)
+        x, L = _rows(x, self.device, allow_int16=False)
+        B = int(x.shape[0])
+        ln = _lengths(lengths, B, L, self.device)
+        lens = ln.cpu().numpy()
+        if steps is None:
+            steps = [self.draw()["steps"] for _ in range(B)]
+        steps = np.broadcast_to(np.asarray(steps, np.float64).reshape(-1), (B,)).copy()
+        if not np.isfinite(steps).all():
+            raise ValueError("steps must be finite, got %s" % (steps,))
+        self.last = steps
+        rates = np.array([self.rate(s) for s in steps], np.float64)
+        spans = [self.span(int(n)) for n in lens]
+        zl = np.array([e - s if e - s >= self.MIN_ZONE else 0 for s, e in spans], np.int64)     # 0: the row is left as it is
+        y = x.clone()
+        if zl.any():
+            self._sinc.ratios(rates[zl > 0], int((zl > 0).sum()))          # a rate outside the resampler's bounds: ValueError
+            Z = int(zl.max())
+            col = torch.arange(Z, device=self.device)[None, :] + torch.tensor([s for s, _ in spans], device=self.device)[:, None]
+            z = torch.gather(x, 1, col.clamp(max=int(x.shape[1]) - 1)).contiguous()
+            ys, ls = self._stretch(z, zl.astype(np.int32), rates)
+            ls = ls.cpu().numpy().astype(np.int64)
+            same = (rates == 1.0) & (zl > 0)
+            go = (zl > 0) & ~same
+            if go.any():
+                self._sinc.launch(ys.contiguous(), np.where(go, ls, 0), np.where(go, rates, 1.0), np.where(go, zl, 0),
+                                  np.array([s for s, _ in spans], np.int64), y)
+            for b in np.nonzero(same)[0]:
+                y[b, spans[b][0]:spans[b][1]] = ys[b, :zl[b]]
+        if quantise:
+            y = AddNoise(self.device)(y, ln, torch.zeros_like(y), 0.0, quantise=True)
+        return (y if L else y[:, :0]), ln
+
+
 DEVICE_KEYS = ("spec_aug", "speed")      # UNSUPPORTED keys that Augmentation(..., enable=) can run on the device
 SIGNAL_KEYS = ("hz", "masking")          # and the two that filter or mask the samples themselves (Hz, Mask)
+UNPINNED_KEYS = ("pitch",)               # Augmentation(..., unpinned=): on the device through a filter of the project's own
+#                                          restatement of the published algorithm, not pinned to the reference's library (Pitch)
 
 
 class _RirAug:
@@ -591,16 +682,23 @@ class Augmentation(dict):
     `np.random` calls in its order, so a seeded run draws the reference's positions, segments and SNRs; the one deviation: a
     source drawn at the receiver is drawn again.  noise_bank: recordings to use instead of reading the `noises` list file.
     enable: keys among spec_aug, speed, hz and masking to run on the device as well (SpecAug, Speed, Hz, Mask) instead of
-    treating them as unsupported; the default, none, leaves everything above as it is.  pitch (librosa's kaiser_best resampler)
-    and vc (TTS models) are not built."""
+    treating them as unsupported; the default, none, leaves everything above as it is.  unpinned: keys among UNPINNED_KEYS,
+    today ("pitch",), to run on the device through a filter that is the project's own restatement of the published algorithm
+    and is not pinned to the reference's library (Pitch: the resampler inside librosa's pitch_shift has not been compared with
+    the resampy package); without it an active pitch stays unsupported, and enable=("pitch",) stays a ValueError.  vc (TTS
+    models) is not built."""
 
-    def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0", enable=()):
+    def __init__(self, config=None, unsupported="raise", noise_bank=None, device="cuda:0", enable=(), unpinned=()):
         if unsupported not in ("raise", "skip"):
             raise ValueError("unsupported must be 'raise' or 'skip', got %r" % (unsupported,))
         enable = (enable,) if isinstance(enable, str) else tuple(enable)
         for key in enable:
             if key not in DEVICE_KEYS + SIGNAL_KEYS:
                 raise ValueError("enable: %r is not one of %s" % (key, DEVICE_KEYS + SIGNAL_KEYS))
+        unpinned = (unpinned,) if isinstance(unpinned, str) else tuple(unpinned)
+        for key in unpinned:
+            if key not in UNPINNED_KEYS:
+                raise ValueError("unpinned: %r is not one of %s" % (key, UNPINNED_KEYS))
         super().__init__(config or {})
         self.device = device
         self.augmentations = []
@@ -614,6 +712,8 @@ class Augmentation(dict):
             if key in enable:
                 cls = {"spec_aug": _SpecAug, "speed": Speed, "hz": Hz, "masking": Mask}[key]
                 self.augmentations.append(cls(device=device, **kw))
+            elif key in unpinned:
+                self.augmentations.append(Pitch(device=device, **kw))
             elif key in UNSUPPORTED:
                 if unsupported == "raise":
                     raise NotImplementedError("augmentation '%s' is active and not built here (unsupported='skip' drops it)" % key)
@@ -640,13 +740,13 @@ class Augmentation(dict):
 
     def process_batch(self, wavs):
         """-> one float32 array per utterance: reverberated (len + 4095 samples), with noise added, with blocks of its spectrum
-        zeroed (160 (len // 160) samples), time-stretched (int(round(len / rate)) samples), band-stopped or masked (len samples);
-        clipped and quantised"""
+        zeroed (160 (len // 160) samples), time-stretched (int(round(len / rate)) samples), band-stopped, masked or pitch-shifted
+        (len samples); clipped and quantised"""
         import torch
         wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
         drawn = [self.draw(len(w)) for w in wavs]
         out = [None] * len(wavs)
-        for key in ("rir", "noise") + DEVICE_KEYS + SIGNAL_KEYS:
+        for key in ("rir", "noise") + DEVICE_KEYS + SIGNAL_KEYS + UNPINNED_KEYS:
             rows = [i for i, (aug, _) in enumerate(drawn) if aug.key == key]
             if not rows:
                 continue
@@ -671,6 +771,9 @@ class Augmentation(dict):
                     y, ln = aug(x, lens, starts=[drawn[i][1]["start"] for i in rows], noise=u, quantise=True)
                 else:
                     y, ln = aug(x, lens, u=[drawn[i][1]["u"] for i in rows], quantise=True)
+                ln = ln.cpu().numpy()
+            elif key in UNPINNED_KEYS:
+                y, ln = drawn[rows[0]][0](x, lens, steps=[drawn[i][1]["steps"] for i in rows], quantise=True)
                 ln = ln.cpu().numpy()
             elif key in DEVICE_KEYS:
                 aug = drawn[rows[0]][0]

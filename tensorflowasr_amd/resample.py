@@ -8,6 +8,13 @@ float64 with NumPy alone and handed to the kernels of csrc/resample.hip as a pha
     srs = StreamResampler(64, 8000, 16000, max_packet=1280)
     new = srs.step([3, 5], [packet3, packet5])            # {slot: float32 samples that became final}
     tail = srs.flush([3])                                  # the rest, zero-extended; the slot is reset
+
+`SincResampler` is the resampler for ANY real ratio, one ratio per row (csrc/sinc_resample.hip): J. O. Smith's band-limited
+interpolation on a tabulated Kaiser-windowed sinc, the algorithm resampy's `kaiser_best` runs inside librosa.effects.pitch_shift.
+It follows the published algorithm and is pinned against the tests' float64 restatement of it; it has not been compared with
+the resampy or librosa packages, and the four filter constants below are quoted from resampy's documentation.
+
+    y, out_len = SincResampler()(x, lengths, ratios=[2 ** (-3 / 12), 1.19])   # row b: ceil(lengths[b] ratios[b]) samples
 """
 import ctypes
 from math import gcd
@@ -15,6 +22,8 @@ from math import gcd
 import numpy as np
 
 MAX_RATIO = 640          # max(up, down): the largest filter (12 801 taps, 11.025 kHz -> 16 kHz) the kernels hold in LDS
+# the windowed sinc of SincResampler: zero crossings, table entries per crossing, roll-off and Kaiser beta of resampy's kaiser_best
+SINC_ZEROS, SINC_NT, SINC_ROLLOFF, SINC_BETA = 64, 512, 0.9475937167399596, 14.769656459379492
 
 
 def ratio(sr_in, sr_out):
@@ -275,3 +284,130 @@ class StreamResampler(_Base):
             out = {s: yh[i, :n_out[i]].copy() for i, s in enumerate(slots)}
         self.reset(slots)
         return out
+
+
+def sinc_table():
+    """the right half of the interpolation filter in float64: 32 769 entries, win[0] = SINC_ROLLOFF"""
+    n = SINC_NT * SINC_ZEROS
+    return np.kaiser(2 * n + 1, SINC_BETA)[n:] * SINC_ROLLOFF * np.sinc(SINC_ROLLOFF * np.linspace(0, SINC_ZEROS, n + 1))
+
+
+def sinc_out_length(n, r):
+    """samples of the output of n input samples at ratio r: ceil(n r), the product in float64"""
+    return int(np.ceil(float(int(n)) * float(r)))
+
+
+def sinc_valid_length(n, r):
+    """outputs that are computed: floor(n r); the rest of a longer output is zero (librosa's fix_length)"""
+    return int(np.floor(float(int(n)) * float(r)))
+
+
+def _sinc_plan(lib, ratio=1.0):
+    v = [ctypes.c_int32() for _ in range(3)]
+    lo, hi = ctypes.c_double(), ctypes.c_double()
+    rc = lib.mi355asr_sinc_plan(float(ratio), *[ctypes.byref(c) for c in v], ctypes.byref(lo), ctypes.byref(hi))
+    plan = dict(tile=v[0].value, wing=v[1].value, table_floats=v[2].value, ratio_min=lo.value, ratio_max=hi.value)
+    if rc != 0:
+        raise ValueError("the ratio %r is outside the supported %g .. %g" % (ratio, lo.value, hi.value))
+    return plan
+
+
+class SincResampler:
+    """One launch per call for a ragged batch with a ratio per row; `tile` is the kernel's output tile, `ratio_min` and
+    `ratio_max` the supported ratios (mi355asr_sinc_plan).  table_mode 1 reads the table through the caches instead of LDS
+    (the same bits; for measurements)."""
+
+    def __init__(self, device="cuda:0", table_mode=0):
+        import torch
+        from . import _lib
+        self.lib = _lib.lib()
+        self.device = torch.device(device)
+        self.table_mode = int(table_mode)
+        self.plan = _sinc_plan(self.lib)
+        self.tile, self.ratio_min, self.ratio_max = self.plan["tile"], self.plan["ratio_min"], self.plan["ratio_max"]
+        self._table = None
+
+    def wing(self, ratio):
+        """taps per wing at most at this ratio; ValueError naming the ratio and the bounds"""
+        return _sinc_plan(self.lib, ratio)["wing"]
+
+    def ratios(self, ratios, B):
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(ratios, np.float64).reshape(-1), (B,)))
+        for b, v in enumerate(r):
+            if not (np.isfinite(v) and self.ratio_min <= v <= self.ratio_max):
+                raise ValueError("row %d: the ratio %r is outside the supported %g .. %g" % (b, float(v), self.ratio_min, self.ratio_max))
+        return r
+
+    def table(self):
+        import torch
+        if self._table is None:
+            tab = np.empty(self.plan["table_floats"], np.float32)
+            win = sinc_table().astype(np.float32)
+            tab[:len(win)] = win
+            tab[len(win):] = win[-1]
+            self._table = torch.from_numpy(tab).to(self.device)
+        return self._table
+
+    def launch(self, x, lens, ratios, out_lens, offs, y):
+        """the library call on prepared arguments: x, y float32 tensors on the device, the rest host arrays -> valid int64 [B]"""
+        import torch
+        from . import _lib
+        B = int(x.shape[0])
+        lens = np.ascontiguousarray(lens, np.int64)
+        out_lens = np.ascontiguousarray(out_lens, np.int64)
+        offs = None if offs is None else np.ascontiguousarray(offs, np.int64)
+        valid = np.zeros(B, np.int64)
+        wb = ctypes.c_size_t()
+        _lib.check(self.lib.mi355asr_sinc_workspace_bytes(B, ctypes.byref(wb)))
+        ws = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mi355asr_sinc_resample(
+                _ptr(x), B, int(x.shape[1]), hp(ratios), hp(lens), hp(out_lens), None if offs is None else hp(offs), hp(valid),
+                _ptr(self.table()), self.table_mode, _ptr(y), int(y.shape[1]), _ptr(ws), wb.value,
+                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._keep = (x, ws)                          # inputs of an asynchronous call
+        return valid
+
+    def __call__(self, x, lengths=None, ratios=1.0, out_lengths=None, out_pad=None):
+        """x [L] or [B, L] float32, NumPy or tensor; lengths [B] samples per row (None: L each); ratios: a number or [B], rate_out /
+        rate_in per row; out_lengths [B] (None: ceil(lengths ratios)) -> (y [B, Omax] float32 on the device, out_len int32 [B] on
+        the device).  Row b holds out_len[b] samples computed as if alone -- those from floor(lengths[b] ratios[b]) on are zero --
+        and zeros after them; Omax = the longest out_len, or `out_pad` columns when given (wider: zeros; narrower: cut).  A ratio
+        of 1 is a low-pass at SINC_ROLLOFF of Nyquist, not a copy."""
+        import torch
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x, np.float32))
+        elif not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        x = x.to(torch.float32)
+        if x.dim() == 1:
+            x = x.reshape(1, -1)
+        if x.dim() != 2:
+            raise ValueError("expected a waveform [L] or [B, L], got %s" % (tuple(x.shape),))
+        B, L = int(x.shape[0]), int(x.shape[1])
+        if B < 1:
+            raise ValueError("an empty batch")
+        if lengths is None:
+            lens = np.full(B, L, np.int64)
+        else:
+            lens = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).reshape(-1).astype(np.int64)
+            if len(lens) != B:
+                raise ValueError("%d rows, %d lengths" % (B, len(lens)))
+            if (lens < 0).any() or (lens > L).any():
+                raise ValueError("lengths must lie within 0 .. %d, got %s" % (L, lens))
+        r = self.ratios(ratios, B)
+        if out_lengths is None:
+            out = np.array([sinc_out_length(n, v) for n, v in zip(lens, r)], np.int64)
+        else:
+            out = np.asarray(out_lengths.cpu() if torch.is_tensor(out_lengths) else out_lengths).reshape(-1).astype(np.int64)
+            if len(out) != B or (out < 0).any():
+                raise ValueError("out_lengths: one per row and none negative, got %s" % (out,))
+        O = max(1, int(out.max()) if out_pad is None else int(out_pad))
+        out = np.minimum(out, O)
+        if L == 0:
+            x = torch.zeros((B, 1), dtype=torch.float32)
+        x = x.to(self.device).contiguous()
+        y = torch.empty((B, O), dtype=torch.float32, device=self.device)
+        self.launch(x, lens, r, out, None, y)
+        return y, torch.from_numpy(out.astype(np.int32)).to(self.device)
