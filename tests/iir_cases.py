@@ -1,5 +1,6 @@
 """The batch the GPU tests of the recursive filters and of Hz share, with its references computed once (iir_ref.py): rows around
-every chunk edge of the extended signal, per-row band-stops at the five starts, NaN past every row's length."""
+every chunk edge of the extended signal, per-row band-stops at the five starts, NaN past every row's length; and long_batch():
+the same past the first tile of the passes and past the first stage of the scan."""
 import functools
 
 import numpy as np
@@ -81,7 +82,58 @@ def tf_refs():
     return out
 
 
-FLIPS = [0, 0]                                  # samples checked / samples whose float32 is not the rounded long-double value
+W = 64 * 128                                    # kLanes * kChunk of iir.hip: the positions of one workgroup of sos_pass_kernel
+SC = 1024 * 128                                 # kScan * kChunk of iir.hip: the positions of one stage of sos_scan_kernel
+LONG_STARTS = (0.01, 0.699, 0.35)               # SciPy's hardest, worst and easiest band-stop here
+
+
+def long_lengths(which):
+    """samples per row.  "tiles": extended rows (N = L + 2 PADLEN) of W - 1, W, W + 1, 2 W and 2 W + 1 positions, and between
+    them rows of 22 and 3 C + 5 samples, which end in tile 0 and are filled in tiles 1 and 2.  "scan": extended rows of SC, SC + 1
+    and 2 SC + 5 positions (1024, 1025 and 2049 chunks: one, two and three stages of the scan), and one row of 6000."""
+    C, P = chunk(), 2 * PADLEN
+    assert W == 64 * C and SC == 1024 * C
+    if which == "tiles":
+        return [W - 1 - P, 22, W - P, 3 * C + 5, W + 1 - P, 22, 2 * W - P, 3 * C + 5, 2 * W + 1 - P]
+    assert which == "scan", which
+    return [SC - P, SC + 1 - P, 2 * SC + 5 - P, 6000]
+
+
+def long_rows(which):
+    """the rows of a long batch that leave tile 0"""
+    return [b for b, n in enumerate(long_lengths(which)) if n + 2 * PADLEN >= W - 1]
+
+
+@functools.lru_cache(maxsize=None)
+def long_batch(which):
+    """batch() past the first tile ("tiles") and past the first scan stage ("scan"): x float32 (NaN past lens), lens, starts (the
+    long rows cycle through LONG_STARTS in their order, and so do the short ones), u float64 uniforms (NaN past lens)"""
+    rng = np.random.default_rng({"tiles": 17, "scan": 19}[which])
+    lens = long_lengths(which)
+    rows = [(rng.uniform(-1, 1, n) * 0.5).astype(np.float32) for n in lens]
+    us = [rng.random(n) for n in lens]
+    starts, seen = [], [0, 0]
+    for n in lens:
+        k = int(n + 2 * PADLEN >= W - 1)
+        starts.append(LONG_STARTS[seen[k] % 3])
+        seen[k] += 1
+    return {"x": poisoned(rows, max(lens) + 7, np.float32), "lens": lens, "rows": [r.astype(np.float64) for r in rows], "starts": starts,
+            "sos": np.stack([sections(s) for s in starts]), "u": poisoned(us, max(lens) + 7, np.float64), "us": us}
+
+
+@functools.lru_cache(maxsize=None)
+def long_refs(which, shared_start=None):
+    """filtfilt_refs() of long_batch(which)"""
+    c = long_batch(which)
+    out = []
+    for b, x in enumerate(c["rows"]):
+        sos = sections(shared_start) if shared_start is not None else c["sos"][b]
+        y_ld = ir.sosfiltfilt_ld(sos, x, PADLEN)
+        out.append((y_ld, ir.distance(signal.sosfiltfilt(sos, x, padlen=PADLEN), y_ld, x)))
+    return out
+
+
+FLIPS = [0, 0]                                 # samples checked / samples whose float32 is not the rounded long-double value
 
 
 def check_bound(y, y_ld, D, extra=0.0):

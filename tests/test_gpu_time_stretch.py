@@ -30,12 +30,13 @@ def spectrum():
     return sr.stft(signal(rng, 30 * HOP + 100), N_FFT, N_FFT, HOP).astype(np.complex64)
 
 
-def vocoder(D, frames, rates):
-    """D complex64 [B, Fpad, bins] -> (O [B, Tpad, bins] NumPy, counts)"""
+def vocoder(D, frames, rates, geo=(N_FFT, N_FFT, HOP)):
+    """D complex64 [B, Fpad, bins] -> (O [B, Tpad, bins] NumPy, counts); Tpad is two frames more than the longest row's count"""
     torch = device()
     from tensorflowasr_amd import _lib
     lib = _lib.lib()
-    B = len(D)
+    B, BINS = len(D), geo[0] // 2 + 1
+    assert D.shape[2] == BINS
     rates = np.ascontiguousarray(rates, np.float64)
     tc = np.array([sr.stretch_frames(F, r) for F, r in zip(frames, rates)], np.int32)
     Tpad = int(tc.max()) + 2
@@ -46,7 +47,7 @@ def vocoder(D, frames, rates):
     _lib.check(lib.mi355asr_phase_vocoder_workspace_bytes(B, ctypes.byref(wb)))
     ws = torch.empty(wb.value // 8, dtype=torch.float64, device="cuda:0")
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _lib.check(lib.mi355asr_phase_vocoder(p(S), p(fr), B, S.shape[1], N_FFT, N_FFT, HOP, rates.ctypes.data_as(ctypes.c_void_p),
+    _lib.check(lib.mi355asr_phase_vocoder(p(S), p(fr), B, S.shape[1], *geo, rates.ctypes.data_as(ctypes.c_void_p),
                                           tc.ctypes.data_as(ctypes.c_void_p), p(O), Tpad, p(ws), wb.value, None))
     torch.cuda.synchronize()
     return O.cpu().numpy(), tc

@@ -188,6 +188,30 @@ def test_chunked_biquad_scan_stays_within_scipys_own_distance(start):
     assert err <= 8 * D
 
 
+@pytest.mark.parametrize("start", [0.01, 0.35, 0.699])
+def test_chunked_biquad_scan_meets_the_device_bound_past_a_tile_and_a_scan_stage(start):
+    """The float64 restatement at the kernel's chunk (128), rounded to float32 as the device rounds, under the device tests' own
+    bound at the extended lengths of tests/test_gpu_iir_tiles.py: the algorithm meets the bound there whatever the kernel does.
+    Measured on these rows, worst over the lengths, float64 err / D and max(err - 2^-24 |y_ld|, 0) / D after the rounding: 1.25
+    and 0.010 (start 0.01), 0.77 and 0 (0.35), 1.64 (N = W - 1) and 0.739 (N = 2 SC + 5) (0.699); the bound is 8.  The easiest
+    start leaves out SC and 2 SC + 5, which keeps the three cases near 10 s."""
+    from iir_cases import SC, W, check_bound
+    assert W == 64 * SOSFilter.CHUNK and SC == 1024 * SOSFilter.CHUNK
+    sos = signal.butter(3, [start, start + 0.3], "bandstop", output="sos")
+    rng = np.random.default_rng(29)
+    for N in (W - 1, W, W + 1, 2 * W + 1, SC, SC + 1, 2 * SC + 5):
+        if start == 0.35 and N in (SC, 2 * SC + 5):
+            rng.uniform(-1, 1, N - 42)                  # the later rows keep their draws
+            continue
+        x = (rng.uniform(-1, 1, N - 42) * 0.5).astype(np.float32).astype(np.float64)
+        y_ld = ir.sosfiltfilt_ld(sos, x, 21)
+        D = ir.distance(signal.sosfiltfilt(sos, x, padlen=21), y_ld, x)
+        y = ir.sosfiltfilt_chunked(sos, x, 21, SOSFilter.CHUNK)
+        err = float(np.abs(y - y_ld).max())
+        r = check_bound(y.astype(np.float32), y_ld, D)
+        print("start %g, N = %d: D = %.3g, float64 err = %.2f D, after rounding to float32: %.3f" % (start, N, D, err / D, r))
+
+
 def test_chunked_transfer_function_scan_fails():
     """The 6th-order direct-form recursion joined over chunks by its 6 x 6 transition is NOT usable: at start 0.699 the
     transition's entries reach 1.8e4 and the result is 3.7e-6 = 1 494 D away from the long-double evaluation (D = 2.5e-9).  Do not retry
