@@ -874,6 +874,34 @@ int mi355asr_sinc_resample(const float* x_dev, int32_t B, int64_t Lpad, const do
                            const int64_t* out_len_host, const int64_t* off_host, int64_t* valid_host, const float* table_dev,
                            int32_t table_mode, float* y_dev, int64_t Opad, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- Ragged edit distance with the substitution / deletion / insertion split -------------------------------------------------
+ * replaces: utils/xer.py:12-35 (`levenshtein`) and :211-220 (`wer`) per hypothesis / label pair, with the filtering
+ * am_tester.py:34-89 does in front of it.  Stateless.
+ *
+ * ref_dev i32 [B, max_ref], hyp_dev i32 [B, max_hyp]; ref_len_dev / hyp_len_dev i32 [B] on the device, clamped to the row
+ * width, null: the whole row counts.  Entries at or past a row's length are never read.  Per row, in this order: the
+ * hypothesis is cut before the first hyp_stop (use_stop != 0); the ids of drop_hyp_host[0 .. n_drop_hyp) are removed from the
+ * hypothesis and those of drop_ref_host[0 .. n_drop_ref) from the reference (host arrays of 0 .. 4 ids, read before the call
+ * returns).  With u the n filtered reference tokens and v the m filtered hypothesis tokens the table is
+ *     sub = prev[y-1] + (u != v), del = prev[y] + 1, ins = curr[y-1] + 1, best = min(sub, del, ins); the counts of a cell are
+ *     those of the substitution predecessor if best == sub, else of the deletion predecessor if best == del, else of the
+ *     insertion predecessor, plus the step; row 0 is all insertions, column 0 all deletions
+ * and out_dev i32 [B, 4] receives (distance, S, D, I) of cell (n, m): n == 0 gives (m, 0, 0, m), m == 0 gives (n, 0, n, 0).
+ * lens_dev i32 [B, 2] receives (n, m).  Integers: a row gives the same result alone, in any batch, at any position and in
+ * every run.  ops_dev u8 [B, max_ref + max_hyp] and n_ops_dev i32 [B] (both or neither): the alignment behind the counts,
+ * n_ops = n + I codes in forward order, 0 match, 1 substitution, 2 deletion, 3 insertion; the rest of the row is not written.
+ * Refused as MI355ASR_EINVAL before anything is launched, outputs untouched: B, max_ref or max_hyp < 1; max_ref or max_hyp
+ * above 16 384 (the counts are kept in 16 bits); with ops, max_ref * max_hyp above 2^24 cells; a drop set of more than 4 ids;
+ * a null required pointer; a workspace that is not 8-byte aligned.  The workspace (mi355asr_edit_distance_workspace_bytes, each
+ * part rounded up to 256 bytes) holds 16 B (max_ref + 1) bytes of strip boundary columns, 4 B (max_ref + max_hyp) bytes of
+ * filtered rows and, with ops, 4 B ceil(max_ref / 16) max_hyp bytes of per-cell choices.  One launch, one workgroup per row,
+ * nothing is waited for. */
+int mi355asr_edit_distance_workspace_bytes(int32_t B, int32_t max_ref, int32_t max_hyp, int32_t want_ops, size_t* ws_bytes);
+int mi355asr_edit_distance(const int32_t* ref_dev, const int32_t* ref_len_dev, const int32_t* hyp_dev, const int32_t* hyp_len_dev,
+                           int32_t B, int32_t max_ref, int32_t max_hyp, const int32_t* drop_ref_host, int32_t n_drop_ref,
+                           const int32_t* drop_hyp_host, int32_t n_drop_hyp, int32_t use_stop, int32_t hyp_stop, int32_t* out_dev,
+                           int32_t* lens_dev, uint8_t* ops_dev, int32_t* n_ops_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel (off by default).
  * profile_read waits for the recorded events, then returns accumulated milliseconds and launch counts per
  * kernel category below (arrays of at least MI355ASR_NUM_KERNELS); reset != 0 clears the accumulators.

@@ -192,6 +192,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "mi355asr_sinc_workspace_bytes": (ctypes.c_int, [_I, ctypes.POINTER(_SZ)]),
     "mi355asr_sinc_resample": (ctypes.c_int, [_P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I, _P, ctypes.c_int64, _P, _SZ, _P]),
+    "mi355asr_edit_distance_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_edit_distance": (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_profile_enable": (ctypes.c_int, [_P, _I]),
     "mi355asr_profile_schemes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _I]),
     "mi355asr_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), _I, _I]),

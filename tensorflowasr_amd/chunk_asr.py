@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from .eval import _Mean, wer
+from .eval import _Mean, update_from_device_scores, wer
 from .featurizers import SpeechFeaturizer, TextFeaturizer
 from .models import ChunkConformer, ctc_greedy_decode, frame_argmax
 
@@ -185,12 +185,16 @@ class ChunkAMTester(ChunkASR):
     SER / CER of the text ids with the S / I / D accumulators.  Batches are the 6-tuples of the reference's chunk loader
     (features, input_length, phone_labels, phone_label_length, tar_label, tar_label_length); 5-tuples of EvalList work too."""
 
-    def __init__(self, config, device="cuda:0", load_checkpoint=True):
+    def __init__(self, config, device="cuda:0", load_checkpoint=True, device_scoring=False):
         self.eval_metrics = {"ser": _Mean(), "cer": _Mean()}
         self.ctc_nums = [0, 0, 0, 0]
         self.steps, self.all_steps = 0, 0
         self.eval_datasets = None
         super().__init__(config, device=device, load_checkpoint=load_checkpoint)
+        self.device_scoring = bool(device_scoring)      # True: scoring.EditDistance, one call per batch (same results())
+        if self.device_scoring:
+            from .scoring import EditDistance
+            self.scorer = EditDistance(device)
 
     def set_all_steps(self, all_steps):
         self.all_steps = all_steps
@@ -202,6 +206,17 @@ class ChunkAMTester(ChunkASR):
         features, tar_label = batch[0], batch[4]
         logits, _ = self.runner.predict(features)
         B, Tp, V = logits.shape
+        pad = self.text_featurizer.pad
+        if self.device_scoring:
+            refs = np.asarray(tar_label).reshape(B, -1)
+            if Tp == 0:
+                ids = torch.zeros((B, 0), dtype=torch.int32, device=logits.device)
+            else:
+                ids, lens = ctc_greedy_decode(frame_argmax(logits), None, blank=V - 1)
+                ids = ids[:, :max(int(lens.max().item()), 1)].clamp(min=0)
+            update_from_device_scores(self.scorer(refs, ids, drop_ref=(pad,), drop_hyp=(pad,)), self.ctc_nums,
+                                      self.eval_metrics["ser"], self.eval_metrics["cer"])
+            return
         if Tp == 0:
             hyps = [[] for _ in range(B)]
         else:
@@ -209,7 +224,6 @@ class ChunkAMTester(ChunkASR):
             ids, lens = ctc_greedy_decode(frame_argmax(logits), None, blank=V - 1)
             ids = ids.clamp(min=0).cpu().numpy()
             hyps = [ids[b, :max(int(lens.max().item()), 1)].tolist() for b in range(B)]
-        pad = self.text_featurizer.pad
         for hyp, ref in zip(hyps, np.asarray(tar_label)):
             i = [int(t) for t in hyp if int(t) != pad]
             j = [int(t) for t in np.asarray(ref).flatten() if int(t) != pad]

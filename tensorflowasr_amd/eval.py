@@ -71,6 +71,20 @@ class _Mean:
         return self.total / self.count if self.count else 0.0
 
 
+def update_from_device_scores(scored, nums, ser, cer):
+    """`scored` = (result i32 [B, 4], lengths i32 [B, 2]) of scoring.EditDistance: what the host loops of the testers do with
+    `wer` per utterance -- nums = [n, s, i, d] accumulators, `ser` 1 for a non-zero distance, `cer` the running rate -- in
+    utterance order.  An empty reference raises ZeroDivisionError, as `wer` does."""
+    import torch
+    for dist, s, d, i, n, _ in torch.cat(scored, 1).cpu().tolist():
+        if n == 0:
+            raise ZeroDivisionError("division by zero: empty reference")
+        nums[0] += n; nums[1] += s; nums[2] += i; nums[3] += d
+        ser.update_state(1 if dist else 0)
+        cer.reset_states()
+        cer.update_state(sum(nums[1:]) / (nums[0] + 1e-6))
+
+
 # ---- asr/dataloaders/am_dataloader.py:118-227 (eval half) -----------------------------------------------------
 class EvalList:
     """Iterates a test list in batches the way `AM_DataLoader.eval_data_generator` builds them:
@@ -199,9 +213,10 @@ class AMTester(ASR):
     with_ctc_loss=True adds the `ctc_loss` metric of CTCTrainer._eval_step (asr/trainer/ctc_runners.py:125-150): the mean of
     tf.keras.backend.ctc_batch_cost(phone_labels, softmax(logits), input_length, phone_label_length) over the utterances."""
 
-    def __init__(self, config, device="cuda:0", load_checkpoint=True, with_ctc_loss=False):
+    def __init__(self, config, device="cuda:0", load_checkpoint=True, with_ctc_loss=False, device_scoring=False):
         self.config = config
         self.with_ctc_loss = bool(with_ctc_loss)
+        self.device_scoring = bool(device_scoring)      # True: scoring.EditDistance, one call per id stream (same results())
         self.eval_metrics = {k: _Mean() for k in ("phone_ser", "phone_cer", "txt_ser", "txt_cer")}
         if self.with_ctc_loss:
             self.eval_metrics["ctc_loss"] = _Mean()
@@ -210,6 +225,9 @@ class AMTester(ASR):
         self.steps, self.all_steps = 0, 0
         self.eval_datasets = None
         super().__init__(config, device=device, load_checkpoint=load_checkpoint)
+        if self.device_scoring:
+            from .scoring import EditDistance
+            self.scorer = EditDistance(device)
         self.output_file_path = os.path.join(self.running_config["outdir"], "test.tsv")
 
     def set_all_steps(self, all_steps):
@@ -238,8 +256,13 @@ class AMTester(ASR):
         ids, lens = ctc_greedy_decode(frame_ids, input_length, blank=self.phone_featurizer.num_classes - 1)
         ctc_decode = ids[:, :max(int(lens.max().item()), 1)].clamp_(min=0).contiguous()
         _, translator_out = self.translator([ctc_decode, enc_output], training=False, return_argmax=True)
-        ctc_decode, translator_out = ctc_decode.cpu().numpy(), translator_out.cpu().numpy()
         pad = self.phone_featurizer.pad
+        tpad, tend = self.text_featurizer.pad, self.text_featurizer.endid()
+        if self.device_scoring:
+            self._score_on_device(ctc_decode, phone_labels, (pad,), None, self.ctc_nums, "phone_ser", "phone_cer")
+            self._score_on_device(translator_out, tar_label, (tpad, tend), 1, self.translator_nums, "txt_ser", "txt_cer")
+            return
+        ctc_decode, translator_out = ctc_decode.cpu().numpy(), translator_out.cpu().numpy()
         for hyp, ref in zip(ctc_decode, np.asarray(phone_labels)):
             i, j = self._strip(hyp, (pad,)), self._strip(ref, (pad,))
             _, ws, wd, wi = wer(j, i)
@@ -247,7 +270,6 @@ class AMTester(ASR):
             self.eval_metrics["phone_ser"].update_state(0 if i == j else 1)
             self.eval_metrics["phone_cer"].reset_states()
             self.eval_metrics["phone_cer"].update_state(sum(self.ctc_nums[1:]) / (self.ctc_nums[0] + 1e-6))
-        tpad, tend = self.text_featurizer.pad, self.text_featurizer.endid()
         for hyp, ref in zip(translator_out, np.asarray(tar_label)):
             hyp = [int(t) for t in hyp]
             if 1 in hyp:
@@ -259,6 +281,12 @@ class AMTester(ASR):
             self.eval_metrics["txt_ser"].update_state(0 if i == j else 1)
             self.eval_metrics["txt_cer"].reset_states()
             self.eval_metrics["txt_cer"].update_state(sum(self.translator_nums[1:]) / (self.translator_nums[0] + 1e-6))
+
+    def _score_on_device(self, hyp, ref, drop, stop, nums, ser, cer):
+        """One scoring call for an id stream whose hypotheses stay on the device; the accumulators and metrics are then updated
+        in utterance order from one [B, 6] copy, as the host loop of _eval_step updates them."""
+        update_from_device_scores(self.scorer(ref, hyp, drop_ref=drop, drop_hyp=drop, hyp_stop=stop), nums,
+                                  self.eval_metrics[ser], self.eval_metrics[cer])
 
     def results(self):
         r = {k: v.result() for k, v in self.eval_metrics.items()}
