@@ -201,6 +201,36 @@ int mi355asr_ctc_align(const float* x_dev, int32_t is_logits, const int32_t* in_
                        int32_t* path_dev, int32_t* spans_dev, float* score_dev, void* ws_dev, size_t ws_bytes,
                        void* stream);
 
+/* replaces: tf.keras.losses.sparse_categorical_crossentropy(labels, logits, from_logits=True), tf.argmax(logits, -1) and the
+ * mask_loss / translate_acc of CTCTrainer (asr/trainer/ctc_runners.py:63-76, 102, 144-146), with d / d logits.
+ * Model-independent.  The logits row of (b, t), t < Q, is the V floats at x_dev + b * ld_b + t * ld_t (elements, not bytes), so
+ * a column slice logits[:, :Q] of a [B, T, V] tensor is ld_b = T * V, ld_t = V; ld_t >= V need not be a multiple of 4, rows
+ * that are not 16-byte aligned are read with narrower loads, and no element past V of a row or at t >= Q is read or written.
+ * labels_dev i32: the label of (b, t) at labels_dev + b * ld_lab + t.
+ * The rows entry: loss_dev f32 [B, Q] = logsumexp(x) - x[label]; argmax_dev i32 [B, Q] (may be NULL), ties to the lowest
+ * index; grad_dev (may be NULL; row (b, t) at grad_dev + b * gld_b + t * gld_t) = w * (softmax(x) - onehot(label)), w =
+ * weights_dev[b * Q + t] or 1 for NULL.  A label outside [0, V): loss NaN, arg-max as usual, gradient row 0 (TensorFlow raises
+ * on the CPU and returns NaN on a GPU).  x[label] = -inf with a finite maximum: loss +inf, gradient finite.
+ * The mask-loss entry runs the rows entry into its workspace and reduces in float64, one workgroup, in a fixed order, with
+ * need = (label != 0), zero = (label == 0):
+ *   mask_loss_dev f32 [B] = mean_t loss[b, t] + sum(loss need) / (sum(need) + 1e-6) + sum(loss zero) / (sum(zero) + 1e-6)
+ *   acc_dev f32 [1]       = sum((argmax == label) need) / (sum(need) + 1e-6)                        (translate_acc)
+ *   mean_dev f32 [1]      = the mean of loss over all B * Q elements                    (what the translate_loss metric keeps)
+ *   grad_dev (may be NULL) = d (sum_b upstream_dev[b] * mask_loss[b]) / d x; upstream_dev f32 [B], NULL = ones; it is read
+ *   only when grad_dev is given
+ * Returns -1 with a message that names the field, launching nothing and writing nothing, for a NULL required pointer, B or Q
+ * below 1, V outside 1 .. 262144, ld_t < V, ld_b < 0, ld_lab < Q, gld_t < V, gradient rows of two batch entries that would
+ * overlap, and a workspace smaller than the workspace entry says (B, Q, want_grad).  No allocation, no host synchronisation,
+ * no atomics; the results of a row are bit-identical from run to run, wherever the row lies and whatever else is in the batch. */
+int mi355asr_xent_workspace_bytes(int32_t B, int32_t Q, int32_t want_grad, size_t* bytes);
+int mi355asr_xent_rows(const float* x_dev, int64_t ld_b, int64_t ld_t, const int32_t* labels_dev, int32_t ld_lab,
+                       const float* weights_dev, int32_t B, int32_t Q, int32_t V, float* loss_dev, int32_t* argmax_dev,
+                       float* grad_dev, int64_t gld_b, int64_t gld_t, void* stream);
+int mi355asr_mask_loss(const float* x_dev, int64_t ld_b, int64_t ld_t, const int32_t* labels_dev, int32_t ld_lab,
+                       const float* upstream_dev, int32_t B, int32_t Q, int32_t V, float* mask_loss_dev, float* acc_dev,
+                       float* mean_dev, float* grad_dev, int64_t gld_b, int64_t gld_t, void* ws_dev, size_t ws_bytes,
+                       void* stream);
+
 /* replaces: ctc_beam_search_decoder_batch(probs_split, vocabulary, beam_size, num_processes, cutoff_prob,
  * cutoff_top_n, ext_scorer = nullptr) of externals/ctc_decoders (ctc_beam_search_decoder.cpp:18-187, 426-459;
  * SWIG entry decoders.i) -- the CTC prefix beam search without a scorer (with one: mi355asr_ctc_prefix_beam_lm* below).  Blank = class V-1, vocabulary = classes

@@ -74,6 +74,7 @@ class Mi355AsrError(RuntimeError):
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 _SZ = ctypes.c_size_t
+_L = ctypes.c_int64
 
 # name -> (restype, argtypes): every symbol include/mi355asr.h declares
 SIGNATURES = {
@@ -103,6 +104,9 @@ SIGNATURES = {
     "mi355asr_ctc_greedy": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "mi355asr_ctc_loss_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_ctc_loss": (ctypes.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi355asr_xent_workspace_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_xent_rows": (ctypes.c_int, [_P, _L, _L, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
+    "mi355asr_mask_loss": (ctypes.c_int, [_P, _L, _L, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _SZ, _P]),
     "mi355asr_ctc_align_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_ctc_align": (ctypes.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_ctc_prefix_beam_host": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),

@@ -211,15 +211,24 @@ class AMTester(ASR):
     """`AMTester(config)`: same models / checkpoints as `ASR`, evaluated over batches
     `(features [B,L,1], input_length [B], phone_labels [B,P], phone_label_length [B], text_labels [B,Q])`.
     with_ctc_loss=True adds the `ctc_loss` metric of CTCTrainer._eval_step (asr/trainer/ctc_runners.py:125-150): the mean of
-    tf.keras.backend.ctc_batch_cost(phone_labels, softmax(logits), input_length, phone_label_length) over the utterances."""
+    tf.keras.backend.ctc_batch_cost(phone_labels, softmax(logits), input_length, phone_label_length) over the utterances.
+    with_trainer_metrics=True adds the other three numbers of that step, updated as it updates them: `ctc_acc` (one value per
+    utterance), `translate_loss` (the mean of the cross-entropy of the Translator logits over all B x min(U, Q) elements) and
+    `translate_acc` (one scalar per step) -- from the logits of the one Translator call the step makes (losses.py); the inputs
+    of the last step are kept in `last_trainer_inputs`.  The decoded ids and their scoring are the same either way."""
 
-    def __init__(self, config, device="cuda:0", load_checkpoint=True, with_ctc_loss=False, device_scoring=False):
+    def __init__(self, config, device="cuda:0", load_checkpoint=True, with_ctc_loss=False, device_scoring=False,
+                 with_trainer_metrics=False):
         self.config = config
         self.with_ctc_loss = bool(with_ctc_loss)
+        self.with_trainer_metrics = bool(with_trainer_metrics)
         self.device_scoring = bool(device_scoring)      # True: scoring.EditDistance, one call per id stream (same results())
         self.eval_metrics = {k: _Mean() for k in ("phone_ser", "phone_cer", "txt_ser", "txt_cer")}
         if self.with_ctc_loss:
             self.eval_metrics["ctc_loss"] = _Mean()
+        if self.with_trainer_metrics:
+            self.eval_metrics.update((k, _Mean()) for k in ("ctc_acc", "translate_loss", "translate_acc"))
+        self.last_trainer_inputs = None
         self.ctc_nums = [0, 0, 0, 0]          # n, s, i, d
         self.translator_nums = [0, 0, 0, 0]
         self.steps, self.all_steps = 0, 0
@@ -255,7 +264,10 @@ class AMTester(ASR):
         # tf.keras.backend.ctc_decode treats the LAST class as the blank whatever `blank_at_zero` says (am_tester.py:38-40)
         ids, lens = ctc_greedy_decode(frame_ids, input_length, blank=self.phone_featurizer.num_classes - 1)
         ctc_decode = ids[:, :max(int(lens.max().item()), 1)].clamp_(min=0).contiguous()
-        _, translator_out = self.translator([ctc_decode, enc_output], training=False, return_argmax=True)
+        translator_logits, translator_out = self.translator([ctc_decode, enc_output], training=False, return_argmax=True,
+                                                            return_logits=self.with_trainer_metrics)
+        if self.with_trainer_metrics:
+            self._trainer_metrics(phone_labels, ctc_decode, tar_label, translator_logits)
         pad = self.phone_featurizer.pad
         tpad, tend = self.text_featurizer.pad, self.text_featurizer.endid()
         if self.device_scoring:
@@ -281,6 +293,18 @@ class AMTester(ASR):
             self.eval_metrics["txt_ser"].update_state(0 if i == j else 1)
             self.eval_metrics["txt_cer"].reset_states()
             self.eval_metrics["txt_cer"].update_state(sum(self.translator_nums[1:]) / (self.translator_nums[0] + 1e-6))
+
+    def _trainer_metrics(self, phone_labels, ctc_decode, tar_label, translator_logits):
+        """ctc_runners.py:144-150: ctc_acc masks with the TEXT featurizer's pad, as the reference does."""
+        from .losses import ctc_acc, translate_metrics
+        mean, acc = translate_metrics(tar_label, translator_logits)
+        accs = ctc_acc(phone_labels, ctc_decode, pad=self.text_featurizer.pad)
+        self.last_trainer_inputs = dict(phone_labels=phone_labels, ctc_decode=ctc_decode, tar_label=tar_label,
+                                        translator_logits=translator_logits)
+        for v in accs.cpu().numpy():
+            self.eval_metrics["ctc_acc"].update_state(v)
+        self.eval_metrics["translate_loss"].update_state(mean.item())
+        self.eval_metrics["translate_acc"].update_state(acc.item())
 
     def _score_on_device(self, hyp, ref, drop, stop, nums, ser, cer):
         """One scoring call for an id stream whose hypotheses stay on the device; the accumulators and metrics are then updated
