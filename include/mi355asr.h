@@ -231,6 +231,46 @@ int mi355asr_mask_loss(const float* x_dev, int64_t ld_b, int64_t ld_t, const int
                        float* mean_dev, float* grad_dev, int64_t gld_b, int64_t gld_t, void* ws_dev, size_t ws_bytes,
                        void* stream);
 
+/* replaces: TFMultiResolutionSTFT.call of vad/utils/stft.py (the wav_loss of VADTrainer) with d / d prediction, and the sums
+ * behind VADTrainer.mask_loss, tf.metrics.binary_accuracy and a binary F1 (vad/trainer/vad_trainer.py:42-48, 76-84).
+ * Model-independent.  Row b of the truth is the Lpad floats at truth_dev + b * ld_truth, of the prediction at pred_dev +
+ * b * ld_pred (elements; unit stride along the row, rows need not be aligned); len_dev i32 [B] (NULL: every row has Lpad
+ * samples) is clamped to 0 .. Lpad and no sample at or past it is read.  Resolution r of R (1 .. 4; host arrays) is
+ * (fft_lengths[r] in {512, 1024, 2048}, 1 <= frame_lengths[r] <= fft_lengths[r], 1 <= frame_steps[r] <= frame_lengths[r]) with
+ * tf.signal.stft semantics: frame f is the samples f * step .. f * step + frame_length - 1 times a periodic Hann window of
+ * frame_length, zero-padded at the end to fft_length; F = 1 + (len - frame_length) / step frames, 0 when len < frame_length.
+ * With p = sqrt(|P|^2 + 1e-7) + 1e-6 of the prediction and t of the truth (formed in float64 from fp32 spectra; both DFT stages
+ * on v_mfma_f32_16x16x4_f32 with float64-computed tables):
+ *   sc_dev f32 [B, R]     = ||p - t||_F / (||p||_F + 1e-6) over the row's frames and bins; 0 for a row without a frame
+ *   mag_dev f32 [B, R]    = the row's mean of (log p - log t)^2; NaN for a row without a frame
+ *   frames_dev i32 [B, R] = F
+ *   grad_dev (may be NULL; row b at grad_dev + b * ld_grad, Lpad elements, every one written) =
+ *     d / d prediction of sum_{b, r} (w_sc_dev[b * R + r] * sc[b, r] + w_mag_dev[b * R + r] * mag[b, r]); 0 at and past len and
+ *     where no frame reaches.  Where ||p - t|| == 0 the sc term contributes 0 (TensorFlow's gradient is NaN there); a resolution
+ *     at which the row has no frame contributes nothing.  The spectra are recomputed for the gradient, not stored.
+ * Frame sums, row sums and p, t, log are float64; sums have a fixed order (no atomics): a row's outputs are bit-identical from run
+ * to run, wherever the row lies and whatever else is in the batch.  The tables of a (device, fft_length, frame_length) are built
+ * and uploaded on first use (that call allocates and copies); afterwards no allocation and no host synchronisation.
+ * Returns -1 with a message, launching nothing, for a NULL required pointer, R outside 1 .. 4, an unsupported size, B outside
+ * 1 .. 65535, Lpad outside 1 .. 2^31 - 65537, a row stride below Lpad when B > 1, grad_dev without both weight arrays, a workspace
+ * that is not 16-byte aligned; -4 for a workspace smaller than the workspace entry says (same B, Lpad, resolutions, want_grad).
+ *
+ * mi355asr_vad_mask_stats: one launch (one workgroup) over labels and logits f32, element (b, t) at labels_dev + b * ld_lab + t and
+ * logits_dev + b * ld_x + t, t < counts_dev[b] (i32 [B], NULL: T; clamped to 0 .. T; nothing at or past it is read).  With
+ * loss = max(x, 0) - x z + log1p(exp(-|x|)), one = (z == 1), zero = (z == 0), float64 / int64 sums in a fixed order:
+ *   sums_dev f64 [4]       = sum loss * one, sum one, sum loss * zero, sum zero      (mask_loss: [0] / ([1] + 1e-6), [2] / ([3] + 1e-6))
+ *   counts_out_dev i64 [4] = TP, FP, FN, TN of the decision x > threshold (the raw logit, as binary_accuracy has it)
+ *   grad_dev (may be NULL; row b at grad_dev + b * ld_grad) = d (one_loss + zero_loss) / d x, 0 from counts_dev[b] on. */
+int mi355asr_stft_loss_workspace_bytes(int32_t B, int64_t Lpad, int32_t R, const int32_t* fft_lengths, const int32_t* frame_lengths,
+                                       const int32_t* frame_steps, int32_t want_grad, size_t* bytes);
+int mi355asr_stft_loss(const float* truth_dev, int64_t ld_truth, const float* pred_dev, int64_t ld_pred, const int32_t* len_dev,
+                       int32_t B, int64_t Lpad, int32_t R, const int32_t* fft_lengths, const int32_t* frame_lengths,
+                       const int32_t* frame_steps, float* sc_dev, float* mag_dev, int32_t* frames_dev, const float* w_sc_dev,
+                       const float* w_mag_dev, float* grad_dev, int64_t ld_grad, void* ws_dev, size_t ws_bytes, void* stream);
+int mi355asr_vad_mask_stats(const float* labels_dev, int64_t ld_lab, const float* logits_dev, int64_t ld_x, const int32_t* counts_dev,
+                            int32_t B, int32_t T, float threshold, double* sums_dev, int64_t* counts_out_dev, float* grad_dev,
+                            int64_t ld_grad, void* stream);
+
 /* replaces: ctc_beam_search_decoder_batch(probs_split, vocabulary, beam_size, num_processes, cutoff_prob,
  * cutoff_top_n, ext_scorer = nullptr) of externals/ctc_decoders (ctc_beam_search_decoder.cpp:18-187, 426-459;
  * SWIG entry decoders.i) -- the CTC prefix beam search without a scorer (with one: mi355asr_ctc_prefix_beam_lm* below).  Blank = class V-1, vocabulary = classes

@@ -107,6 +107,9 @@ SIGNATURES = {
     "mi355asr_xent_workspace_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_xent_rows": (ctypes.c_int, [_P, _L, _L, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "mi355asr_mask_loss": (ctypes.c_int, [_P, _L, _L, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _SZ, _P]),
+    "mi355asr_stft_loss_workspace_bytes": (ctypes.c_int, [_I, _L, _I, _P, _P, _P, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_stft_loss": (ctypes.c_int, [_P, _L, _P, _L, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _SZ, _P]),
+    "mi355asr_vad_mask_stats": (ctypes.c_int, [_P, _L, _P, _L, _P, _I, _I, ctypes.c_float, _P, _P, _P, _L, _P]),
     "mi355asr_ctc_align_workspace_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_ctc_align": (ctypes.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi355asr_ctc_prefix_beam_host": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),

@@ -335,3 +335,52 @@ class AMTester(ASR):
                                if hasattr(self.eval_datasets, "eval_per_epoch_steps") else 1)
         self._eval_batches()
         return self.results()
+
+
+class VADTester:
+    """What `VADTrainer._eval_step` (vad/trainer/vad_trainer.py:76-84) keeps for the online VAD model, on the GPU: per step
+    vad_loss = one_loss + zero_loss of mask_loss on the speech logits, wav_loss = the multi-resolution STFT loss between the
+    clean waveform and the voice-mask head's output, vad_acc = binary_accuracy (the raw logit against the threshold), plus the
+    binary F1 from the same counts.  The reference's own VadTester cannot run as written (it reads
+    running_config['voice_thread'], which no config has, and calls .result of None), so F1 is the ordinary
+    2 TP / (2 TP + FP + FN) and the reference does not pin it.
+
+        tester = VADTester(VAD().load_saved_model(path))
+        for x, vad_label, wav_label in batches:          # [B, T, 80], [B, T, 1], [B, T, 80] at 8 kHz, as the dataloader yields
+            tester.update(x, vad_label, wav_label)
+        tester.results()                                  # {'vad_loss', 'wav_loss', 'vad_acc', 'f1'}: the means over the steps
+
+    The step values stay on the device; `results` is the one place that copies to the host."""
+
+    def __init__(self, vad, threshold=0.5, stft_loss=None):
+        from . import losses
+        self.vad = vad
+        self.threshold = float(threshold)
+        self.stft_loss = stft_loss if stft_loss is not None else losses.MultiResolutionSTFTLoss(device=vad.device)
+        self._losses = losses
+        self.reset()
+
+    def reset(self):
+        self._steps = {"vad_loss": [], "wav_loss": [], "vad_acc": [], "f1": []}
+
+    def update(self, x, vad_label, wav_label, lengths=None):
+        """x [B, T, 80] noisy 8 kHz frames, vad_label [B, T, 1] (or [B, T]) in {0, 1}, wav_label [B, T, 80] clean frames;
+        `lengths`: valid frames per row (None: all T).  -> this step's values as device scalars."""
+        import torch
+        xt = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
+        if xt.dim() != 3:
+            raise ValueError("x is [B, T, 80] (got shape %s)" % (tuple(xt.shape),))
+        B, T, frame = xt.shape
+        samples = None if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(B) * frame
+        enhanced, logits = self.vad.enhance(xt.reshape(B, T * frame), lengths=samples, sample_rate=8000)
+        one, zero = self._losses.vad_mask_loss(vad_label, logits, lengths=lengths)
+        m = self._losses.vad_metrics(vad_label, logits, threshold=self.threshold, lengths=lengths)
+        wav = self.stft_loss(wav_label, enhanced, lengths=samples)
+        step = {"vad_loss": one + zero, "wav_loss": wav, "vad_acc": m["acc"], "f1": m["f1"]}
+        for k, v in step.items():
+            self._steps[k].append(v)
+        return step
+
+    def results(self):
+        import torch
+        return {k: float(torch.stack(v).to(torch.float64).mean().item()) if v else float("nan") for k, v in self._steps.items()}

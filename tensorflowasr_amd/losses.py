@@ -8,6 +8,14 @@
     acc = translate_acc(labels, logits)                                  # f32 scalar
     accs = ctc_acc(phone_labels, decoded, pad=0)                         # f32 [B]
 
+The VAD trainer's losses (vad/trainer/vad_trainer.py, vad/utils/stft.py; `mi355asr_stft_loss`, `mi355asr_vad_mask_stats`,
+csrc/stft_loss.hip):
+
+    wav_loss = MultiResolutionSTFTLoss()(wav_label, enhanced)            # f32 scalar, TFMultiResolutionSTFT.call
+    wav_loss, grad = MultiResolutionSTFTLoss()(wav_label, enhanced, return_grad=True)
+    one, zero = vad_mask_loss(vad_label, logits)                         # VADTrainer.mask_loss
+    m = vad_metrics(vad_label, logits)                                   # acc (binary_accuracy), f1, tp, fp, fn, tn
+
 Everything returned is a device tensor; nothing here copies to the host or waits for the stream."""
 import ctypes
 
@@ -156,3 +164,203 @@ def ctc_acc(labels, decoded, pad=0):
     mask = (y != float(pad)).to(torch.float32)
     value = (y == d).to(torch.float32)
     return (value * mask).sum(-1) / (mask.sum(-1) + 1e-6)
+
+
+# ---- the VAD trainer's losses ----------------------------------------------------------------------------------------------------------
+OLA_TILE = 256                  # kLossOlaTile of csrc/stft_loss.hip: gradient samples per workgroup of the overlap-add
+FRAMES_PER_WORKGROUP = 1        # one frame of one row per workgroup of the frame kernel
+MAX_RESOLUTIONS = 4
+FFT_LENGTHS = (512, 1024, 2048)
+
+
+def _wave(t, dev, what):
+    """[B, L] or the trainer's [B, T, frame] -> f32 [B, L] on the device with unit stride along L (a strided view is used in place)"""
+    x = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+    if x.dim() == 3:
+        x = x.reshape(x.shape[0], -1)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("%s is [B, L] or [B, T, frame] (got shape %s)" % (what, tuple(x.shape)))
+    x = x.to(device=dev, dtype=torch.float32)
+    if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x
+
+
+def _counts(lengths, B, dev):
+    if lengths is None:
+        return None
+    n = lengths if torch.is_tensor(lengths) else torch.from_numpy(np.asarray(lengths, dtype=np.int32))
+    n = n.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if n.numel() != B:
+        raise ValueError("lengths holds %d values for %d rows" % (n.numel(), B))
+    return n
+
+
+class MultiResolutionSTFTLoss:
+    """TFMultiResolutionSTFT of vad/utils/stft.py on the GPU.  Per resolution r = (fft_length, frame_length, frame_step), with
+    P, T = tf.signal.stft(prediction), tf.signal.stft(truth) (periodic Hann of frame_length at the start of the FFT frame, no
+    centring, F = 1 + (L - frame_length) // step frames) and p = sqrt(|P|^2 + 1e-7) + 1e-6, t likewise:
+        sc[b, r]  = ||p_b - t_b||_F / (||p_b||_F + 1e-6)      (the denominator is the PREDICTED magnitude, as the reference has it)
+        mag[b, r] = mean over the row's frames and bins of (log p - log t)^2
+    The scalar is mean_r(mean_b sc) + mean_r(mean over all valid frames of the batch of (log p - log t)^2): with equal lengths
+    exactly TFMultiResolutionSTFT.call(y_true, y_pred).  1 to 4 resolutions, fft_length 512, 1024 or 2048,
+    1 <= frame_length <= fft_length, 1 <= frame_step <= frame_length; anything else is a ValueError."""
+
+    def __init__(self, fft_lengths=(1024, 512), frame_lengths=(600, 250), frame_steps=(120, 50), device="cuda:0"):
+        fft, fl, st = [int(v) for v in fft_lengths], [int(v) for v in frame_lengths], [int(v) for v in frame_steps]
+        if not (len(fft) == len(fl) == len(st)) or not 1 <= len(fft) <= MAX_RESOLUTIONS:
+            raise ValueError("1 to %d resolutions, the three lists of equal length (got %d, %d, %d)" % (MAX_RESOLUTIONS, len(fft), len(fl), len(st)))
+        for n, l, s in zip(fft, fl, st):
+            if n not in FFT_LENGTHS:
+                raise ValueError("fft_length %d is not one of %s" % (n, FFT_LENGTHS))
+            if not 1 <= l <= n:
+                raise ValueError("need 1 <= frame_length <= fft_length (got %d, %d)" % (l, n))
+            if not 1 <= s <= l:
+                raise ValueError("need 1 <= frame_step <= frame_length (got %d, %d)" % (s, l))
+        self.resolutions = list(zip(fft, fl, st))
+        self.R = len(fft)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.Mi355AsrError("the losses run on the GPU only (got device %s)" % self.device)
+        arr = ctypes.c_int32 * self.R
+        self._fft, self._fl, self._st = arr(*fft), arr(*fl), arr(*st)
+
+    def _call(self, y_true, y_pred, lengths, w_sc=None, w_mag=None, grad=None):
+        """one `mi355asr_stft_loss` on [B, L] device tensors -> (sc, mag, frames); `grad` f32 [B, >= L] is written when given"""
+        lib = _lib.lib()
+        dev = self.device
+        t, p = _wave(y_true, dev, "y_true"), _wave(y_pred, dev, "y_pred")
+        if t.shape != p.shape:
+            raise ValueError("y_true %s and y_pred %s differ in shape" % (tuple(t.shape), tuple(p.shape)))
+        B, L = t.shape
+        n = _counts(lengths, B, dev)
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.mi355asr_stft_loss_workspace_bytes(B, L, self.R, self._fft, self._fl, self._st, int(grad is not None), ctypes.byref(nbytes)))
+        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+        sc = torch.empty((B, self.R), dtype=torch.float32, device=dev)
+        mag = torch.empty((B, self.R), dtype=torch.float32, device=dev)
+        frames = torch.empty((B, self.R), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.mi355asr_stft_loss(_p(t), t.stride(0), _p(p), p.stride(0), _p(n), B, L, self.R, self._fft, self._fl, self._st,
+                                              _p(sc), _p(mag), _p(frames), _p(w_sc), _p(w_mag), _p(grad),
+                                              grad.stride(0) if grad is not None else 0, _p(ws), nbytes.value, st))
+        return sc, mag, frames
+
+    def rows(self, y_true, y_pred, lengths=None):
+        """-> sc f32 [B, R], mag f32 [B, R] (NaN for a row without a frame at that resolution, where sc is 0), frames i32 [B, R].
+        A row is computed from its own samples below lengths[b] alone."""
+        return self._call(y_true, y_pred, lengths)
+
+    def grad_rows(self, y_true, y_pred, w_sc, w_mag, lengths=None, out=None):
+        """d / d y_pred of sum_{b, r} (w_sc[b, r] sc[b, r] + w_mag[b, r] mag[b, r]) for caller-given coefficients f32 [B, R]
+        -> (sc, mag, frames, grad f32 [B, L]).  Every element of the gradient is written: 0 at and past lengths[b] and where no
+        frame reaches.  Where ||p - t|| == 0 the sc term contributes 0 (TensorFlow's gradient is NaN there); a resolution at
+        which the row has no frame contributes nothing.  `out`: a caller-owned f32 [B, >= L] buffer with unit stride."""
+        dev = self.device
+        p = _wave(y_pred, dev, "y_pred")
+        B, L = p.shape
+        w = [torch.as_tensor(v, dtype=torch.float32, device=dev).reshape(B, self.R).contiguous() for v in (w_sc, w_mag)]
+        grad = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=dev)
+        sc, mag, frames = self._call(y_true, p, lengths, w[0], w[1], grad)
+        return sc, mag, frames, grad[:, :L]
+
+    def _weights(self, frames, upstream):
+        f = frames.to(torch.float64)
+        B = f.shape[0]
+        tot = f.sum(0, keepdim=True)
+        w_mag = torch.where(tot > 0, f / (self.R * tot), torch.zeros_like(f))
+        w_sc = torch.full_like(f, 1.0 / (self.R * B))
+        if upstream is not None:
+            u = torch.as_tensor(upstream, dtype=torch.float64, device=f.device).reshape(())
+            w_sc, w_mag = w_sc * u, w_mag * u
+        return w_sc, w_mag, tot
+
+    def _scalar(self, sc, mag, frames):
+        w_sc, w_mag, tot = self._weights(frames, None)
+        m = torch.where(frames > 0, mag.to(torch.float64), torch.zeros((), dtype=torch.float64, device=mag.device))
+        v = (w_sc * sc.to(torch.float64)).sum() + (w_mag * m).sum()
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=mag.device)
+        return torch.where((tot > 0).all(), v, nan).to(torch.float32)      # a resolution without any frame: the mean of nothing
+
+    def __call__(self, y_true, y_pred, lengths=None, return_grad=False, upstream=None):
+        """-> the reference's scalar (f32, on the device); with return_grad also upstream * d scalar / d y_pred, f32 with the
+        [B, L] shape of the flattened input (upstream: a scalar, None = 1).  With ragged `lengths` the mag term of a resolution
+        is the mean over all valid frames of the batch: w_mag[b, r] = F[b, r] / (R sum_b F[b, r]), w_sc = 1 / (R B).
+        The coefficients depend on the frame counts alone, which follow from the lengths: they are formed on the device before
+        the one C call, and nothing waits for the stream."""
+        if not return_grad:
+            return self._scalar(*self._call(y_true, y_pred, lengths))
+        p = _wave(y_pred, self.device, "y_pred")
+        B, L = p.shape
+        n = _counts(lengths, B, self.device)
+        Lb = torch.full((B,), L, dtype=torch.int64, device=self.device) if n is None else n.to(torch.int64).clamp(0, L)
+        zero = torch.zeros_like(Lb)
+        frames = torch.stack([torch.where(Lb >= fl, 1 + (Lb - fl) // st, zero) for _, fl, st in self.resolutions], 1)
+        w_sc, w_mag, _ = self._weights(frames, upstream)
+        sc, mag, frames, grad = self.grad_rows(y_true, p, w_sc, w_mag, n)
+        return self._scalar(sc, mag, frames), grad
+
+
+def _mask_stats(labels, logits, lengths, threshold, return_grad):
+    lib = _lib.lib()
+    dev = _device_of(logits, None)
+    if dev.type != "cuda":
+        raise _lib.Mi355AsrError("the losses run on the GPU only (got device %s)" % dev)
+
+    def two_d(t, what):
+        x = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+        if x.dim() == 3 and x.shape[2] == 1:
+            x = x[:, :, 0]
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("%s is [B, T] or [B, T, 1] (got shape %s)" % (what, tuple(x.shape)))
+        x = x.to(device=dev, dtype=torch.float32)
+        if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
+            x = x.contiguous()
+        return x
+    z, x = two_d(labels, "labels"), two_d(logits, "logits")
+    if z.shape != x.shape:
+        raise ValueError("labels %s and logits %s differ in shape" % (tuple(z.shape), tuple(x.shape)))
+    B, T = x.shape
+    n = _counts(lengths, B, dev)
+    sums = torch.empty((4,), dtype=torch.float64, device=dev)
+    cnt = torch.empty((4,), dtype=torch.int64, device=dev)
+    grad = torch.empty((B, T), dtype=torch.float32, device=dev) if return_grad else None
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mi355asr_vad_mask_stats(_p(z), z.stride(0), _p(x), x.stride(0), _p(n), B, T, float(threshold), _p(sums), _p(cnt),
+                                               _p(grad), T, st))
+    return sums, cnt, grad
+
+
+def vad_mask_stats(labels, logits, lengths=None, threshold=0.5, return_grad=False):
+    """One launch over labels and logits f32 [B, T] (or [B, T, 1]); frames t >= lengths[b] take no part.
+    -> sums f64 [4] = (sum loss*one, sum one, sum loss*zero, sum zero) with loss = max(x, 0) - x z + log1p(exp(-|x|)),
+    one = (z == 1), zero = (z == 0); counts i64 [4] = (TP, FP, FN, TN) of the decision logit > threshold against one / zero;
+    with return_grad also d (one_loss + zero_loss) / d logits f32 [B, T] (0 past a row's count)."""
+    sums, cnt, grad = _mask_stats(labels, logits, lengths, threshold, return_grad)
+    return (sums, cnt, grad) if return_grad else (sums, cnt)
+
+
+def vad_mask_loss(labels, logits, lengths=None, return_grad=False):
+    """VADTrainer.mask_loss (vad_trainer.py:42-48): loss = binary_crossentropy(y, logits, from_logits=True),
+    one_loss = sum(loss * [y == 1]) / (sum[y == 1] + 1e-6) over the WHOLE batch, zero_loss likewise with [y == 0]
+    -> (one_loss, zero_loss) f32 scalars on the device (vad_loss is their sum); with return_grad also
+    d (one_loss + zero_loss) / d logits.  The sums are taken in float64 on the device."""
+    sums, _, grad = _mask_stats(labels, logits, lengths, 0.5, return_grad)
+    one = (sums[0] / (sums[1] + 1e-6)).to(torch.float32)
+    zero = (sums[2] / (sums[3] + 1e-6)).to(torch.float32)
+    return (one, zero, grad) if return_grad else (one, zero)
+
+
+def vad_metrics(labels, logits, threshold=0.5, lengths=None):
+    """-> dict of device scalars: acc = mean(binary_accuracy(y, logits)) of the trainer, which compares the RAW logit with the
+    threshold (logit > 0.5, not the probability); f1 = 2 TP / (2 TP + FP + FN), 0 when that denominator is 0; tp, fp, fn, tn
+    (i64).  The reference's VadTester cannot run as written (it reads a config key no config has and calls .result of None), so
+    F1 is the ordinary binary F1 from these counts; the reference does not pin it."""
+    _, c, _ = _mask_stats(labels, logits, lengths, threshold, False)
+    tp, fp, fn, tn = c[0], c[1], c[2], c[3]
+    cf = c.to(torch.float64)
+    den = 2 * cf[0] + cf[1] + cf[2]
+    f1 = torch.where(den > 0, 2 * cf[0] / torch.clamp(den, min=1.0), torch.zeros_like(den))
+    return {"acc": ((cf[0] + cf[3]) / cf.sum()).to(torch.float32), "f1": f1.to(torch.float32), "tp": tp, "fp": fp, "fn": fn, "tn": tn}
