@@ -741,6 +741,54 @@ int mi355asr_punc_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t T,
  * activations in the workspace, whatever T and B are.  T > max_tokens is MI355ASR_EINVAL before anything is launched. */
 int mi355asr_punc_forward(mi355asr_model* m, const int32_t* ids_dev, const int32_t* len_dev, int32_t B, int32_t T,
                           float* probs_dev, int32_t* cls_dev, float* pmax_dev, void* ws_dev, size_t ws_bytes, void* stream);
+/* The model's training outputs: PuncTransformer.call([inp, mask], training=False) as PuncTrainer._eval_step runs it (no dropout).
+ * ids_dev, len_dev, B, T, the workspace and the limits as in mi355asr_punc_forward (the workspace entry returns the same size).
+ *   logits_dev f32 [B, T, classes] (may be NULL): bd_output, the values mi355asr_punc_forward takes its softmax of; they go
+ *     through the folded 64 x 64 matrix as inference does.
+ *   feature_dev f32 [B, T, 768] (may be NULL): bert_out = to_bert(enc_output) from the unfolded to_bert/kernel [64, 768] and its
+ *     bias, exact fp32 on the MFMA.
+ * At least one of the two is non-NULL (else MI355ASR_EINVAL, before anything is launched).  Rows at or past len[b] are written as
+ * zeros (the reference computes values there; every loss below masks them).  A row's result depends on its own length alone.
+ * mi355asr_punc_forward on the same handle is not affected: same kernel, same bits as before. */
+int mi355asr_punc_heads_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t T, size_t* bytes);
+int mi355asr_punc_heads(mi355asr_model* m, const int32_t* ids_dev, const int32_t* len_dev, int32_t B, int32_t T,
+                        float* logits_dev, float* feature_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* replaces: PuncTrainer.classes_loss, classes_acc and bert_feature_loss (punc_recover/trainer/punc_trainer.py:93-126) with the
+ * gradients with respect to the model's two outputs.  Model-independent (csrc/punc_loss.hip).
+ *
+ * mi355asr_punc_classes_loss: label (b, t) at labels_dev + b * ld_lab + t (i32, Q columns), logit (b, t, c) at logits_dev +
+ * b * ld_b + t * ld_t + c (f32, T tokens, C <= 64 classes, unit stride over c).  The first Q' = min(T, Q) columns of both are
+ * used.  With xe = logsumexp(logits) - logits[label], m = (label != 0), m1 = m * (label != 1), N = sum m, N1 = sum m1:
+ *   loss_dev f32 [B]    = sum(xe m) / (N + 1e-6) + sum(xe m1) / (N1 + 1e-6)
+ *   acc_dev f32 [B]     = sum((argmax == label) m) / N -- no epsilon, as the reference has none: NaN for a row without a label;
+ *                         ties go to the lowest index
+ *   acc_mean_dev f32 [1] = the mean of acc_dev over the batch (classes_acc)
+ *   grad_dev (may be NULL; (b, t, c) at grad_dev + b * gld_b + t * gld_t + c, every element of [B, T, C] written) =
+ *     upstream[b] * (m / (N + 1e-6) + m1 / (N1 + 1e-6)) * (softmax - onehot); upstream_dev f32 [B] or NULL (ones); zeros for
+ *     t >= Q', where label == 0 and where the label is outside [0, C) (there the loss is NaN, as in mi355asr_xent_rows).
+ * The logits of a token whose label is 0 are not read.  One launch (one workgroup per row, a lane per token; the lane walks its
+ * token's row twice for the loss and once more for the gradient, out of L1), then a one-wave launch for the batch mean.  C > 64 is MI355ASR_EINVAL.
+ *
+ * mi355asr_masked_feature_mse: real (b, t, f) at real_dev + b * rld_b + t * rld_t + f (T1 tokens), pred likewise with pld_b,
+ * pld_t (T2 tokens); F >= 1 features with unit stride, rows need not be aligned (aligned rows are read 16 bytes per lane).
+ * T = min(T1, T2), k = (real != -10) per element (an exact float compare), cnt = sum_f k:
+ *   out_dev f32 [B] = mean over t < T of sum_f (real - pred)^2 k / (cnt + 1e-6); a token without an unmasked element counts in
+ *     the mean with 0, as in the reference
+ *   grad_dev (may be NULL; (b, t, f) at grad_dev + b * gld_b + t * gld_t + f, every element of [B, T2, F] written) =
+ *     upstream[b] * 2 (pred - real) k / ((cnt + 1e-6) T); 0 for t >= T and where real == -10.
+ * ws_dev: mi355asr_masked_feature_mse_workspace_bytes(B, T1, T2) bytes, 8-byte aligned (the row values, float64).
+ * Both: every sum is float64 in a fixed order without atomics; a row of a batch gives the bits it gives alone.  No allocation,
+ * no host synchronisation.  -1 with a message, launching nothing, for a NULL required pointer, a size below 1, B * T >= 2^31 -
+ * 65536 or strides that let rows overlap; -4 for a workspace that is too small. */
+int mi355asr_punc_classes_loss(const int32_t* labels_dev, int64_t ld_lab, const float* logits_dev, int64_t ld_b, int64_t ld_t,
+                               const float* upstream_dev, int32_t B, int32_t Q, int32_t T, int32_t C, float* loss_dev,
+                               float* acc_dev, float* acc_mean_dev, float* grad_dev, int64_t gld_b, int64_t gld_t, void* stream);
+int mi355asr_masked_feature_mse_workspace_bytes(int32_t B, int32_t T1, int32_t T2, size_t* bytes);
+int mi355asr_masked_feature_mse(const float* real_dev, int64_t rld_b, int64_t rld_t, const float* pred_dev, int64_t pld_b,
+                                int64_t pld_t, const float* upstream_dev, int32_t B, int32_t T1, int32_t T2, int32_t F,
+                                float* out_dev, float* grad_dev, int64_t gld_b, int64_t gld_t, void* ws_dev, size_t ws_bytes,
+                                void* stream);
 
 /* ---- Polyphase resampling (scipy.signal.resample_poly, default Kaiser filter) ------------------------------------
  * replaces: the host resampling of utils/speech_featurizers.py read_raw_audio (librosa.load at another rate).

@@ -172,6 +172,11 @@ SIGNATURES = {
     "mi355asr_punc_limits": (ctypes.c_int, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mi355asr_punc_workspace_bytes": (ctypes.c_int, [_P, _I, _I, ctypes.POINTER(_SZ)]),
     "mi355asr_punc_forward": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mi355asr_punc_heads_workspace_bytes": (ctypes.c_int, [_P, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_punc_heads": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi355asr_punc_classes_loss": (ctypes.c_int, [_P, _L, _P, _L, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P]),
+    "mi355asr_masked_feature_mse_workspace_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mi355asr_masked_feature_mse": (ctypes.c_int, [_P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _P, _P, _L, _L, _P, _SZ, _P]),
     "mi355asr_resample_plan": (ctypes.c_int, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mi355asr_resample": (ctypes.c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _I, _P, _P, ctypes.c_int64, _P]),
     "mi355asr_resample_streams_bytes": (ctypes.c_int, [_I, _I, _I, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),

@@ -13,6 +13,9 @@
 // Activations are four [Tp, 64] buffers (row stride kLd) plus the key mask.  A sentence of up to kLdsTokens tokens keeps them in
 // LDS; a longer one runs the same code on its region of the caller's workspace (global memory, workgroup barriers between the
 // steps).  Which of the two a row takes depends on its own length alone, so a row's result does not depend on its batch.
+// punc_heads_kernel (mi355asr_punc_heads) is the same walk compiled with HEADS: where the encoder stack ends it also multiplies
+// enc_output by the UNFOLDED to_bert [64, 768] (the trainer's distillation feature; 48 column tiles over the eight waves, straight
+// to global memory), and at the end it writes the logits in place of their softmax.  punc_kernel is the HEADS = false instance.
 #include <cfloat>
 
 #include "common.h"
@@ -44,6 +47,9 @@ constexpr size_t kDenseFloats = kMat + kD;                      // packed matrix
 constexpr size_t kLayerFloats = 6 * kMat + 6 * kD + 4 * kD;     // wq wk wv wo w1 w2 | their biases | g1 b1 g2 b2
 constexpr size_t kLayerBias = 6 * kMat, kLayerLn = 6 * kMat + 6 * kD;
 constexpr size_t kConvFloats = 3 * kMat + kD;
+// the unfolded to_bert (the distillation feature of mi355asr_punc_heads) lies behind pos_encoding: [to_bert | its bias]
+constexpr int kBert = 768;
+constexpr size_t kBertFloats = (size_t)kD * kBert + kBert;
 
 struct PuncArgs {
   const int32_t* ids;     // [B, T]
@@ -56,6 +62,10 @@ struct PuncArgs {
   size_t ws_row;
   size_t o_conv, o_fold, o_map, o_head, o_emb, o_pe;
   int B, T, n_enc, n_map, vocab, classes;
+  // the training outputs (punc_heads_kernel); appended, so the inference kernel's arguments keep their places
+  float* logits;          // [B, T, classes] or null
+  float* feature;         // [B, T, kBert] or null
+  size_t o_bert;
 };
 
 enum { ACT_NONE, ACT_RELU, ACT_ELU };
@@ -101,6 +111,40 @@ DEV void mm64(const float* in, float* out, const float* res, const float* wp, co
       if (ACT == ACT_ELU) v = v > 0.f ? v : expm1f(v);
       if (RES) v += res[at];
       out[at] = v;
+    }
+  }
+}
+
+// out[i][n] = sum_k in[i][k] W[k][n] + bias[n] for the rows i < len and the kBert columns of to_bert, written to global memory (row
+// stride kBert): wave w takes the column tiles w, w + 8, ..., keeps a tile's four weight fragments in registers over the rows
+// and adds k in the order mm64 does
+DEV void to_bert(const float* in, float* out, const float* wp, const float* bias, int len, int Tp) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, h = lane >> 4;
+  constexpr int G = kD / 16;
+  for (int ct = w; ct < kBert / 16; ct += kWaves) {
+    const f32x4* wpw = reinterpret_cast<const f32x4*>(wp) + (size_t)ct * G * 64 + lane;
+    f32x4 bv[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) bv[g] = wpw[g * 64];
+    const int col = 16 * ct + r;
+    const float bb = bias[col];
+    for (int m = 0; m < Tp / 16; ++m) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* a = in + (16 * m + r) * kLd + 4 * h;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(a + 16 * g);
+        acc = mfma4(av.x, bv[g].x, acc);
+        acc = mfma4(av.y, bv[g].y, acc);
+        acc = mfma4(av.z, bv[g].z, acc);
+        acc = mfma4(av.w, bv[g].w, acc);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = 16 * m + 4 * h + j;
+        if (row < len) out[(size_t)row * kBert + col] = acc[j] + bb;
+      }
     }
   }
 }
@@ -200,7 +244,10 @@ DEV void encoder_layer(const float* X, float* Qb, float* Kb, float* Vb, const fl
   __syncthreads();
 }
 
-// the whole network over one sentence; `act` is LDS or the sentence's workspace region (the address space is inferred per call)
+// the whole network over one sentence; `act` is LDS or the sentence's workspace region (the address space is inferred per call).
+// HEADS: the training outputs in place of the probabilities -- to_bert(enc_output) from the unfolded weights, and the logits the
+// softmax would take
+template <bool HEADS>
 DEV void punc_sentence(const PuncArgs& a, int b, int len, float* act) {
   const int tid = threadIdx.x, sub = tid & 15;
   const int Tp = (len + 15) & ~15;
@@ -234,6 +281,11 @@ DEV void punc_sentence(const PuncArgs& a, int b, int len, float* act) {
     __syncthreads();
     const int t = bx; bx = bk; bk = t;
   }
+  if constexpr (HEADS) {
+    // enc_output is read here and by the fold below; neither writes it
+    if (a.feature)
+      to_bert(buf(bx), a.feature + (size_t)b * a.T * kBert, a.w + a.o_bert, a.w + a.o_bert + (size_t)kD * kBert, len, Tp);
+  }
   mm64<1, ACT_NONE, false>(buf(bx), buf(bk), nullptr, a.w + a.o_fold, a.w + a.o_fold + kMat, Tp);
   __syncthreads();
   { const int t = bx; bx = bk; bk = t; }
@@ -246,6 +298,13 @@ DEV void punc_sentence(const PuncArgs& a, int b, int len, float* act) {
   // softmax over the classes, the arg-max of the probabilities as written (the lowest class on a tie) and its value
   const float* lg = buf(bk);
   const int C = a.classes;
+  if constexpr (HEADS) {
+    if (a.logits) {
+      float* out = a.logits + (size_t)b * a.T * C;
+      for (int i = tid; i < len * C; i += kThreads) out[i] = lg[(i / C) * kLd + i % C];
+    }
+    return;
+  }
   for (int t = tid >> 4; t < len; t += kThreads / 16) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(lg + t * kLd + 4 * sub);
     float x[4] = {v.x, v.y, v.z, v.w};
@@ -306,9 +365,29 @@ __global__ __launch_bounds__(kThreads) void punc_kernel(PuncArgs a) {
   }
   if (len == 0) return;
   if (len <= kLdsTokens)
-    punc_sentence(a, b, len, punc_lds);
+    punc_sentence<false>(a, b, len, punc_lds);
   else
-    punc_sentence(a, b, len, a.ws + (size_t)b * a.ws_row);
+    punc_sentence<false>(a, b, len, a.ws + (size_t)b * a.ws_row);
+}
+
+// the same walk with the training outputs (mi355asr_punc_heads): logits and / or the to_bert feature, zeros at and past the length
+__global__ __launch_bounds__(kThreads) void punc_heads_kernel(PuncArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int len = a.T;
+  if (a.lens) len = min(max(a.lens[b], 0), a.T);
+  {
+    const size_t row = (size_t)b * a.T + len;
+    const size_t rest = (size_t)(a.T - len);
+    if (a.logits)
+      for (size_t i = tid; i < rest * a.classes; i += kThreads) a.logits[row * a.classes + i] = 0.f;
+    if (a.feature)
+      for (size_t i = tid; i < rest * kBert; i += kThreads) a.feature[row * kBert + i] = 0.f;
+  }
+  if (len == 0) return;
+  if (len <= kLdsTokens)
+    punc_sentence<true>(a, b, len, punc_lds);
+  else
+    punc_sentence<true>(a, b, len, a.ws + (size_t)b * a.ws_row);
 }
 
 // weights [taps][64 in][n_out <= 64 out] -> fragments [column tile][tap][group g][lane][j] = W[tap][16 g + 4 (lane >> 4) + j][16 ct + (lane & 15)],
@@ -323,6 +402,18 @@ void pack_mat(const float* w, int taps, int n_out, float* p) {
             const int k = 16 * g + 4 * (lane >> 4) + j, n = 16 * ct + (lane & 15);
             p[((((size_t)ct * taps + tap) * G + g) * 64 + lane) * 4 + j] = n < n_out ? w[((size_t)tap * kD + k) * n_out + n] : 0.f;
           }
+}
+
+// to_bert [64 in][kBert out] -> fragments [column tile][group g][lane][j] = W[16 g + 4 (lane >> 4) + j][16 ct + (lane & 15)]
+void pack_bert(const float* w, float* p) {
+  const int G = kD / 16;
+  for (int ct = 0; ct < kBert / 16; ++ct)
+    for (int g = 0; g < G; ++g)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 4; ++j) {
+          const int k = 16 * g + 4 * (lane >> 4) + j, n = 16 * ct + (lane & 15);
+          p[(((size_t)ct * G + g) * 64 + lane) * 4 + j] = w[(size_t)k * kBert + n];
+        }
 }
 
 int map_layers(int num_layers) { return std::max(num_layers - 1, 1); }
@@ -358,10 +449,11 @@ int allow_lds() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
   if (!allowed_on[dev]) {
-    if (hipFuncSetAttribute((const void*)punc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget) != hipSuccess) {
-      (void)hipGetLastError();
-      return -1;
-    }
+    for (const void* k : {(const void*)punc_kernel, (const void*)punc_heads_kernel})
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+      }
     allowed_on[dev] = true;
   }
   return 0;
@@ -378,7 +470,7 @@ int finalize_punc(mi355asr_model* m, hipStream_t s) {
   const int n_enc = c.num_layers, n_map = map_layers(c.num_layers);
   const size_t o_conv = kDenseFloats + (size_t)n_enc * kLayerFloats, o_fold = o_conv + (size_t)n_enc * kConvFloats,
                o_map = o_fold + kDenseFloats, o_head = o_map + (size_t)n_map * kLayerFloats, o_emb = o_head + kDenseFloats,
-               o_pe = o_emb + (size_t)c.vocab * kD, total = o_pe + (size_t)c.pe_input * kD;
+               o_pe = o_emb + (size_t)c.vocab * kD, o_bert = o_pe + (size_t)c.pe_input * kD, total = o_bert + kBertFloats;
   std::vector<float> arena(total, 0.f);
   pack_mat(m->host["encoder/dense/kernel"].data.data(), 1, kD, arena.data());
   std::memcpy(arena.data() + kMat, m->host["encoder/dense/bias"].data.data(), kD * sizeof(float));
@@ -408,6 +500,9 @@ int finalize_punc(mi355asr_model* m, hipStream_t s) {
     }
     pack_mat(w.data(), 1, kD, arena.data() + o_fold);
     std::memcpy(arena.data() + o_fold + kMat, bias.data(), kD * sizeof(float));
+    // ... and to_bert as it is, for the distillation feature (mi355asr_punc_heads)
+    pack_bert(w19.data(), arena.data() + o_bert);
+    std::memcpy(arena.data() + o_bert + (size_t)kD * kBert, b19.data(), kBert * sizeof(float));
   }
   pack_mat(m->host["final/kernel"].data.data(), 1, c.classes, arena.data() + o_head);
   std::memcpy(arena.data() + o_head + kMat, m->host["final/bias"].data.data(), c.classes * sizeof(float));
@@ -476,22 +571,21 @@ int mi355asr_punc_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t T,
   return 0;
 }
 
-int mi355asr_punc_forward(mi355asr_model* m, const int32_t* ids, const int32_t* lens, int32_t B, int32_t T, float* probs,
-                          int32_t* cls, float* pmax, void* ws, size_t ws_bytes, void* stream) {
-  if (!m || !m->is_punc) return fail(MI355ASR_EINVAL, "not a Punc handle");
+// the checks and the launch both entry points share; `a` arrives with its output pointers set, heads = punc_heads_kernel
+static int punc_launch(mi355asr_model* m, const int32_t* ids, const int32_t* lens, int32_t B, int32_t T, PuncArgs a, bool heads,
+                       void* ws, size_t ws_bytes, void* stream) {
   if (!m->finalized) return fail(MI355ASR_ESTATE, "weights not finalised: call mi355asr_finalize_weights first");
   if (B < 1 || T < 1) return fail(MI355ASR_EINVAL, "B and T must be positive (got %d, %d)", B, T);
   if (T > m->pcfg.pe_input) return fail(MI355ASR_EINVAL, "T=%d exceeds the longest sentence (pe_input=%d)", T, m->pcfg.pe_input);
-  if (!ids || !probs) return fail(MI355ASR_EINVAL, "null argument");
+  if (!ids || (!heads && !a.probs)) return fail(MI355ASR_EINVAL, "null argument");
   size_t need = 0;
   if (int rc = mi355asr_punc_workspace_bytes(m, B, T, &need)) return rc;
   if (need && (!ws || ws_bytes < need)) return fail(MI355ASR_EWORKSPACE, "workspace of %zu bytes, need %zu", ws_bytes, need);
   if (need && ((uintptr_t)ws & 15)) return fail(MI355ASR_EWORKSPACE, "workspace must be 16-byte aligned");
   const size_t lds = lds_bytes_for(T);
-  if (lds > 64 * 1024 && allow_lds() != 0) return fail(MI355ASR_EHIP, "punc_kernel: cannot raise the dynamic LDS limit to %zu bytes", kLdsBudget);
+  if (lds > 64 * 1024 && allow_lds() != 0) return fail(MI355ASR_EHIP, "%s: cannot raise the dynamic LDS limit to %zu bytes", heads ? "punc_heads_kernel" : "punc_kernel", kLdsBudget);
   const auto& c = m->pcfg;
-  PuncArgs a{};
-  a.ids = ids; a.lens = lens; a.probs = probs; a.cls = cls; a.pmax = pmax; a.w = m->arena;
+  a.ids = ids; a.lens = lens; a.w = m->arena;
   a.ws = (float*)ws; a.ws_row = ws_row_floats(T);
   a.n_enc = c.num_layers; a.n_map = map_layers(c.num_layers);
   a.o_conv = kDenseFloats + (size_t)a.n_enc * kLayerFloats;
@@ -500,10 +594,35 @@ int mi355asr_punc_forward(mi355asr_model* m, const int32_t* ids, const int32_t* 
   a.o_head = a.o_map + (size_t)a.n_map * kLayerFloats;
   a.o_emb = a.o_head + kDenseFloats;
   a.o_pe = a.o_emb + (size_t)c.vocab * kD;
+  a.o_bert = a.o_pe + (size_t)c.pe_input * kD;
   a.B = B; a.T = T; a.vocab = c.vocab; a.classes = c.classes;
-  hipLaunchKernelGGL(punc_kernel, dim3((unsigned)B), dim3(kThreads), lds, (hipStream_t)stream, a);
+  if (heads)
+    hipLaunchKernelGGL(punc_heads_kernel, dim3((unsigned)B), dim3(kThreads), lds, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(punc_kernel, dim3((unsigned)B), dim3(kThreads), lds, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MI355ASR_EHIP, "launch punc_kernel: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MI355ASR_EHIP, "launch %s: %s", heads ? "punc_heads_kernel" : "punc_kernel", hipGetErrorString(e));
   return 0;
+}
+
+int mi355asr_punc_forward(mi355asr_model* m, const int32_t* ids, const int32_t* lens, int32_t B, int32_t T, float* probs,
+                          int32_t* cls, float* pmax, void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !m->is_punc) return fail(MI355ASR_EINVAL, "not a Punc handle");
+  PuncArgs a{};
+  a.probs = probs; a.cls = cls; a.pmax = pmax;
+  return punc_launch(m, ids, lens, B, T, a, false, ws, ws_bytes, stream);
+}
+
+int mi355asr_punc_heads_workspace_bytes(const mi355asr_model* m, int32_t B, int32_t T, size_t* bytes) {
+  return mi355asr_punc_workspace_bytes(m, B, T, bytes);
+}
+
+int mi355asr_punc_heads(mi355asr_model* m, const int32_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits, float* feature,
+                        void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !m->is_punc) return fail(MI355ASR_EINVAL, "not a Punc handle");
+  if (!logits && !feature) return fail(MI355ASR_EINVAL, "punc_heads: logits_dev and feature_dev are both null");
+  PuncArgs a{};
+  a.logits = logits; a.feature = feature;
+  return punc_launch(m, ids, lens, B, T, a, true, ws, ws_bytes, stream);
 }
 }  // extern "C"

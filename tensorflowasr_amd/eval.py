@@ -384,3 +384,44 @@ class VADTester:
     def results(self):
         import torch
         return {k: float(torch.stack(v).to(torch.float64).mean().item()) if v else float("nan") for k, v in self._steps.items()}
+
+
+class PuncTester:
+    """The reference's PuncTester (punc_recover/tester/punc_tester.py) and the eval half of PuncTrainer
+    (punc_recover/trainer/punc_trainer.py:77-90) for the punctuation model, on the GPU: per step acc = classes_acc (the one metric
+    the reference's tester keeps; the trainer calls it bd_acc), bd_loss = the batch mean of classes_loss, and, when the BERT
+    teacher's features are given, feature_map_loss = the batch mean of bert_feature_loss.
+
+        tester = PuncTester(Punc(config).load_onnx(path))
+        for ids, labels, features in batches:            # [B, T] ids (0 = padding), [B, T] classes, [B, T, 768] or None
+            tester.update(ids, labels, features)
+        tester.results()                                  # {'acc', 'bd_loss', 'feature_map_loss'}: the means over the steps
+
+    One `Punc.heads` launch per step.  `heads` checks the ids on the host before it launches (their range, and that no 0 stands in
+    front of a non-zero id), which waits for the stream as `Punc.forward` does; the step values themselves stay on the device until
+    `results` copies them."""
+
+    def __init__(self, punc):
+        from . import losses
+        self.punc = punc
+        self._losses = losses
+        self.reset()
+
+    def reset(self):
+        self._steps = {"acc": [], "bd_loss": [], "feature_map_loss": []}
+
+    def update(self, ids, labels, features=None):
+        """ids int [B, T] with 0 as padding behind each sentence (the lengths follow from it, as creat_mask has it), labels int
+        [B, Q], features f32 [B, T1, 768] or None -> this step's values as device scalars."""
+        logits, feature = self.punc.heads(ids, want_feature=features is not None)
+        loss, _, acc, _ = self._losses._punc_classes_call(labels, logits)
+        step = {"acc": acc, "bd_loss": loss.mean()}
+        if features is not None:
+            step["feature_map_loss"] = self._losses.bert_feature_loss(features, feature).mean()
+        for k, v in step.items():
+            self._steps[k].append(v)
+        return step
+
+    def results(self):
+        import torch
+        return {k: float(torch.stack(v).to(torch.float64).mean().item()) if v else float("nan") for k, v in self._steps.items()}

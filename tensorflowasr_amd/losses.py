@@ -16,6 +16,14 @@ csrc/stft_loss.hip):
     one, zero = vad_mask_loss(vad_label, logits)                         # VADTrainer.mask_loss
     m = vad_metrics(vad_label, logits)                                   # acc (binary_accuracy), f1, tp, fp, fn, tn
 
+The punctuation trainer's losses (punc_recover/trainer/punc_trainer.py:93-126; `mi355asr_punc_classes_loss`,
+`mi355asr_masked_feature_mse`, csrc/punc_loss.hip) on the outputs of `Punc.heads`:
+
+    bd_loss = punc_classes_loss(tar_bd, bd_pred)                         # f32 [B], PuncTrainer.classes_loss
+    bd_acc = punc_classes_acc(tar_bd, bd_pred)                           # f32 scalar, PuncTrainer.classes_acc
+    feature_map_loss = bert_feature_loss(feature, out_feature)           # f32 [B], PuncTrainer.bert_feature_loss
+    out = punc_losses(tar_bd, feature, bd_pred, out_feature, return_grad=True)   # the train step's values and gradients
+
 Everything returned is a device tensor; nothing here copies to the host or waits for the stream."""
 import ctypes
 
@@ -364,3 +372,147 @@ def vad_metrics(labels, logits, threshold=0.5, lengths=None):
     den = 2 * cf[0] + cf[1] + cf[2]
     f1 = torch.where(den > 0, 2 * cf[0] / torch.clamp(den, min=1.0), torch.zeros_like(den))
     return {"acc": ((cf[0] + cf[3]) / cf.sum()).to(torch.float32), "f1": f1.to(torch.float32), "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+
+
+# ---- the punctuation trainer's losses --------------------------------------------------------------------------------------------------
+MAX_PUNC_CLASSES = 64           # kMaxClasses of csrc/punc.hip and csrc/punc_loss.hip
+FEATURE_MASK_VALUE = -10.0      # the dataloader's padding of the BERT features
+
+
+def _as_tensor(t, dtype):
+    return t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=dtype)))
+
+
+def _rows3(t, dev):
+    """[B, T, F] -> f32 on the device, used in place when the last axis has unit stride and the rows do not overlap"""
+    x = t.to(device=dev, dtype=torch.float32)
+    B, T, F = x.shape
+    if F > 1 and x.stride(2) != 1 or T > 1 and x.stride(1) < F or B > 1 and x.stride(0) < F or x.stride(0) < 0 or x.stride(1) < 0:
+        x = x.contiguous()
+    return x
+
+
+def _upstream(upstream, B, dev):
+    if upstream is None:
+        return None
+    g = _as_tensor(upstream, np.float32).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if g.numel() != B:
+        raise ValueError("upstream holds %d values for %d rows" % (g.numel(), B))
+    return g
+
+
+def _punc_classes_call(real, pred, upstream=None, return_grad=False):
+    """one `mi355asr_punc_classes_loss` -> (loss f32 [B], acc f32 [B], mean acc f32 [], gradient [B, T, C] or None)"""
+    x, y = _as_tensor(pred, np.float32), _as_tensor(real, np.int32)
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError("pred is [B, T, C], not empty (got shape %s)" % (tuple(x.shape),))
+    B, T, C = x.shape
+    if C > MAX_PUNC_CLASSES:
+        raise ValueError("%d classes: the punctuation losses take at most %d (for a wide class axis see mask_loss)" % (C, MAX_PUNC_CLASSES))
+    if y.dim() != 2 or y.shape[0] != B or y.shape[1] < 1:
+        raise ValueError("real is [B, Q] with the B of pred and Q >= 1 (got %s for %d rows)" % (tuple(y.shape), B))
+    dev = _device_of(x, None)
+    if dev.type != "cuda":
+        raise _lib.Mi355AsrError("the losses run on the GPU only (got device %s)" % dev)
+    lib = _lib.lib()
+    x = _rows3(x, dev)
+    y = y.to(device=dev, dtype=torch.int32).contiguous()
+    g = _upstream(upstream, B, dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    acc = torch.empty((B,), dtype=torch.float32, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, T, C), dtype=torch.float32, device=dev) if return_grad else None
+    launch_punc_classes(lib, y, x, g, B, y.shape[1], T, C, loss, acc, mean, grad, dev)
+    return loss, acc, mean, grad
+
+
+def launch_punc_classes(lib, y, x, g, B, Q, T, C, loss, acc, mean, grad, dev):
+    """The C call on buffers the caller owns (the tests hand in poisoned outputs and strided views)."""
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mi355asr_punc_classes_loss(_p(y), y.stride(0), _p(x), x.stride(0), x.stride(1), _p(g), B, Q, T, C, _p(loss), _p(acc),
+                                                  _p(mean), _p(grad), grad.stride(0) if grad is not None else 0,
+                                                  grad.stride(1) if grad is not None else 0, st))
+
+
+def punc_classes_loss(real, pred, return_grad=False, upstream=None):
+    """PuncTrainer.classes_loss (punc_trainer.py:104-115): real int [B, Q] (0 = padding, 1 = no mark), pred f32 [B, T, C <= 64]
+    logits (a strided view is read in place); the first Q' = min(T, Q) columns of both are used, the rule `sparse_xent`
+    documents.  With xe = sparse_xent, m = (real != 0), m1 = m * (real != 1):
+        loss[b] = sum(xe m) / (sum m + 1e-6) + sum(xe m1) / (sum m1 + 1e-6)      -> f32 [B] (the reference keeps a trailing 1)
+    return_grad: also d (sum_b upstream[b] loss[b]) / d pred, f32 with the shape of pred (upstream f32 [B], None = ones); zeros for
+    t >= Q' and where real == 0.  A label outside [0, C) gives loss NaN and a zero gradient row.  Sums in float64 on the device."""
+    loss, _, _, grad = _punc_classes_call(real, pred, upstream, return_grad)
+    return (loss, grad) if return_grad else loss
+
+
+def punc_classes_acc(real, pred):
+    """PuncTrainer.classes_acc (punc_trainer.py:118-126): the batch mean of sum((argmax(pred) == real) m) / sum m, m = (real != 0)
+    -> f32 scalar.  No epsilon, as the reference has none: a row without a label is NaN and so is the mean.  Ties: lowest index."""
+    return _punc_classes_call(real, pred)[2]
+
+
+def _feature_call(real, pred, upstream=None, return_grad=False):
+    r, p = _as_tensor(real, np.float32), _as_tensor(pred, np.float32)
+    if r.dim() != 3 or p.dim() != 3 or min(r.shape) < 1 or min(p.shape) < 1:
+        raise ValueError("real and pred are [B, T, F], not empty (got shapes %s, %s)" % (tuple(r.shape), tuple(p.shape)))
+    if r.shape[0] != p.shape[0] or r.shape[2] != p.shape[2]:
+        raise ValueError("real %s and pred %s differ in B or F" % (tuple(r.shape), tuple(p.shape)))
+    dev = _device_of(p, None)
+    if dev.type != "cuda":
+        raise _lib.Mi355AsrError("the losses run on the GPU only (got device %s)" % dev)
+    lib = _lib.lib()
+    r, p = _rows3(r, dev), _rows3(p, dev)
+    B, T1, F = r.shape
+    T2 = p.shape[1]
+    g = _upstream(upstream, B, dev)
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, T2, F), dtype=torch.float32, device=dev) if return_grad else None
+    launch_feature_mse(lib, r, p, g, B, T1, T2, F, out, grad, dev)
+    return out, grad
+
+
+def launch_feature_mse(lib, r, p, g, B, T1, T2, F, out, grad, dev):
+    """The C call on buffers the caller owns (the tests hand in poisoned outputs, misaligned and strided views)."""
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.mi355asr_masked_feature_mse_workspace_bytes(B, T1, T2, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mi355asr_masked_feature_mse(_p(r), r.stride(0), r.stride(1), _p(p), p.stride(0), p.stride(1), _p(g), B, T1, T2, F,
+                                                   _p(out), _p(grad), grad.stride(0) if grad is not None else 0,
+                                                   grad.stride(1) if grad is not None else 0, _p(ws), nbytes.value, st))
+
+
+def bert_feature_loss(real, pred, return_grad=False, upstream=None):
+    """PuncTrainer.bert_feature_loss (punc_trainer.py:93-102): real f32 [B, T1, F] (the BERT teacher's features, -10 where the
+    dataloader padded), pred f32 [B, T2, F] (`Punc.heads`' feature); T = min(T1, T2), k = (real != -10) per element:
+        out[b] = mean over t < T of sum_f (real - pred)^2 k / (sum_f k + 1e-6)     -> f32 [B] (the reference keeps a trailing 1)
+    Padded tokens count in the mean with 0, as in the reference.  return_grad: also d (sum_b upstream[b] out[b]) / d pred, f32
+    [B, T2, F] (upstream f32 [B], None = ones), zero for t >= T and where real == -10.  Strided views are read in place."""
+    out, grad = _feature_call(real, pred, upstream, return_grad)
+    return (out, grad) if return_grad else out
+
+
+def punc_losses(tar_bd, feature, bd_pred, out_feature, return_grad=False, global_batch_size=None):
+    """What PuncTrainer._train_step forms from the model's two outputs (punc_trainer.py:58-65) -> dict of device tensors:
+    bd_loss [B], feature_map_loss [B], bd_acc (scalar) and train_loss = sum(10 feature_map_loss + bd_loss) / global_batch_size
+    (tf.nn.compute_average_loss; global_batch_size defaults to B).  return_grad: also grad_bd_pred and grad_out_feature, the
+    gradients of train_loss with respect to the two outputs; their upstream coefficients 1 / gbs and 10 / gbs are formed on the
+    device."""
+    B = int(bd_pred.shape[0])
+    gbs = float(B if global_batch_size is None else global_batch_size)
+    if not gbs > 0:
+        raise ValueError("global_batch_size must be positive (got %r)" % (global_batch_size,))
+    up_bd = up_f = None
+    if return_grad:
+        dev = _device_of(bd_pred, None)
+        up_bd = torch.full((B,), 1.0 / gbs, dtype=torch.float32, device=dev)
+        up_f = torch.full((B,), 10.0 / gbs, dtype=torch.float32, device=dev)
+    bd_loss, _, bd_acc, g_bd = _punc_classes_call(tar_bd, bd_pred, up_bd, return_grad)
+    f_loss, g_f = _feature_call(feature, out_feature, up_f, return_grad)
+    out = {"bd_loss": bd_loss, "feature_map_loss": f_loss, "bd_acc": bd_acc,
+           "train_loss": ((10.0 * f_loss.to(torch.float64) + bd_loss.to(torch.float64)).sum() / gbs).to(torch.float32)}
+    if return_grad:
+        out["grad_bd_pred"], out["grad_out_feature"] = g_bd, g_f
+    return out

@@ -108,6 +108,25 @@ def pos_encoding(pe_input, d_model):
     return np.array(angle_rads, "float32")
 
 
+FEATURE_DIM = 768               # to_bert's width (kBert of csrc/punc.hip)
+
+
+def lengths_from_ids(ids):
+    """PuncTrainer.creat_mask's rule as lengths: ids int [B, T] (array or tensor, any device), 0 = padding -> i32 [B] on the
+    ids' device, a row's length one past its last non-zero id.  An id 0 in front of a non-zero id raises ValueError."""
+    x = ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids)))
+    if x.dim() != 2:
+        raise ValueError("ids are [B, T] (got shape %s)" % (tuple(x.shape),))
+    used = x != 0
+    pos = torch.arange(1, x.shape[1] + 1, device=x.device, dtype=torch.int32)
+    ln = (used.to(torch.int32) * pos).amax(1) if x.shape[1] else torch.zeros(x.shape[0], dtype=torch.int32, device=x.device)
+    inner = (~used) & (pos[None, :] <= ln[:, None])
+    if bool(inner.any()):
+        b, t = (int(v) for v in inner.nonzero()[0])
+        raise ValueError("id 0 at token %d of row %d, in front of a non-zero id: padding must follow the sentence" % (t, b))
+    return ln.to(torch.int32)
+
+
 def apply_rule(txt, cls, pmax, vocab_array):
     """punc_recover's loop on the rows of the characters (markers dropped): after character t the mark
     `vocab_array[argmax]` when argmax > 1 and max >= 0.65 -> list"""
@@ -222,6 +241,44 @@ class Punc:
                 _lib.check(h.lib.mi355asr_punc_forward(h.ptr, _p(x), _p(ln), B, T, _p(probs), _p(cls), _p(pmax), _p(ws), n.value,
                                                        h._stream()))
         return probs, cls, pmax
+
+    def heads(self, ids, lengths=None, want_logits=True, want_feature=True):
+        """The model's training outputs, `PuncTransformer.call([inp, mask], training=False)` as PuncTrainer._eval_step runs it:
+        -> (logits [B, T, classes], the values `forward` takes its softmax of, and feature [B, T, 768] = to_bert(enc_output),
+        the distillation feature) on the device, one launch; the one not wanted is None.  Rows at or past a sentence's length
+        are zeros (the reference computes values there; the trainer's losses mask them).
+        lengths=None: taken from the ids as the reference's creat_mask does from `ids == 0` -- a row's length is one past its
+        last non-zero id; an id 0 in front of a non-zero id is a ValueError (the kernel masks by length, the reference would
+        mask that key alone)."""
+        if not (want_logits or want_feature):
+            raise ValueError("heads: neither output is wanted")
+        h = self._handle()
+        x = h.to_device(ids, dtype=torch.int32)
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[1] < 1:
+            raise ValueError("expected ids [T] or [B, T] with T >= 1, got %s" % (tuple(x.shape),))
+        B, T = x.shape
+        if T > self.max_tokens:
+            raise ValueError("%d tokens (markers included) exceed pe_input = %d" % (T, self.max_tokens))
+        if B and (int(x.min()) < 0 or int(x.max()) >= self.cfg["vocab"]):
+            raise ValueError("token id outside [0, %d)" % self.cfg["vocab"])
+        if lengths is None:
+            ln = lengths_from_ids(x)
+        else:
+            ln = h.to_device(lengths if torch.is_tensor(lengths) else np.asarray(lengths), dtype=torch.int32)
+            if ln.shape != (B,):
+                raise ValueError("lengths must be [B]")
+        C = self.cfg["classes"]
+        logits = torch.empty((B, T, C), dtype=torch.float32, device=h.device) if want_logits else None
+        feature = torch.empty((B, T, FEATURE_DIM), dtype=torch.float32, device=h.device) if want_feature else None
+        if B:
+            n = ctypes.c_size_t()
+            _lib.check(h.lib.mi355asr_punc_heads_workspace_bytes(h.ptr, B, T, ctypes.byref(n)))
+            ws = h.workspace(n.value) if n.value else None
+            with torch.cuda.device(h.device):
+                _lib.check(h.lib.mi355asr_punc_heads(h.ptr, _p(x), _p(ln), B, T, _p(logits), _p(feature), _p(ws), n.value, h._stream()))
+        return logits, feature
 
     def probs(self, ids, lengths=None):
         """-> device tensor [B, T, classes]"""
