@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmi355asr.so")
 SOURCES = ["api.hip", "weights.hip", "block_path.hip", "api_chunk.hip", "chunk_stream.hip", "api_translator.hip", "api_beam.hip", "api_ctc.hip", "ctc_lattice.hip", "api_xent.hip", "xent.hip", "stft_loss.hip", "punc_loss.hip", "blocks.hip", "frontend.hip", "beam.hip", "beam_device.hip", "lm.hip", "fused.hip", "fused_pp.hip", "fused_ns.hip", "fft_stft.hip", "attention_lds.hip", "attention_split.hip", "attention_split64.hip", "subconv.hip", "bf16.hip", "stream256.hip", "gemm_ring.hip", "leaf.hip", "wavpick.hip", "vad.hip", "punc.hip", "stream_hist.hip", "resample.hip", "augment.hip", "stft.hip", "iir.hip", "sinc_resample.hip", "edit_distance.hip"]
-HEADERS = ["common.h", "launch.h", "beam.h", "lm_table.h", "ctc_lattice.h", "xent.h", "wstream.h", "model.h", "prep_sched.inc", "prep2_sched.inc", "pp_units.inc", "pp_layout.inc", "refmath.h", "split_f16.h", "mfma_ops.h", "block144.h", "env.h", "refmath_tables.inc", os.path.join("..", "..", "include", "mi355asr.h")]
+HEADERS = ["common.h", "launch.h", "beam.h", "lm_table.h", "ctc_lattice.h", "xent.h", "wstream.h", "model.h", "prep_sched.inc", "prep2_sched.inc", "pp_units.inc", "pp_layout.inc", "refmath.h", "split_f16.h", "mfma_ops.h", "block144.h", "env.h", "refmath_tables.inc", "dft_tables.h", "dft_mfma.h", os.path.join("..", "..", "include", "mi355asr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("MI355ASR_EXTRA_HIPCC_FLAGS", "").split()      # e.g. -DMI355ASR_DIAG_KERNELS (timing-only kernel variants)
 

@@ -6,22 +6,20 @@
 namespace mi355 {
 namespace {
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct CtcLossPlan {
   size_t lp, stat, logp, feasible, norm, ab, chain, total;
 };
 CtcLossPlan loss_plan(size_t B, size_t T, size_t U, bool want_grad) {
   CtcLossPlan p{};
   size_t o = 0;
-  p.lp = o; o += up256(B * T * (U + 1) * sizeof(float));
-  p.stat = o; o += up256(B * T * 2 * sizeof(float));
-  p.logp = o; o += up256(B * sizeof(double));
-  p.feasible = o; o += up256(B * sizeof(int32_t));
+  p.lp = o; o += align256(B * T * (U + 1) * sizeof(float));
+  p.stat = o; o += align256(B * T * 2 * sizeof(float));
+  p.logp = o; o += align256(B * sizeof(double));
+  p.feasible = o; o += align256(B * sizeof(int32_t));
   if (want_grad) {
-    p.norm = o; o += up256(2 * B * T * sizeof(double));
-    p.ab = o; o += up256(2 * B * T * (2 * U + 1) * sizeof(float));
-    p.chain = o; o += up256(B * std::max<size_t>(U, 1) * sizeof(int32_t));
+    p.norm = o; o += align256(2 * B * T * sizeof(double));
+    p.ab = o; o += align256(2 * B * T * (2 * U + 1) * sizeof(float));
+    p.chain = o; o += align256(B * std::max<size_t>(U, 1) * sizeof(int32_t));
   }
   p.total = o;
   return p;
@@ -33,8 +31,8 @@ struct CtcAlignPlan {
 CtcAlignPlan align_plan(size_t B, size_t T, size_t U) {
   CtcAlignPlan p{};
   p.lp = 0;
-  p.bp = up256(B * T * (U + 1) * sizeof(float));
-  p.total = p.bp + up256(B * T * (2 * U + 1));
+  p.bp = align256(B * T * (U + 1) * sizeof(float));
+  p.total = p.bp + align256(B * T * (2 * U + 1));
   return p;
 }
 

@@ -7,17 +7,15 @@
 namespace mi355 {
 namespace {
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct XentPlan {
   size_t loss, amax, w, total;
 };
 XentPlan xent_plan(size_t B, size_t Q, bool want_grad) {
   XentPlan p{};
   size_t o = 0;
-  p.loss = o; o += up256(B * Q * sizeof(float));
-  p.amax = o; o += up256(B * Q * sizeof(int32_t));
-  p.w = o; o += want_grad ? up256(B * Q * sizeof(float)) : 0;
+  p.loss = o; o += align256(B * Q * sizeof(float));
+  p.amax = o; o += align256(B * Q * sizeof(int32_t));
+  p.w = o; o += want_grad ? align256(B * Q * sizeof(float)) : 0;
   p.total = o;
   return p;
 }

@@ -152,7 +152,8 @@ struct MixArgs {
   int quantise;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
+// DESCENDING offsets (32, 16, .. 1), unlike common.h's wave_sum: kept apart on purpose, the two orders round a float64 sum differently
+__device__ __forceinline__ double wave_sum_descending(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
@@ -172,8 +173,8 @@ __global__ __launch_bounds__(kMixThreads) void mix_snr_kernel(MixArgs a) {
     px += xv * xv;
     pd += dv * dv;
   }
-  px = wave_sum(px);
-  pd = wave_sum(pd);
+  px = wave_sum_descending(px);
+  pd = wave_sum_descending(pd);
   if ((threadIdx.x & 63) == 0) {
     red[0][threadIdx.x >> 6] = px;
     red[1][threadIdx.x >> 6] = pd;

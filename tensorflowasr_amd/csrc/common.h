@@ -167,6 +167,19 @@ DEV float group_max(float v) {
   return v;
 }
 
+// sum over the 64 lanes of a wave, in every lane: a butterfly with ASCENDING offsets (1, 2, .. 32).  The order fixes the bits of a
+// float64 sum: another order is another function (augment.hip keeps a descending one)
+DEV double wave_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+DEV long long wave_sum(long long v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
 DEV float fast_sigmoid(float x) {
   // 1/(1+e^-x): v_exp_f32 + v_rcp_f32 (both ~1 ulp); saturates cleanly for |x| large.
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));

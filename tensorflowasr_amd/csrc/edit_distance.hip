@@ -229,8 +229,6 @@ __global__ __launch_bounds__(kStrip) void edit_kernel(EditArgs a) {
   }
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct EditLayout { size_t col, dirs, uf, vf, total; };
 
 EditLayout layout_of(int B, int N, int M, bool want_ops) {

@@ -286,6 +286,9 @@ struct Plan : ScratchPlan {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// the longest row (or the most rows) a kernel that indexes with 32 bits takes: 2^31 less the slack of a grid rounded up to whole tiles
+constexpr int64_t kMaxExtent32 = ((int64_t)1 << 31) - 65536;
+
 // lays a workspace out: buffers one behind the other, each 256-byte aligned
 struct Layout {
   size_t o = 0;

@@ -27,13 +27,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWavesPerGroup = kThreads / 64;
 constexpr int kMaxClasses = 64;                          // kMaxClasses of punc.hip
-constexpr int64_t kMaxRows = ((int64_t)1 << 31) - 65536;  // B * T of either kernel
-
-DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 struct ClassesArgs {
   const int32_t* labels;   // (b, t) at labels + b ld_lab + t
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(64) void feature_reduce_kernel(const double* rows, 
   if (threadIdx.x == 0) out[b] = (float)(s / (double)T);
 }
 
-size_t feature_ws_bytes(int B, int T) { return (((size_t)B * T * sizeof(double)) + 255) & ~(size_t)255; }
+size_t feature_ws_bytes(int B, int T) { return align256((size_t)B * T * sizeof(double)); }
 
 }  // namespace
 
@@ -219,7 +212,7 @@ int mi355asr_punc_classes_loss(const int32_t* labels_dev, int64_t ld_lab, const 
   if (!logits_dev) return fail(MI355ASR_EINVAL, "punc_classes_loss: null pointer logits_dev");
   if (!loss_dev || !acc_dev || !acc_mean_dev) return fail(MI355ASR_EINVAL, "punc_classes_loss: null output pointer (loss_dev, acc_dev, acc_mean_dev)");
   if (C < 1 || C > kMaxClasses) return fail(MI355ASR_EINVAL, "punc_classes_loss: C=%d classes, supported is 1 .. %d", C, kMaxClasses);
-  if (B < 1 || Q < 1 || T < 1 || (int64_t)B * T > kMaxRows)
+  if (B < 1 || Q < 1 || T < 1 || (int64_t)B * T > kMaxExtent32)
     return fail(MI355ASR_EINVAL, "punc_classes_loss: need B, Q, T >= 1 and B * T < 2^31 - 65536 (got %d, %d, %d)", B, Q, T);
   const int Qu = std::min(Q, T);
   if (ld_lab < 0 || ld_b < 0 || (B > 1 && (ld_lab < Qu || ld_b < C)) || (Qu > 1 && ld_t < C))
@@ -241,7 +234,7 @@ int mi355asr_punc_classes_loss(const int32_t* labels_dev, int64_t ld_lab, const 
 
 int mi355asr_masked_feature_mse_workspace_bytes(int32_t B, int32_t T1, int32_t T2, size_t* bytes) {
   if (!bytes) return fail(MI355ASR_EINVAL, "masked_feature_mse: null pointer bytes");
-  if (B < 1 || T1 < 1 || T2 < 1 || (int64_t)B * std::max(T1, T2) > kMaxRows)
+  if (B < 1 || T1 < 1 || T2 < 1 || (int64_t)B * std::max(T1, T2) > kMaxExtent32)
     return fail(MI355ASR_EINVAL, "masked_feature_mse: need B, T1, T2 >= 1 and B * max(T1, T2) < 2^31 - 65536 (got %d, %d, %d)", B, T1, T2);
   *bytes = feature_ws_bytes(B, std::min(T1, T2));
   return 0;

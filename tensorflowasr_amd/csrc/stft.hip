@@ -25,11 +25,8 @@
 // frame order, and the squared window along with them, and divides where the sum exceeds tiny(float32).
 // vocoder_kernel: one lane owns one bin of one row and walks the output frames; the time step t * rate is float64, the expected
 // phase advance comes from a host table reduced modulo 2 pi in float64, and the accumulated phase is kept in [-pi, pi].
-#include <map>
-#include <mutex>
-#include <utility>
-
 #include "common.h"
+#include "dft_mfma.h"
 #include "model.h"
 
 namespace {
@@ -43,12 +40,7 @@ enum { MODE_STFT = 0, MODE_ISTFT = 1, MODE_SPECAUG = 2 };
 struct StftTables {
   const float* win;       // [N] the padded window
   const float* wsq;       // [N] its square (float64, rounded once)
-  const float* twc;       // [32][N2] cos(2 pi k1 n2 / N)
-  const float* tws;       // [32][N2] sin(2 pi k1 n2 / N)
-  const float* T1;        // packed stage matrices, forward 1 and 2, inverse 1 and 2
-  const float* T2;
-  const float* T3;
-  const float* T4;
+  DftTables dft;          // twiddles and packed stage matrices; T4 carries 1 / N
   const float* phi;       // [N/2 + 1] pi hop k / (N/2) reduced to [-pi, pi] in float64
 };
 
@@ -71,27 +63,6 @@ DEV float to_f32(int16_t v) { return (float)v * (1.0f / 32768.0f); }
 
 // frames of a row of L samples: reflect padding needs L >= N/2 + 1
 DEV int row_frames(int64_t L, int N, int hop) { return L >= N / 2 + 1 ? 1 + (int)(L / hop) : 0; }
-
-// D[M = 16 MT][N = 16 NT] = T[M][K = 4 KS] * Bm[K][N]: T packed as [mt][ks][lane] = T[16 mt + (lane & 15)][4 ks + (lane >> 4)],
-// Bm in LDS with row stride ldb; store(row, col, value) receives every element once
-template <int MT, int NT, int KS, typename Store>
-DEV void block_gemm(const float* __restrict__ Tp, const float* Bm, int ldb, Store store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane >> 4, c = lane & 15;
-#pragma unroll 1
-  for (int t = wave; t < MT * NT; t += kStftThreads / 64) {
-    const int mt = t / NT, nt = t - mt * NT;
-    const float* tp = Tp + (size_t)mt * KS * 64 + lane;
-    const float* bp = Bm + g * ldb + 16 * nt + c;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-    for (int ks = 0; ks < KS; ++ks) acc = mfma4(tp[ks * 64], bp[4 * ks * ldb], acc);
-    store(16 * mt + 4 * g + 0, 16 * nt + c, acc.x);
-    store(16 * mt + 4 * g + 1, 16 * nt + c, acc.y);
-    store(16 * mt + 4 * g + 2, 16 * nt + c, acc.z);
-    store(16 * mt + 4 * g + 3, 16 * nt + c, acc.w);
-  }
-}
 
 template <int N2, typename T, int MODE>
 __global__ __launch_bounds__(kStftThreads) void frame_kernel(FrameArgs a) {
@@ -144,20 +115,20 @@ __global__ __launch_bounds__(kStftThreads) void frame_kernel(FrameArgs a) {
     if ((tid & 63) == 0) red[tid >> 6] = part;
     __syncthreads();
     // ---- forward stage 1: bufD[(re | im) k1][n2]
-    block_gemm<4, N2 / 16, 8>(a.t.T1, bufA, LDX, [&](int r, int col, float v) { bufD[r * LDX + col] = v; });
+    dft_block_gemm<kStftThreads, 4, N2 / 16, 8>(a.t.dft.T1, bufA, LDX, [&](int r, int col, float v) { bufD[r * LDX + col] = v; });
     __syncthreads();
     // ---- twiddle, transposed: bufT[(re | im) n2][k1]
     for (int i = tid; i < 32 * N2; i += kStftThreads) {
       const int k1 = i / N2, n2 = i - k1 * N2;
       const float are = bufD[k1 * LDX + n2], aim = bufD[(32 + k1) * LDX + n2];
-      const float tc = a.t.twc[i], ts = a.t.tws[i];
+      const float tc = a.t.dft.twc[i], ts = a.t.dft.tws[i];
       bufT[n2 * kLDT + k1] = fmaf(are, tc, __fmul_rn(aim, ts));
       bufT[(N2 + n2) * kLDT + k1] = fmaf(aim, tc, -__fmul_rn(are, ts));
     }
     const float nyq = (red[0] + red[1]) + (red[2] + red[3]);
     __syncthreads();
     // ---- forward stage 2: row r < N2/2 is Re X[32 r + col], row N2/2 + r is Im X[32 r + col]
-    block_gemm<N2 / 16, 2, N2 / 2>(a.t.T2, bufT, kLDT, [&](int r, int col, float v) { bufD[r * 32 + col] = v; });
+    dft_block_gemm<kStftThreads, N2 / 16, 2, N2 / 2>(a.t.dft.T2, bufT, kLDT, [&](int r, int col, float v) { bufD[r * 32 + col] = v; });
     if (tid == 0) red[4] = nyq;
     __syncthreads();
   }
@@ -223,18 +194,18 @@ __global__ __launch_bounds__(kStftThreads) void frame_kernel(FrameArgs a) {
   }
   __syncthreads();
   // ---- inverse stage 1: bufD[(re | im) p][k2]
-  block_gemm<4, N2 / 16, 16>(a.t.T3, bufA, LDX, [&](int r, int col, float v) { bufD[r * LDX + col] = v; });
+  dft_block_gemm<kStftThreads, 4, N2 / 16, 16>(a.t.dft.T3, bufA, LDX, [&](int r, int col, float v) { bufD[r * LDX + col] = v; });
   __syncthreads();
   for (int i = tid; i < 32 * N2; i += kStftThreads) {
     const int p = i / N2, k2 = i - p * N2;
     const float are = bufD[p * LDX + k2], aim = bufD[(32 + p) * LDX + k2];
-    const float tc = a.t.twc[i], ts = a.t.tws[i];
+    const float tc = a.t.dft.twc[i], ts = a.t.dft.tws[i];
     bufT[k2 * kLDT + p] = fmaf(are, tc, -__fmul_rn(aim, ts));
     bufT[(N2 + k2) * kLDT + p] = fmaf(are, ts, __fmul_rn(aim, tc));
   }
   __syncthreads();
   // ---- inverse stage 2: bufA[32 q + p] = y[n], 1 / N included in the table
-  block_gemm<N2 / 16, 2, N2 / 2>(a.t.T4, bufT, kLDT, [&](int r, int col, float v) { bufA[r * 32 + col] = v; });
+  dft_block_gemm<kStftThreads, N2 / 16, 2, N2 / 2>(a.t.dft.T4, bufT, kLDT, [&](int r, int col, float v) { bufA[r * 32 + col] = v; });
   __syncthreads();
   const int off = (N - a.win) / 2;
   float* out = a.fr + ((size_t)b * a.Fpad + f) * a.win;
@@ -356,114 +327,26 @@ int stft_geo(int n_fft, int win, int hop, StftGeo* g) {
               win, hop);
 }
 
-const double kPi = 3.14159265358979323846;
-
-// cos / sin of 2 pi (a b mod M) / M
-double cosm(int64_t a, int64_t b, int64_t M) { return cos(2.0 * kPi * (double)((a * b) % M) / (double)M); }
-double sinm(int64_t a, int64_t b, int64_t M) { return sin(2.0 * kPi * (double)((a * b) % M) / (double)M); }
-
-// T [M][K] (double) -> fragment order [M / 16][K / 4][64]
-void pack_frag(const std::vector<double>& T, int M, int K, std::vector<float>* out) {
-  const size_t base = out->size();
-  out->resize(base + (size_t)M * K);
-  for (int mt = 0; mt < M / 16; ++mt)
-    for (int ks = 0; ks < K / 4; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        (*out)[base + ((size_t)mt * (K / 4) + ks) * 64 + lane] = (float)T[(size_t)(16 * mt + (lane & 15)) * K + 4 * ks + (lane >> 4)];
-}
-
-void build_tables(const StftGeo& g, std::vector<float>* buf, size_t (&at)[9]) {
-  const int N = g.N, N2 = g.N2, H = N2 / 2, off = (N - g.win) / 2;
-  at[0] = buf->size();
-  for (int n = 0; n < N; ++n) {
-    const int j = n - off;
-    buf->push_back(j >= 0 && j < g.win ? (float)(0.5 - 0.5 * cos(2.0 * kPi * j / g.win)) : 0.0f);
-  }
-  at[1] = buf->size();
-  for (int n = 0; n < N; ++n) {
-    const int j = n - off;
-    const double w = j >= 0 && j < g.win ? 0.5 - 0.5 * cos(2.0 * kPi * j / g.win) : 0.0;
-    buf->push_back((float)(w * w));
-  }
-  at[2] = buf->size();
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n2 = 0; n2 < N2; ++n2) buf->push_back((float)cosm(k1, n2, N));
-  at[3] = buf->size();
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n2 = 0; n2 < N2; ++n2) buf->push_back((float)sinm(k1, n2, N));
-  std::vector<double> T;
-  // forward stage 1 [64][32]: rows k1 cos, rows 32 + k1 -sin
-  T.assign(64 * 32, 0.0);
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n1 = 0; n1 < 32; ++n1) {
-      T[k1 * 32 + n1] = cosm(k1, n1, 32);
-      T[(32 + k1) * 32 + n1] = -sinm(k1, n1, 32);
-    }
-  at[4] = buf->size();
-  pack_frag(T, 64, 32, buf);
-  // forward stage 2 [2 H][2 N2]: Re = C Bre + S Bim, Im = -S Bre + C Bim
-  T.assign((size_t)2 * H * 2 * N2, 0.0);
-  for (int k2 = 0; k2 < H; ++k2)
-    for (int n2 = 0; n2 < N2; ++n2) {
-      const double c = cosm(k2, n2, N2), s = sinm(k2, n2, N2);
-      T[(size_t)k2 * 2 * N2 + n2] = c;
-      T[(size_t)k2 * 2 * N2 + N2 + n2] = s;
-      T[(size_t)(H + k2) * 2 * N2 + n2] = -s;
-      T[(size_t)(H + k2) * 2 * N2 + N2 + n2] = c;
-    }
-  at[5] = buf->size();
-  pack_frag(T, 2 * H, 2 * N2, buf);
-  // inverse stage 1 [64][64]: Re = C Fre - S Fim, Im = S Fre + C Fim
-  T.assign(64 * 64, 0.0);
-  for (int p = 0; p < 32; ++p)
-    for (int k1 = 0; k1 < 32; ++k1) {
-      const double c = cosm(p, k1, 32), s = sinm(p, k1, 32);
-      T[p * 64 + k1] = c;
-      T[p * 64 + 32 + k1] = -s;
-      T[(32 + p) * 64 + k1] = s;
-      T[(32 + p) * 64 + 32 + k1] = c;
-    }
-  at[6] = buf->size();
-  pack_frag(T, 64, 64, buf);
-  // inverse stage 2 [N2][2 N2]: y = (C Bre - S Bim) / N
-  T.assign((size_t)N2 * 2 * N2, 0.0);
-  for (int q = 0; q < N2; ++q)
-    for (int k2 = 0; k2 < N2; ++k2) {
-      T[(size_t)q * 2 * N2 + k2] = cosm(q, k2, N2) / N;
-      T[(size_t)q * 2 * N2 + N2 + k2] = -sinm(q, k2, N2) / N;
-    }
-  at[7] = buf->size();
-  pack_frag(T, N2, 2 * N2, buf);
-  // the vocoder's expected phase advance linspace(0, pi hop, bins)[k] = pi hop k / (N/2), modulo 2 pi: the angle is
-  // 2 pi (hop k mod N) / N exactly
-  at[8] = buf->size();
-  for (int k = 0; k <= N / 2; ++k) {
-    int64_t r = ((int64_t)g.hop * k) % N;
-    if (r > N / 2) r -= N;
-    buf->push_back((float)(2.0 * kPi * (double)r / (double)N));
-  }
-}
-
-// one set of tables per device and size, uploaded on first use and kept for the life of the process
+// one set of tables per device and size
 int get_tables(const StftGeo& g, StftTables* t) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, StftTables> cache;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find({dev, g.N});
-  if (it == cache.end()) {
-    std::vector<float> buf;
-    size_t at[9];
-    build_tables(g, &buf, at);
-    float* d = nullptr;
-    HIP_TRY(hipMalloc(&d, buf.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(d, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
-    StftTables s{d + at[0], d + at[1], d + at[2], d + at[3], d + at[4], d + at[5], d + at[6], d + at[7], d + at[8]};
-    it = cache.emplace(std::make_pair(dev, g.N), s).first;
-  }
-  *t = it->second;
-  return 0;
+  static TableCache<int, StftTables> cache;
+  return cache.get(g.N, t, [&g](std::vector<float>* buf) {
+    const int N = g.N, off = (N - g.win) / 2;
+    const size_t win = buf->size();
+    append_hann(g.win, N, off, false, buf);
+    const size_t wsq = buf->size();
+    append_hann(g.win, N, off, true, buf);
+    const DftOffsets at = append_dft_tables(N, 1.0 / N, buf);
+    // the vocoder's expected phase advance linspace(0, pi hop, bins)[k] = pi hop k / (N/2), modulo 2 pi: the angle is
+    // 2 pi (hop k mod N) / N exactly
+    const size_t phi = buf->size();
+    for (int k = 0; k <= N / 2; ++k) {
+      int64_t r = ((int64_t)g.hop * k) % N;
+      if (r > N / 2) r -= N;
+      buf->push_back((float)(2.0 * kPi * (double)r / (double)N));
+    }
+    return [=](const float* d) { return StftTables{d + win, d + wsq, dft_pointers(d, at), d + phi}; };
+  });
 }
 
 template <int MODE>
@@ -488,12 +371,11 @@ int launch_ola(const OlaArgs& a, int dtype, int B, hipStream_t s) {
   return 0;
 }
 
-constexpr int64_t kMaxCols = ((int64_t)1 << 31) - 65536;
 constexpr int kMaxFrames = 1 << 22;
 
 int check_batch(const char* who, int32_t B, int64_t cols, const char* cols_name) {
   if (B < 1 || B > 65535) return fail(MI355ASR_EINVAL, "%s: need 1 <= B <= 65535 (got %d)", who, B);
-  if (cols < 1 || cols > kMaxCols) return fail(MI355ASR_EINVAL, "%s: need 1 <= %s < 2^31 - 65536 (got %lld)", who, cols_name, (long long)cols);
+  if (cols < 1 || cols > kMaxExtent32) return fail(MI355ASR_EINVAL, "%s: need 1 <= %s < 2^31 - 65536 (got %lld)", who, cols_name, (long long)cols);
   return 0;
 }
 
@@ -507,7 +389,7 @@ int mi355asr_stft_frames(int32_t n_fft, int32_t win_length, int32_t hop, int64_t
   StftGeo g;
   if (!frames) return fail(MI355ASR_EINVAL, "null pointer");
   if (int rc = stft_geo(n_fft, win_length, hop, &g)) return rc;
-  *frames = n_samples >= g.N / 2 + 1 && n_samples <= kMaxCols ? 1 + (int32_t)(n_samples / g.hop) : 0;
+  *frames = n_samples >= g.N / 2 + 1 && n_samples <= kMaxExtent32 ? 1 + (int32_t)(n_samples / g.hop) : 0;
   return 0;
 }
 

@@ -28,12 +28,8 @@
 // mask_stats_kernel: one workgroup; float64 / int64 sums in a fixed order, then (on request) the gradient from the totals.
 // A row is computed from its own samples alone and nothing depends on timing (no atomics): a row of a ragged batch equals the
 // row alone bit for bit.
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <vector>
-
 #include "common.h"
+#include "dft_mfma.h"
 #include "model.h"
 
 namespace {
@@ -46,12 +42,7 @@ constexpr int kMaxRes = 4;
 
 struct LossTables {
   const float* win;       // [N] periodic Hann of frame_length, zero from frame_length on
-  const float* twc;       // [32][N2] cos(2 pi k1 n2 / N)
-  const float* tws;       // [32][N2] sin(2 pi k1 n2 / N)
-  const float* T1;        // packed stage matrices, forward 1 and 2, transposed (inverse) 1 and 2
-  const float* T2;
-  const float* T3;
-  const float* T4;
+  DftTables dft;          // twiddles and packed stage matrices; the last two are the transpose: T4 carries no 1 / N
 };
 
 struct LossFrameArgs {
@@ -75,38 +66,6 @@ DEV int64_t row_len(const int32_t* len, int b, int64_t Lpad) {
   return L < 0 ? 0 : (L > Lpad ? Lpad : L);
 }
 DEV int loss_frames(int64_t L, int fl, int step) { return L >= fl ? 1 + (int)((L - fl) / step) : 0; }
-
-DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;
-}
-DEV long long wave_sum(long long v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// D[M = 16 MT][N = 16 NT] = T[M][K = 4 KS] * Bm[K][N]: T packed as [mt][ks][lane] = T[16 mt + (lane & 15)][4 ks + (lane >> 4)],
-// Bm in LDS with row stride ldb; store(row, col, value) receives every element once (the tile helper of stft.hip)
-template <int MT, int NT, int KS, typename Store>
-DEV void block_gemm(const float* __restrict__ Tp, const float* Bm, int ldb, Store store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane >> 4, c = lane & 15;
-#pragma unroll 1
-  for (int t = wave; t < MT * NT; t += kThreads / 64) {
-    const int mt = t / NT, nt = t - mt * NT;
-    const float* tp = Tp + (size_t)mt * KS * 64 + lane;
-    const float* bp = Bm + g * ldb + 16 * nt + c;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-    for (int ks = 0; ks < KS; ++ks) acc = mfma4(tp[ks * 64], bp[4 * ks * ldb], acc);
-    store(16 * mt + 4 * g + 0, 16 * nt + c, acc.x);
-    store(16 * mt + 4 * g + 1, 16 * nt + c, acc.y);
-    store(16 * mt + 4 * g + 2, 16 * nt + c, acc.z);
-    store(16 * mt + 4 * g + 3, 16 * nt + c, acc.w);
-  }
-}
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
@@ -161,14 +120,14 @@ __global__ __launch_bounds__(kThreads) void loss_frame_kernel(LossFrameArgs a) {
   }
   __syncthreads();
   // ---- forward stage 1: bufD[(re | im) k1][pred n2 | truth n2]
-  block_gemm<4, 2 * N2 / 16, 8>(a.t.T1, bufU, LDX2, [&](int r, int col, float v) { bufD[r * LDX2 + col] = v; });
+  dft_block_gemm<kThreads, 4, 2 * N2 / 16, 8>(a.t.dft.T1, bufU, LDX2, [&](int r, int col, float v) { bufD[r * LDX2 + col] = v; });
   __syncthreads();
   // ---- twiddle, transposed: bufU[(re | im) n2][pred k1 | truth k1]
   for (int i = tid; i < 2 * 32 * N2; i += kThreads) {
     const int sig = i / (32 * N2), j = i - sig * (32 * N2);
     const int k1 = j / N2, n2 = j - k1 * N2;
     const float are = bufD[k1 * LDX2 + sig * N2 + n2], aim = bufD[(32 + k1) * LDX2 + sig * N2 + n2];
-    const float tc = a.t.twc[j], ts = a.t.tws[j];
+    const float tc = a.t.dft.twc[j], ts = a.t.dft.tws[j];
     bufU[n2 * kLDT2 + 32 * sig + k1] = fmaf(are, tc, __fmul_rn(aim, ts));
     bufU[(N2 + n2) * kLDT2 + 32 * sig + k1] = fmaf(aim, tc, -__fmul_rn(are, ts));
   }
@@ -176,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void loss_frame_kernel(LossFrameArgs a) {
   const float nyq_t = (red[4] + red[5]) + (red[6] + red[7]);
   __syncthreads();
   // ---- forward stage 2: row r < N2/2 is Re X[32 r + col], row N2/2 + r is Im X[32 r + col]; columns 32 .. 63 are the truth
-  block_gemm<N2 / 16, 4, N2 / 2>(a.t.T2, bufU, kLDT2, [&](int r, int col, float v) { bufD[r * 64 + col] = v; });
+  dft_block_gemm<kThreads, N2 / 16, 4, N2 / 2>(a.t.dft.T2, bufU, kLDT2, [&](int r, int col, float v) { bufD[r * 64 + col] = v; });
   __syncthreads();
 
   double cA = 0.0, cB = 0.0, cM = 0.0;
@@ -234,18 +193,18 @@ __global__ __launch_bounds__(kThreads) void loss_frame_kernel(LossFrameArgs a) {
   } else {
     __syncthreads();
     // ---- transposed stage 1: bufD[(re | im) p][k2]
-    block_gemm<4, N2 / 16, 16>(a.t.T3, bufU, LDX1, [&](int r, int col, float v) { bufD[r * LDX1 + col] = v; });
+    dft_block_gemm<kThreads, 4, N2 / 16, 16>(a.t.dft.T3, bufU, LDX1, [&](int r, int col, float v) { bufD[r * LDX1 + col] = v; });
     __syncthreads();
     for (int i = tid; i < 32 * N2; i += kThreads) {
       const int p = i / N2, k2 = i - p * N2;
       const float are = bufD[p * LDX1 + k2], aim = bufD[(32 + p) * LDX1 + k2];
-      const float tc = a.t.twc[i], ts = a.t.tws[i];
+      const float tc = a.t.dft.twc[i], ts = a.t.dft.tws[i];
       bufU[k2 * kLDT1 + p] = fmaf(are, tc, -__fmul_rn(aim, ts));
       bufU[(N2 + k2) * kLDT1 + p] = fmaf(are, ts, __fmul_rn(aim, tc));
     }
     __syncthreads();
     // ---- transposed stage 2: bufD[32 q + p] = dL / d xw[n]
-    block_gemm<N2 / 16, 2, N2 / 2>(a.t.T4, bufU, kLDT1, [&](int r, int col, float v) { bufD[r * 32 + col] = v; });
+    dft_block_gemm<kThreads, N2 / 16, 2, N2 / 2>(a.t.dft.T4, bufU, kLDT1, [&](int r, int col, float v) { bufD[r * 32 + col] = v; });
     __syncthreads();
     float* out = a.fr + ((size_t)b * a.Fpad + f) * a.fl;
     for (int j = tid; j < a.fl; j += kThreads) out[j] = bufD[j] * a.t.win[j];
@@ -398,97 +357,15 @@ __global__ __launch_bounds__(kThreads) void mask_stats_kernel(MaskStatsArgs a) {
 }
 
 // ---- host: sizes, tables ------------------------------------------------------------------------------------------------------------
-const double kPi = 3.14159265358979323846;
-
-// cos / sin of 2 pi (a b mod M) / M
-double cosm(int64_t a, int64_t b, int64_t M) { return cos(2.0 * kPi * (double)((a * b) % M) / (double)M); }
-double sinm(int64_t a, int64_t b, int64_t M) { return sin(2.0 * kPi * (double)((a * b) % M) / (double)M); }
-
-// T [M][K] (double) -> fragment order [M / 16][K / 4][64]
-void pack_frag(const std::vector<double>& T, int M, int K, std::vector<float>* out) {
-  const size_t base = out->size();
-  out->resize(base + (size_t)M * K);
-  for (int mt = 0; mt < M / 16; ++mt)
-    for (int ks = 0; ks < K / 4; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        (*out)[base + ((size_t)mt * (K / 4) + ks) * 64 + lane] = (float)T[(size_t)(16 * mt + (lane & 15)) * K + 4 * ks + (lane >> 4)];
-}
-
-void build_tables(int N, int fl, std::vector<float>* buf, size_t (&at)[7]) {
-  const int N2 = N / 32, H = N2 / 2;
-  at[0] = buf->size();
-  for (int n = 0; n < N; ++n) buf->push_back(n < fl ? (float)(0.5 - 0.5 * cos(2.0 * kPi * n / fl)) : 0.0f);
-  at[1] = buf->size();
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n2 = 0; n2 < N2; ++n2) buf->push_back((float)cosm(k1, n2, N));
-  at[2] = buf->size();
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n2 = 0; n2 < N2; ++n2) buf->push_back((float)sinm(k1, n2, N));
-  std::vector<double> T;
-  // forward stage 1 [64][32]: rows k1 cos, rows 32 + k1 -sin
-  T.assign(64 * 32, 0.0);
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int n1 = 0; n1 < 32; ++n1) {
-      T[k1 * 32 + n1] = cosm(k1, n1, 32);
-      T[(32 + k1) * 32 + n1] = -sinm(k1, n1, 32);
-    }
-  at[3] = buf->size();
-  pack_frag(T, 64, 32, buf);
-  // forward stage 2 [2 H][2 N2]: Re = C Bre + S Bim, Im = -S Bre + C Bim
-  T.assign((size_t)2 * H * 2 * N2, 0.0);
-  for (int k2 = 0; k2 < H; ++k2)
-    for (int n2 = 0; n2 < N2; ++n2) {
-      const double c = cosm(k2, n2, N2), s = sinm(k2, n2, N2);
-      T[(size_t)k2 * 2 * N2 + n2] = c;
-      T[(size_t)k2 * 2 * N2 + N2 + n2] = s;
-      T[(size_t)(H + k2) * 2 * N2 + n2] = -s;
-      T[(size_t)(H + k2) * 2 * N2 + N2 + n2] = c;
-    }
-  at[4] = buf->size();
-  pack_frag(T, 2 * H, 2 * N2, buf);
-  // transposed stage 1 [64][64]: Re = C Fre - S Fim, Im = S Fre + C Fim
-  T.assign(64 * 64, 0.0);
-  for (int p = 0; p < 32; ++p)
-    for (int k1 = 0; k1 < 32; ++k1) {
-      const double c = cosm(p, k1, 32), s = sinm(p, k1, 32);
-      T[p * 64 + k1] = c;
-      T[p * 64 + 32 + k1] = -s;
-      T[(32 + p) * 64 + k1] = s;
-      T[(32 + p) * 64 + 32 + k1] = c;
-    }
-  at[5] = buf->size();
-  pack_frag(T, 64, 64, buf);
-  // transposed stage 2 [N2][2 N2]: y = C Bre - S Bim (no 1 / N: this is the transpose, not the inverse)
-  T.assign((size_t)N2 * 2 * N2, 0.0);
-  for (int q = 0; q < N2; ++q)
-    for (int k2 = 0; k2 < N2; ++k2) {
-      T[(size_t)q * 2 * N2 + k2] = cosm(q, k2, N2);
-      T[(size_t)q * 2 * N2 + N2 + k2] = -sinm(q, k2, N2);
-    }
-  at[6] = buf->size();
-  pack_frag(T, N2, 2 * N2, buf);
-}
-
-// one set of tables per device, fft_length and frame_length, uploaded on first use and kept for the life of the process
+// one set of tables per device, fft_length and frame_length
 int get_tables(int N, int fl, LossTables* t) {
-  static std::mutex mu;
-  static std::map<std::tuple<int, int, int>, LossTables> cache;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(std::make_tuple(dev, N, fl));
-  if (it == cache.end()) {
-    std::vector<float> buf;
-    size_t at[7];
-    build_tables(N, fl, &buf, at);
-    float* d = nullptr;
-    HIP_TRY(hipMalloc(&d, buf.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(d, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
-    LossTables s{d + at[0], d + at[1], d + at[2], d + at[3], d + at[4], d + at[5], d + at[6]};
-    it = cache.emplace(std::make_tuple(dev, N, fl), s).first;
-  }
-  *t = it->second;
-  return 0;
+  static TableCache<std::pair<int, int>, LossTables> cache;
+  return cache.get({N, fl}, t, [N, fl](std::vector<float>* buf) {
+    const size_t win = buf->size();
+    append_hann(fl, N, 0, false, buf);
+    const DftOffsets at = append_dft_tables(N, 1.0, buf);
+    return [=](const float* d) { return LossTables{d + win, dft_pointers(d, at)}; };
+  });
 }
 
 template <bool GRAD>
@@ -500,10 +377,6 @@ int launch_loss_frames(int N, const LossFrameArgs& a, int B, hipStream_t s) {
   HIP_TRY(hipGetLastError());
   return 0;
 }
-
-constexpr int64_t kMaxCols = ((int64_t)1 << 31) - 65536;
-
-size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct LossPlan {
   LossRes res[kMaxRes];
@@ -517,7 +390,7 @@ int loss_plan(int32_t B, int64_t Lpad, int32_t R, const int32_t* fft, const int3
   if (!fft || !fl || !step) return fail(MI355ASR_EINVAL, "stft_loss: null pointer in the resolution arrays");
   if (R < 1 || R > kMaxRes) return fail(MI355ASR_EINVAL, "stft_loss: need 1 <= resolutions <= %d (got %d)", kMaxRes, R);
   if (B < 1 || B > 65535) return fail(MI355ASR_EINVAL, "stft_loss: need 1 <= B <= 65535 (got %d)", B);
-  if (Lpad < 1 || Lpad > kMaxCols) return fail(MI355ASR_EINVAL, "stft_loss: need 1 <= Lpad < 2^31 - 65536 (got %lld)", (long long)Lpad);
+  if (Lpad < 1 || Lpad > kMaxExtent32) return fail(MI355ASR_EINVAL, "stft_loss: need 1 <= Lpad < 2^31 - 65536 (got %lld)", (long long)Lpad);
   size_t o = 0;
   for (int r = 0; r < R; ++r) {
     if (fft[r] != 512 && fft[r] != 1024 && fft[r] != 2048)
@@ -530,15 +403,15 @@ int loss_plan(int32_t B, int64_t Lpad, int32_t R, const int32_t* fft, const int3
     q.fl = fl[r]; q.step = step[r]; q.bins = fft[r] / 2 + 1;
     q.Fpad = Lpad >= fl[r] ? 1 + (int)((Lpad - fl[r]) / step[r]) : 0;
     q.part_off = o / sizeof(double);
-    o += up256((size_t)B * q.Fpad * 3 * sizeof(double));
+    o += align256((size_t)B * q.Fpad * 3 * sizeof(double));
   }
   p->norms_off = o;
-  o += up256((size_t)B * R * 2 * sizeof(double));
+  o += align256((size_t)B * R * 2 * sizeof(double));
   p->fr_bytes_off = o;
   size_t fo = 0;
   for (int r = 0; r < R; ++r) {
     p->res[r].fr_off = fo / sizeof(float);
-    if (want_grad) fo += up256((size_t)B * p->res[r].Fpad * p->res[r].fl * sizeof(float));
+    if (want_grad) fo += align256((size_t)B * p->res[r].Fpad * p->res[r].fl * sizeof(float));
   }
   p->total = o + fo;
   return 0;
@@ -617,7 +490,7 @@ int mi355asr_vad_mask_stats(const float* labels_dev, int64_t ld_lab, const float
   if (!labels_dev) return fail(MI355ASR_EINVAL, "vad_mask_stats: null pointer labels_dev");
   if (!logits_dev) return fail(MI355ASR_EINVAL, "vad_mask_stats: null pointer logits_dev");
   if (!sums_dev || !counts_out_dev) return fail(MI355ASR_EINVAL, "vad_mask_stats: null output pointer (sums_dev, counts_out_dev)");
-  if (B < 1 || T < 1 || (int64_t)B * T > kMaxCols) return fail(MI355ASR_EINVAL, "vad_mask_stats: need B, T >= 1 and B * T < 2^31 - 65536 (got %d, %d)", B, T);
+  if (B < 1 || T < 1 || (int64_t)B * T > kMaxExtent32) return fail(MI355ASR_EINVAL, "vad_mask_stats: need B, T >= 1 and B * T < 2^31 - 65536 (got %d, %d)", B, T);
   if (ld_lab < 0 || ld_x < 0 || (B > 1 && (ld_lab < T || ld_x < T)))
     return fail(MI355ASR_EINVAL, "vad_mask_stats: the row strides ld_lab=%lld, ld_x=%lld are smaller than T=%d", (long long)ld_lab, (long long)ld_x, T);
   if (grad_dev && B > 1 && ld_grad < T) return fail(MI355ASR_EINVAL, "vad_mask_stats: ld_grad=%lld lets the gradient rows overlap", (long long)ld_grad);

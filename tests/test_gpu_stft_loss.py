@@ -100,6 +100,43 @@ def test_accuracy_line(accuracy):
         assert mine <= 4.0 * yard, (key, mine, yard)
 
 
+@pytest.mark.parametrize("geo,L,res,seed", [((1024, 800, 160), 2400, (1024, 600, 120), 7), ((2048, 2048, 512), 4100, (2048, 2048, 512), 8)])
+def test_the_stft_pair_and_the_loss_keep_their_own_tables(gpu, geo, L, res, seed):
+    """csrc/stft.hip and csrc/stft_loss.hip build their tables with one builder and upload them through one cache, each under its
+    own keys: at the same N the last stage differs by the factor N (the inverse against the transpose) and at 1024 the window
+    too (800 centred against 600 at the start).  Both run once before either is checked, so a table served to the wrong user shows
+    whichever of the two filled its cache first."""
+    import stft_ref as sr
+    from stft_cases import U24, signal, worst_ratio
+    from test_gpu_stft_pair import C_Y
+    from tensorflowasr_amd import losses
+    from tensorflowasr_amd.stft import STFT
+    n_fft, win, hop = geo
+    row = signal(np.random.default_rng(n_fft), (1, L))
+    y, x = R.seeded_pair((1, L), seed=seed)
+    st = STFT(*geo)
+    S, frames = st.forward(row, [L])
+    back, out_len = st.inverse(S, frames)
+    fn = losses.MultiResolutionSTFTLoss((res[0],), (res[1],), (res[2],))
+    _, grad = fn(torch.from_numpy(y).to(gpu), torch.from_numpy(x).to(gpu), return_grad=True)
+    # the round trip, as test_gpu_stft_pair.test_round_trip_parity_lengths_and_zeros forms it
+    F = sr.n_frames(L, n_fft, hop)
+    want_len = hop * (F - 1)
+    assert F > 1 and int(frames.cpu()[0]) == F and int(out_len.cpu()[0]) == want_len
+    want = sr.istft(sr.stft(row[0], *geo), *geo)
+    scale = U24 * sr.ola_scale(sr.frame_l1(row[0], *geo), *geo)
+    trip = worst_ratio(np.abs(back.cpu().numpy()[0, :want_len] - want), scale)
+    # the gradient, as test_accuracy_line forms it
+    g64 = R.loss_and_grad(y, x, None, (res,))[1]
+    ty, tx = torch.from_numpy(y), torch.from_numpy(x).requires_grad_(True)
+    R.torch_loss(ty, tx, [L], (res,))[0].backward()
+    mine = np.abs(grad.cpu().numpy() - g64).max() / np.abs(g64).max()
+    yard = np.abs(tx.grad.numpy() - g64).max() / np.abs(g64).max()
+    print("tables %d: round trip ratio %.4f (line %.2f), gradient kernel %.3e torch-float32 %.3e" % (n_fft, trip, C_Y, mine, yard))
+    assert trip <= C_Y
+    assert yard > 0.0 and mine <= 4.0 * yard, (mine, yard)
+
+
 def test_fixture_inputs_give_the_reference_float32_scalar(gpu, accuracy):
     golden = np.load(R.__file__.replace("stft_loss_ref.py", "golden/stft_loss_ref.npz"))
     fn = make("pair")
